@@ -2,13 +2,21 @@
 """bench.py -- MPN-forward edges/s on MI355X, with the roofline of the dominant kernel and the CPU baseline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|s02|s02_L1|s02_tracker|cfg4|cfg5]
+                    [--full [--no-stress] [--no-cpu]] [--dump-outputs DIR]
 
 A step = one full `MOTMPNet.forward` (all L rounds, eval mode, inputs resident in HBM).  Metric and
 workloads are BASELINE.json's: at 1 GPU the AIC19-S02 graph (ground-truth topology 124/90/99/137
-tracklets -> N=450, E=150 454; the real tracker files are not available offline) at L=3, Cs=1; the same
-run also reports the 100k-node / 10M-edge stress graph (config 4) under "stress".  With --gpus N > 1 the
-1M-node / 100M-edge graph (config 5) is edge-range partitioned over the ranks (strong scaling).
+tracklets -> N=450, E=150 454; the real tracker files are not available offline) at L=3, Cs=1.  With
+--gpus N > 1 the 1M-node / 100M-edge graph (config 5) is edge-range partitioned over the ranks (strong scaling).
 Rank 0 prints ONE JSON line.
+
+A plain 1-GPU run measures the headline and nothing else: set-up, W warm-up steps, EXACTLY K timed steps (in the faster
+way of launching the forward, chosen by a short probe of both), the result line.  --full adds everything else, as one
+line: the roofline of the dominant kernel from per-phase timings, the box's measured HBM peak, the CPU baseline, the
+uncached and exact-fp32 legs, and (workload auto, without --no-stress) the 100k-node / 10M-edge stress graph (config 4)
+under "stress", config 5 on this one GPU, the other config-2 legs, graph build, training step and post-processing.
+--dump-outputs DIR writes what the timed path returned in its last step (per-step logits and the latent node features)
+as DIR/<name>.npy in float32; above 64 MB in all, the same fixed, seeded sample of rows of every array.
 """
 import argparse
 import copy
@@ -166,10 +174,11 @@ def percentiles(v):
     return {"median": v[n // 2], "p10": v[int(0.1 * (n - 1))], "p90": v[int(round(0.9 * (n - 1)))], "min": v[0], "max": v[-1]}
 
 
-def time_forward(model, data, steps, warmup, dist=None, fn=None):
+def time_forward(model, data, steps, warmup, dist=None, fn=None, keep=None):
     """W untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides (the driver's contract):
     returns (seconds per step from the wall clock, per-step GPU milliseconds from HIP events recorded on the launch
-    stream between consecutive steps -> median / p10 / p90)."""
+    stream between consecutive steps -> median / p10 / p90).  `keep` (a dict): receives what the LAST
+    timed step returned under "result" (the earlier steps' results are dropped as they come, as without it)."""
     dev = data.x.device
     fn = fn or (lambda: model(data))
     with torch.no_grad():
@@ -183,14 +192,48 @@ def time_forward(model, data, steps, warmup, dist=None, fn=None):
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(steps):
-            fn()
+            r = fn()
             marks[i + 1].record()
+            if i + 1 < steps:
+                del r
         torch.cuda.synchronize(dev)
         if dist is not None:
             dist.barrier()
         t1 = time.perf_counter()
+    if keep is not None and steps > 0:
+        keep["result"] = r
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]
     return (t1 - t0) / steps, percentiles(per_step)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def sample_outputs(result, budget=DUMP_BYTES):
+    """What a caller of the timed forward receives, `(outputs, latent_node_feats)`, as float32 arrays on the host:
+    {"classified_edges_<i>": [E, 2] per classified step, "latent_node_feats": [N, 32]}.  Above `budget` bytes in all, every
+    array keeps the same share of its rows, chosen by a fixed seed (the same rows for arrays of the same length)."""
+    import numpy as np
+    outputs, h = result
+    arrays = {f"classified_edges_{i}": t for i, t in enumerate(outputs["classified_edges"])}
+    arrays["latent_node_feats"] = h
+    total = sum(t.numel() * 4 for t in arrays.values())
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if total > budget:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))
+            rows = rows[:max(1, t.shape[0] * budget // total)].sort().values
+            t = t[rows.to(t.device)]
+        out[name] = np.ascontiguousarray(t.to(torch.float32).cpu().numpy())
+    return out
+
+
+def write_outputs(outdir, arrays):
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def hbm_probe(device, gib=2, reps=20):
@@ -334,25 +377,66 @@ def panel_times(model, data, reps=5):
     return tot / reps, n_panels
 
 
-def run_single(name, device, steps, warmup, with_cpu=True, phase_iters=20, legs=True):
+def setup_workload(name, device):
+    """The seeded model (random-init weights, torch.manual_seed(0)) and the workload's inputs on `device`."""
     desc, L, cs = WORKLOADS[name]
     params = mtmc_mpn.default_params(num_enc_steps=L, num_class_steps=cs)
     torch.manual_seed(0)
     model = mtmc_mpn.MOTMPNet(copy.deepcopy(params), None, ARCH).to(device).eval()
     model.deterministic = bool(os.environ.get("MTMC_DETERMINISTIC"))
-    data = make_workload(name, device)
+    return params, model, make_workload(name, device)
+
+
+def graph_replay_eligible(e):
+    # few-edge graphs: ~20 launches per forward can cost the host more than the forward costs the GPU; the same
+    # forward replayed from a HIP graph (model.capture) is immune to that -- report the faster way of launching it
+    return e <= 2_000_000 and not os.environ.get("MTMC_NO_GRAPH")
+
+
+def run_headline(name, device, steps, warmup, dump=False, probe_steps=200):
+    """The plain run: what the headline figure needs and nothing else.  Where both ways of launching the forward apply,
+    a probe of `probe_steps` steps of each picks the faster; then W warm-up steps and EXACTLY `steps` timed steps of it."""
+    desc, L, cs = WORKLOADS[name]
+    params, model, data = setup_workload(name, device)
     n, e = data.x.shape[0], data.edge_index.shape[1]
-    sec, dist_ms = time_forward(model, data, steps, warmup)
-    launch_mode, eager_ms, replay_ms = "eager launches", sec * 1e3, None
-    if e <= 2_000_000 and not os.environ.get("MTMC_NO_GRAPH"):
-        # few-edge graphs: ~20 launches per forward can cost the host more than the forward costs the GPU; the same
-        # forward replayed from a HIP graph (model.capture) is immune to that -- report the faster way of launching it
+    fn, launch = None, {"mode": "eager launches"}
+    if graph_replay_eligible(e):
+        # eager first, then capture and replay, as in run_single: no eager forward runs between the capture and its replays
+        eager_sec, _ = time_forward(model, data, probe_steps, 3)
         with torch.no_grad():
             replay = model.capture(data)
-        r_sec, r_dist = time_forward(model, data, steps, warmup, fn=replay)
+        replay_sec, _ = time_forward(model, data, probe_steps, 3, fn=replay)
+        launch.update({"probe_eager_ms": eager_sec * 1e3, "probe_graph_replay_ms": replay_sec * 1e3, "probe_steps": probe_steps})
+        if replay_sec < eager_sec:
+            fn, launch["mode"] = replay, "HIP graph replay (model.capture)"
+    kept = {}
+    sec, dist_ms = time_forward(model, data, steps, warmup, fn=fn, keep=kept)
+    res = {"workload": name, "description": desc, "N": n, "E": e, "L": L, "Cs": cs,
+           "value": e / sec, "ms_per_step": sec * 1e3, "edge_rounds_per_s": e * L / sec,
+           "launch": launch, "step_ms": {k: round(v, 5) for k, v in dist_ms.items()}}
+    if dump:
+        res["outputs"] = sample_outputs(kept["result"])
+    return res
+
+
+def run_single(name, device, steps, warmup, with_cpu=True, phase_iters=20, legs=True, dump=False):
+    desc, L, cs = WORKLOADS[name]
+    params, model, data = setup_workload(name, device)
+    n, e = data.x.shape[0], data.edge_index.shape[1]
+    kept = {} if dump else None              # (--dump-outputs: the last step of whichever way of launching is reported)
+    sec, dist_ms = time_forward(model, data, steps, warmup, keep=kept)
+    outputs = sample_outputs(kept.pop("result")) if dump else None
+    launch_mode, eager_ms, replay_ms = "eager launches", sec * 1e3, None
+    if graph_replay_eligible(e):
+        with torch.no_grad():
+            replay = model.capture(data)
+        r_sec, r_dist = time_forward(model, data, steps, warmup, fn=replay, keep=kept)
         replay_ms = r_sec * 1e3
         if replay_ms < eager_ms:
             sec, dist_ms, launch_mode = r_sec, r_dist, "HIP graph replay (model.capture)"
+            outputs = sample_outputs(kept["result"]) if dump else None
+        if dump:
+            kept.clear()
     seq, ms = time_phases(model, data, phase_iters)
     spec = model.spec
     # dominant kernel = the kernel NAME with the largest summed time (all its launches in a step, the same
@@ -465,6 +549,8 @@ def run_single(name, device, steps, warmup, with_cpu=True, phase_iters=20, legs=
     if with_cpu:
         sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
         res["cpu_baseline"] = cpu_baseline(name, params, sd, data)
+    if dump:
+        res["outputs"] = outputs
     del data, model
     torch.cuda.empty_cache()
     return res
@@ -476,7 +562,7 @@ def exact_fp32_leg(name, steps, warmup):
     import subprocess
     env = dict(os.environ, MTMC_GEMM_FP32="1", MTMC_BENCH_CHILD="1")
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", str(warmup),
-           "--no-cpu", "--no-stress"]
+           "--full", "--no-cpu", "--no-stress"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         return json.loads(r.stdout.strip().splitlines()[-1])["ms_per_step"]
@@ -689,6 +775,8 @@ def self_launch_command(args, port=None):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--workload", args.workload]
+    if getattr(args, "full", False):
+        cmd.append("--full")
     if args.no_stress:
         cmd.append("--no-stress")
     if args.no_cpu:
@@ -720,14 +808,29 @@ def launch_or_refuse(args):
     return subprocess.run(cmd).returncode                   # children inherit stdout: rank 0's JSON line is ours
 
 
+def result_line(args, name, res):
+    """The fields every 1-GPU result line opens with (plain and --full alike)."""
+    return {"metric": "MPN forward edges/sec (+ achieved roofline fraction of the dominant kernel)",
+            "value": res["value"], "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic (seeded features on the reference's S02 ground-truth topology; random-init weights)",
+            "config": {"workload": f"{name}: {res['description']}, L={res['L']}, Cs={res['Cs']}, eval forward",
+                       "N": res["N"], "E": res["E"], "parallelism": "1 GPU"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="auto")
-    ap.add_argument("--no-stress", action="store_true", help="skip the config-4 stress graph in the 1-GPU run")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline, HBM probe, CPU baseline, extra legs and (workload auto) the other "
+                         "workloads, training step, graph build and post-processing")
+    ap.add_argument("--no-stress", action="store_true", help="--full: skip the config-4 stress graph and the other extra workloads")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed forward returned in its last step to DIR/<name>.npy (float32, 64 MB at most)")
     ap.add_argument("--train-graph-child", action="store_true", help=argparse.SUPPRESS)   # (training_graph_leg's child)
     args = ap.parse_args()
     if args.train_graph_child:
@@ -735,10 +838,14 @@ def main():
         print(json.dumps(training_graph_child(torch.device("cuda:0"))))
         return
 
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (args.gpus > 1 or world > 1 or os.environ.get("MTMC_BENCH_FORCE_DIST")):
+        print("bench.py: --dump-outputs is for the 1-GPU run (the ranks of --gpus N each hold a shard of the edges)",
+              file=sys.stderr)
+        sys.exit(2)
     rc = launch_or_refuse(args)
     if rc is not None:
         sys.exit(rc)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 or world > 1 or os.environ.get("MTMC_BENCH_FORCE_DIST"):
         from bench_dist import main_distributed   # multi-GPU leg lives beside this file
         return main_distributed(args)
@@ -746,20 +853,27 @@ def main():
     device = torch.device("cuda:0")
     torch.cuda.set_device(device)
     name = "s02" if args.workload == "auto" else args.workload
+    if not args.full:
+        res = run_headline(name, device, args.steps, args.warmup, dump=bool(args.dump_outputs))
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, res.pop("outputs"))
+        line = result_line(args, name, res)
+        line.update({"launch": res["launch"], "edge_rounds_per_s": res["edge_rounds_per_s"], "step_ms": res["step_ms"]})
+        print(json.dumps(line))
+        return
+
     probe = hbm_probe(device)
     child = bool(os.environ.get("MTMC_BENCH_CHILD"))
-    res = run_single(name, device, args.steps, args.warmup, with_cpu=not args.no_cpu, legs=not child)
+    res = run_single(name, device, args.steps, args.warmup, with_cpu=not args.no_cpu, legs=not child,
+                     dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, res.pop("outputs"))
     add_measured_peak(res, probe)
-    line = {"metric": "MPN forward edges/sec (+ achieved roofline fraction of the dominant kernel)",
-            "value": res["value"], "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic (seeded features on the reference's S02 ground-truth topology; random-init weights)",
-            "config": {"workload": f"{name}: {res['description']}, L={res['L']}, Cs={res['Cs']}, eval forward",
-                       "N": res["N"], "E": res["E"], "parallelism": "1 GPU"},
-            "roofline": res["roofline"], "cpu_baseline": res.get("cpu_baseline"), "launch": res["launch"],
-            "forward_algorithmic": res["forward_algorithmic"], "edge_rounds_per_s": res["edge_rounds_per_s"],
-            "phase_ms": res["phase_ms"], "step_ms": res["step_ms"], "hbm_probe": probe, "plan": res["plan"],
-            "weight_plane_cache": res["weight_plane_cache"], "ms_per_step_uncached": res.get("ms_per_step_uncached")}
+    line = result_line(args, name, res)
+    line.update({"roofline": res["roofline"], "cpu_baseline": res.get("cpu_baseline"), "launch": res["launch"],
+                 "forward_algorithmic": res["forward_algorithmic"], "edge_rounds_per_s": res["edge_rounds_per_s"],
+                 "phase_ms": res["phase_ms"], "step_ms": res["step_ms"], "hbm_probe": probe, "plan": res["plan"],
+                 "weight_plane_cache": res["weight_plane_cache"], "ms_per_step_uncached": res.get("ms_per_step_uncached")})
     if "roofline_longest_launch" in res:
         line["roofline_longest_launch"] = res["roofline_longest_launch"]
     if not child and not args.no_stress:

@@ -39,3 +39,34 @@ def test_self_launch_command_is_the_drivers():
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[cmd.index("--master-port") + 1] == "29999"
     tail = cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:]
     assert tail == ["--gpus", "4", "--steps", "7", "--warmup", "2", "--workload", "auto", "--no-cpu"]
+
+
+def test_full_reaches_the_ranks_it_starts():
+    sys.path.insert(0, ROOT)
+    import bench
+    args = types.SimpleNamespace(gpus=2, steps=7, warmup=2, workload="auto", no_stress=True, no_cpu=False, full=True)
+    cmd = bench.self_launch_command(args, port=29999)
+    assert cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:] == [
+        "--gpus", "2", "--steps", "7", "--warmup", "2", "--workload", "auto", "--full", "--no-stress"]
+
+
+def test_dumped_outputs_are_float32_and_capped_by_one_seeded_sample():
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(1)
+    res = ({"classified_edges": [torch.randn(5000, 2, generator=g), torch.randn(5000, 2, generator=g)]},
+           torch.randn(300, 32, generator=g))
+    whole = bench.sample_outputs(res)
+    assert sorted(whole) == ["classified_edges_0", "classified_edges_1", "latent_node_feats"]
+    assert all(a.dtype == np.float32 for a in whole.values())
+    assert np.array_equal(whole["classified_edges_1"], res[0]["classified_edges"][1].numpy())
+    budget = 40_000
+    a, b = bench.sample_outputs(res, budget=budget), bench.sample_outputs(res, budget=budget)
+    assert sum(x.nbytes for x in a.values()) <= budget
+    assert all(np.array_equal(a[k], b[k]) for k in a)                         # the same rows from run to run
+    rows = [int(np.flatnonzero((res[0]["classified_edges"][0].numpy() == r).all(1))[0]) for r in a["classified_edges_0"][:50]]
+    assert rows == sorted(rows)
+    # arrays of the same length keep the same rows
+    assert np.array_equal(a["classified_edges_1"][:50], res[0]["classified_edges"][1].numpy()[rows])

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 for wl in cfg4 cfg5; do
   for mode in 0 1 2 3 1 0; do
     steps=20; [ $wl = cfg5 ] && steps=6
-    MTMC_L0_PIPELINE=$mode python3 $ROOT/bench.py --workload $wl --steps $steps --warmup 3 --no-cpu 2>/dev/null | python3 -c "
+    MTMC_L0_PIPELINE=$mode python3 $ROOT/bench.py --full --workload $wl --steps $steps --warmup 3 --no-cpu 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$wl mode $mode: %.4f ms  (median %.4f)  begin %.3f  gemm0 %.3f' % (d['ms_per_step'], d['step_ms']['median'], d['phase_ms'].get('memset+prep_kernel(+split_rows_kernel)', 0), d['phase_ms'].get('gemm_f16p_m16_kernel[0]', 0)))

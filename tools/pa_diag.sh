@@ -10,7 +10,7 @@ cd $ROOT && patch -p1 < tools/pa_diag.patch > /dev/null
 export MTMC_NO_COL_BLOCKS=1 MTMC_SKIP_ISA_LINT=1
 for d in 0 1 2 3 4; do
   (cd $CS && rm -f edge_kernels.o && make -s EXTRA="-DPA_DIAG=$d" libmtmc_mpn.so > /dev/null 2>&1)
-  python3 $ROOT/bench.py --workload cfg5 --steps 4 --warmup 2 --no-cpu 2>/dev/null | python3 -c "
+  python3 $ROOT/bench.py --full --workload cfg5 --steps 4 --warmup 2 --no-cpu 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('PA_DIAG=$d: forward %.3f ms  pass_a (3 launches) %.3f ms  pass_b %.3f  pass_c %.3f' % (d['ms_per_step'], d['phase_ms'].get('pass_a_kernel', 0), d['phase_ms'].get('pass_b_kernel', 0), d['phase_ms'].get('pass_c_kernel', 0)))

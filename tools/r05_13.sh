@@ -7,7 +7,7 @@ tail -n 3 $OUT/r05_t13.log
 for rep in 1 2 3; do
   for nr in 1 0; do
     if [ $nr = 1 ]; then export MTMC_NO_PREP_RIDE=1; else unset MTMC_NO_PREP_RIDE; fi
-    python3 bench.py --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
+    python3 bench.py --full --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('s02 NO_PREP_RIDE=$nr: %.4f ms  (median %.4f, p10 %.4f) replay %s' % (d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10'], d['launch']['graph_replay_ms']))

@@ -9,7 +9,7 @@ tail -n 3 $OUT/r05_t10.log
 for rep in 1 2 3; do
   for which in nohoist base projmfma; do
     if [ $which = base ]; then unset MTMC_MPN_LIB; else export MTMC_MPN_LIB=$ROOT/build_ab/$which/pkg/csrc/libmtmc_mpn.so; fi
-    python3 bench.py --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
+    python3 bench.py --full --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('s02 $which: %.4f ms  (median %.4f, p10 %.4f)' % (d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10']), {k: v for k, v in d['phase_ms'].items() if 'node_proj' in k or 'pass' in k})

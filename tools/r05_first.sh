@@ -11,7 +11,7 @@ tail -5 $OUT/r05_t2.log
 for rep in 1 2; do
   for which in old new; do
     if [ $which = old ]; then export MTMC_GEMM_NO_FEW=1; else unset MTMC_GEMM_NO_FEW; fi
-    python3 bench.py --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>/dev/null | python3 -c "
+    python3 bench.py --full --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('s02 $which: %.4f ms  (median %.4f, p10 %.4f)  eager %.4f  replay %s' % (d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10'], d['launch']['eager_ms'], d['launch']['graph_replay_ms']))

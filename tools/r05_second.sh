@@ -12,7 +12,7 @@ ab() {  # workload steps
   for rep in 1 2 3; do
     for which in swzold new; do
       if [ $which = swzold ]; then export MTMC_MPN_LIB=$ROOT/build_ab/swzold/pkg/csrc/libmtmc_mpn.so; else unset MTMC_MPN_LIB; fi
-      python3 bench.py --workload $1 --steps $2 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
+      python3 bench.py --full --workload $1 --steps $2 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1 $which: %.4f ms  (median %.4f, p10 %.4f)' % (d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10']), {k: v for k, v in d['phase_ms'].items() if 'gemm' in k or 'few' in k})
@@ -25,7 +25,7 @@ unset MTMC_MPN_LIB
 for rep in 1 2 3; do
   for which in old new; do
     if [ $which = old ]; then export MTMC_GEMM_NO_FEW=1; else unset MTMC_GEMM_NO_FEW; fi
-    python3 bench.py --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
+    python3 bench.py --full --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('s02 $which: %.4f ms  (median %.4f, p10 %.4f)  eager %.4f  replay %s' % (d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10'], d['launch']['eager_ms'], d['launch']['graph_replay_ms']))

@@ -8,7 +8,7 @@ for rep in 1 2; do
   MTMC_FEW_ROWS_MAX=4095 python3 tools/few_crossover.py 2>/dev/null
   MTMC_GEMM_NO_FEW=1 python3 tools/few_crossover.py 2>/dev/null
 done | tee $OUT/r05_few_crossover.txt
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r05_bench_default.json 2> $OUT/r05_bench_default.err; echo "bench: $?"
+timeout -k 10 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r05_bench_default.json 2> $OUT/r05_bench_default.err; echo "bench: $?"
 tail -n 3 $OUT/r05_bench_default.err
 python3 - <<'PY'
 import json

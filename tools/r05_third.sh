@@ -15,7 +15,7 @@ cat $OUT/r05_few_stamps2.txt
 for rep in 1 2 3; do
   for cfg in "1 1" "2 1" "1 2" "2 2"; do
     set -- $cfg
-    MTMC_FEW_L0_WN=$1 MTMC_FEW_WAVE_RB=$2 python3 bench.py --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
+    MTMC_FEW_L0_WN=$1 MTMC_FEW_WAVE_RB=$2 python3 bench.py --full --workload s02 --steps 100 --warmup 10 --no-cpu --no-stress 2>$OUT/r05_bench_err.log | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('s02 WN=$1 RB=$2: %.4f ms  (median %.4f, p10 %.4f)' % (d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10']), {k: v for k, v in d['phase_ms'].items() if 'few' in k or 'prep' in k})

@@ -21,7 +21,7 @@ for wl in ${WORKLOADS:-s02 cfg4 cfg5}; do
   echo "$wl done"
 done
 # the bench command itself (headline workload only) and the training step
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/bench_stats -o bench --output-format csv -- python3 $ROOT/bench.py --no-stress --no-cpu > $OUT/bench_stats.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/bench_stats -o bench --output-format csv -- python3 $ROOT/bench.py --full --no-stress --no-cpu > $OUT/bench_stats.log 2>&1
 trim $OUT/bench_stats/bench_kernel_stats.csv $ROOT/gpurun_out/${ROUND}_bench_s02_kernel_stats.csv
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/train -o train --output-format csv -- python3 $ROOT/tools/train_loop.py 100 > $OUT/train.log 2>&1
 trim $OUT/train/train_kernel_stats.csv $ROOT/gpurun_out/${ROUND}_train_kernel_stats.csv

@@ -4,7 +4,7 @@
 # workgroups, 2 / 8 slots per lane and trip; none better than the shipped 1024 workgroups x 4 slots with streaming stores).
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 run() {
-  python3 $ROOT/bench.py --workload cfg5 --steps 6 --warmup 3 --no-cpu --no-stress 2>/dev/null | python3 -c "
+  python3 $ROOT/bench.py --full --workload cfg5 --steps 6 --warmup 3 --no-cpu --no-stress 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1: %.4f ms (median %.4f)  pass_a %.3f' % (d['ms_per_step'], d['step_ms']['median'], d['phase_ms'].get('pass_a_kernel', 0)))
