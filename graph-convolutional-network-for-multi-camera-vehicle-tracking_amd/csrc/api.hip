@@ -144,61 +144,22 @@ int32_t mtmc_mpn_plan_call(const mtmc_mpn_model* model, const mtmc_mpn_call* cal
   if (c->n_nodes < 0 || c->n_edges < 0 || c->n_edges > c->n_edges_total || c->node_lo < 0 || c->node_hi < c->node_lo ||
       c->node_hi > c->n_nodes || c->row_lo < 0 || c->row_hi < c->row_lo || c->row_hi > c->n_nodes)
     return fail(MTMC_E_ARG, "mtmc_mpn_plan_call: sizes / ranges out of order");
-  *out = mtmc_mpn_plan();
-  const int64_t rows = c->node_hi - c->node_lo;
-  const bool pre0 = !c->training && mtmc::presplit_layer0(c->n_nodes, model->enc_node[0].in_dim, model->enc_node[0].out_dim) &&
-                    mtmc::presplit_layer0(rows, model->enc_node[0].in_dim, model->enc_node[0].out_dim);
+  Layout lo;                   // (host-only: offsets and flags, nothing is allocated)
   CacheLayout cl;
+  CallPlan p;                  // what mtmc_mpn_forward would run (make_ctx builds the same plan)
+  make_layout(model, c->n_nodes, c->n_edges, &lo, c->training != 0);
   make_cache_layout(model, &cl);
-  bool few = c->weight_cache != nullptr && few_shape(model, c->n_nodes) && few_shape(model, rows);   // use_few (training too)
-  for (int l = 0; l < model->n_enc_layers; ++l) few = few && cl.has[l];
-  for (int l = 0; l < model->n_enc_layers; ++l) {
-    const mtmc_layer& L = model->enc_node[l];
-    if (few) {
-      out->enc_kernel[l] = l == 0 ? MTMC_GEMM_FEW_L0 : MTMC_GEMM_FEW_WAVE;
-      out->enc_split_k[l] = 1;
-      continue;
-    }
-    int sk_full = 1, sk_here = 1;
-    mtmc::gemm_plan(c->n_nodes, L.in_dim, L.out_dim, &sk_full);
-    const int cfg = rows > 0 ? mtmc::gemm_plan(rows, L.in_dim, L.out_dim, &sk_here) : 0;
-    const bool slab = sk_here > 1 && (size_t)sk_here * rows <= (size_t)(sk_full > 1 ? sk_full : 0) * c->n_nodes;   // run_phase
-    const bool stg = l >= 1 && !c->training && mtmc::staged_layer(c->n_nodes, L.in_dim, L.out_dim) && mtmc::staged_layer(rows, L.in_dim, L.out_dim);
-    const bool rws = l >= 1 && !c->training && mtmc::rows_layer(c->n_nodes, L.in_dim, L.out_dim) && mtmc::rows_layer(rows, L.in_dim, L.out_dim);
-    out->enc_kernel[l] = (l == 0 && pre0) ? MTMC_GEMM_PRESPLIT_256 : stg ? MTMC_GEMM_STAGED_128 : rws ? MTMC_GEMM_ROWS_16 : cfg == 2 ? MTMC_GEMM_INLOOP_128 : cfg == 1 ? MTMC_GEMM_INLOOP_64
-                                                                                                           : MTMC_GEMM_GENERIC;
-    out->enc_split_k[l] = ((l == 0 && pre0) || stg || rws || !slab) ? 1 : sk_here;
-  }
-  out->edges_per_thread = mtmc::plan_edges_per_thread(c->n_edges);
-  out->lazy_edges = lazy_edges(c) ? 1 : 0;
-  out->avg_degree = avg_degree(c);
-  out->pass_a_col_blocks = (model->num_enc_steps > 0 && mtmc::plan_col_blocks(c->n_nodes, c->n_edges, 1e30, c->training != 0) > 0)
-                               ? mtmc::plan_col_blocks(c->n_nodes, c->n_edges, out->avg_degree, c->training != 0) : 0;
-  const bool drop_n = c->training && model->dropout_upd_node > 0.f;
-  // the public enum names what launch_pass_c launches: the sorted kernel is MFMA_SORTED, the any-order kernel MFMA_ANY
-  // (on a many-edge list it still has the walk launched behind it for unsorted rows)
-  const int pc = mtmc::plan_pass_c(model->agg, (c->flags & MTMC_F_DETERMINISTIC) != 0, drop_n, c->n_edges, c->n_nodes, out->avg_degree);
-  out->pass_c = pc == 1 ? (mtmc::pass_c_sorted_taken(c->n_nodes) ? MTMC_PASS_C_MFMA_SORTED : MTMC_PASS_C_MFMA_ANY) : pc;
-  out->node_stat_folded = mtmc::fold_node_stat(c->n_edges) ? 1 : 0;
-  out->layer0_panels = 1;
-  if (pre0 && mtmc::knobs().l0_pipeline > 0) {
-    int64_t cuts[kMaxPanels + 1];
-    int bm;
-    out->layer0_panels = l0_panels(rows, model->enc_node[0].out_dim, cuts, &bm);
-  }
-  {   // (enc2_can_ride without a Ctx: the same conditions on sizes alone)
-    const int last = model->n_enc_layers - 1;
-    const mtmc_layer& L = model->enc_node[last];
-    int sk;
-    const bool big_last = (last == 0 && pre0) ||
-                          (last >= 1 && !c->training && ((mtmc::staged_layer(c->n_nodes, L.in_dim, L.out_dim) && mtmc::staged_layer(rows, L.in_dim, L.out_dim)) ||
-                                                         (mtmc::rows_layer(c->n_nodes, L.in_dim, L.out_dim) && mtmc::rows_layer(rows, L.in_dim, L.out_dim))));
-    out->enc2_passenger = (c->n_edges > 0 && rows > 0 && c->n_edges <= mtmc::kSmallEdges && !big_last &&
-                           mtmc::gemm_plan(rows, L.in_dim, L.out_dim, &sk) == 1 && !(c->flags & MTMC_F_FORK)) ? 1 : 0;
-    if (few)
-      out->enc2_passenger = (c->n_edges > 0 && c->n_edges <= mtmc::kSmallEdges && last >= 1 &&
-                             mtmc::few_wave_threads(L.in_dim) == 256 && !(c->flags & MTMC_F_FORK)) ? 1 : 0;
-  }
+  make_plan(model, c, lo, cl, &p);
+  *out = mtmc_mpn_plan();
+  for (int l = 0; l < model->n_enc_layers; ++l) { out->enc_kernel[l] = p.enc_kernel[l]; out->enc_split_k[l] = p.enc_split_k[l]; }
+  out->edges_per_thread = p.edges_per_thread;
+  out->lazy_edges = p.lazy_edges ? 1 : 0;
+  out->avg_degree = p.avg_degree;
+  out->pass_a_col_blocks = p.col_blocks;
+  out->pass_c = p.pass_c_pub;
+  out->node_stat_folded = p.fold_node_stat ? 1 : 0;
+  out->layer0_panels = p.l0_panels;
+  out->enc2_passenger = (p.enc2_may_ride && !(c->flags & MTMC_F_FORK)) ? 1 : 0;     // what mtmc_mpn_forward makes of it
   return MTMC_OK;
 }
 
@@ -207,11 +168,7 @@ int32_t mtmc_mpn_forward(const mtmc_mpn_model* model, const mtmc_mpn_call* call)
   if (int rc = make_ctx(model, call, &x)) return rc;
   int rc;
   // many-row graphs: layer 0 in row panels, the operand split one panel ahead on a side stream (MTMC_L0_PIPELINE=0: off)
-  if (mtmc::knobs().l0_pipeline > 0 && use_presplit0(x)) {
-    int64_t cuts[kMaxPanels + 1];
-    int bm;
-    if (l0_panels(call->node_hi - call->node_lo, model->enc_node[0].out_dim, cuts, &bm) >= 2) x.pipe = pipe_for(x.stream);
-  }
+  if (x.plan.l0_panels >= 2) x.pipe = pipe_for(x.stream);
   Side* sd = (call->flags & MTMC_F_FORK) ? side_for_current_device() : nullptr;
   if (sd) {
     if ((rc = run_phase(x, MTMC_PH_BEGIN, 0))) return rc;      // prep also gathers the node encoder's operand scales
@@ -225,7 +182,7 @@ int32_t mtmc_mpn_forward(const mtmc_mpn_model* model, const mtmc_mpn_call* call)
     // (round 5 tried the edge part of prep_kernel as passenger of encoder layer 0, with the statistics head cleared by the operand
     //  jobs' launch instead of a memset: layer 0 took 6 us longer, the jobs alone 8.0 us against prep_kernel's 8.8 -- DESIGN.md A.5)
     if ((rc = run_phase(x, MTMC_PH_BEGIN, 0))) return rc;
-    x.enc2_rides = enc2_can_ride(x);              // few-row graphs: enc2 as passenger of the last encoder layer's launch
+    x.enc2_rides = x.plan.enc2_may_ride;          // few-row graphs: enc2 as passenger of the last encoder layer's launch
     if (!x.enc2_rides && (rc = run_phase(x, MTMC_PH_EDGE_ENC, 0))) return rc;
   }
   for (int l = 0; l < model->n_enc_layers; ++l) {

@@ -155,7 +155,7 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
   // Layer 0 of a many-row graph runs on operands split ONCE into fp16 pairs (gemm_presplit.hip): planes of x [2][N][K]
   // and of W0 [2][out][K] plus one power-of-two scale per row.  An x-sized region; eval mode only.
   lo->presplit0 = !training && mtmc::presplit_layer0(N, m->enc_node[0].in_dim, m->enc_node[0].out_dim);
-  lo->few = few_shape(m, N);                  // (the call also needs a weight-plane cache: use_few; training forwards too)
+  lo->few = few_shape(m, N);                  // (the call also needs a weight-plane cache: make_plan; training forwards too)
   if (lo->presplit0 || lo->few) {
     const size_t K0 = m->enc_node[0].in_dim, O0 = m->enc_node[0].out_dim;
     lo->xh = take((size_t)2 * N * K0 * sizeof(uint16_t));
@@ -227,14 +227,112 @@ struct SidePipe { hipStream_t stream = nullptr; hipEvent_t fork = nullptr; hipEv
 struct PanelTiming { bool on = false, created = false; hipEvent_t ev[2 * kMaxPanels]; int n = 0; };
 inline PanelTiming& panel_timing() { static PanelTiming t; return t; }
 
+// Row panels of the pipelined layer 0: cuts[0..np] (multiples of the tile height), np <= kMaxPanels; *bm = the tile height
+// of every panel (what the whole matrix would pick).  One round = 256 workgroups = 256 / tiles_n row tiles.
+inline int l0_panels(int64_t rows, int Nout, int64_t* cuts, int* bm) {
+  const int tiles_n = (Nout + 255) / 256;
+  *bm = mtmc::presplit_tile_rows(rows, tiles_n);
+  const int64_t per_round = (int64_t)(256 / tiles_n > 0 ? 256 / tiles_n : 1) * *bm;
+  const int mode = mtmc::knobs().l0_pipeline;
+  int np = 0;
+  int64_t at = 0, k = 1;
+  cuts[0] = 0;
+  while (at < rows) {
+    int64_t take = per_round * (mode == 3 ? 2 : mode == 2 ? 1 : k);
+    if (np == kMaxPanels - 1 || at + take > rows) take = rows - at;
+    at += take;
+    cuts[++np] = at;
+    if (k < 8) k *= 2;
+  }
+  return np;
+}
+
+// Which kernels one call runs, decided once (make_plan): the launches read it and mtmc_mpn_plan_call reports it.
+struct CallPlan {
+  int64_t rows;                                  // node_hi - node_lo: the rows the node encoder encodes here
+  int enc_kernel[MTMC_MAX_ENC_LAYERS];           // MTMC_GEMM_* per node-encoder layer
+  int enc_split_k[MTMC_MAX_ENC_LAYERS];          // > 1: the in-loop kernel slices K into the slab, MTMC_PH_NODE_COMBINE adds up
+  bool w_cached[MTMC_MAX_ENC_LAYERS];            // the layer's weight planes are in the weight-plane cache (else the workspace)
+  int l0_panels, l0_bm;                          // pre-split layer 0 in row panels [l0_cuts[i], l0_cuts[i+1]) of tile height l0_bm
+  int64_t l0_cuts[kMaxPanels + 1];               // (1 panel: one split pass, one GEMM)
+  bool enc2_may_ride;                            // enc2 may ride in the last encoder layer's launch (mtmc_mpn_forward decides)
+  int edges_per_thread;                          // passes A / B
+  bool lazy_edges;                               // e' is never stored: passes B / C and the next pass A recompute it from z1
+  bool fold_node_stat;                           // few-edge list: node-update statistics out of node_proj + pass B
+  double avg_degree;                             // edges per source row of this call's edges
+  int col_blocks;                                // column blocks of pass A (0: edge order)
+  int pass_c, pass_c_pub;                        // plan_pass_c (RoundParams::mfma_c) and the MTMC_PASS_C_* it amounts to
+};
+
+inline bool in_loop_kernel(int k) { return k == MTMC_GEMM_GENERIC || k == MTMC_GEMM_INLOOP_64 || k == MTMC_GEMM_INLOOP_128; }
+
+// From the call's sizes, ranges, flags and mode, the layout and the knobs.  No pointer of the call is read (weight_cache is
+// only tested for NULL), so the host-only query builds the same plan.  The layout says what the WHOLE graph qualifies for
+// (presplit0, few, staged[l]); a layer takes a kernel when this call's rows qualify too.
+inline void make_plan(const mtmc_mpn_model* m, const mtmc_mpn_call* c, const Layout& lo, const CacheLayout& cl, CallPlan* p) {
+  *p = CallPlan();
+  const int64_t N = c->n_nodes, E = c->n_edges, rows = c->node_hi - c->node_lo;
+  const mtmc_layer& L0 = m->enc_node[0];
+  p->rows = rows;
+  const bool pre0 = lo.presplit0 && mtmc::presplit_layer0(rows, L0.in_dim, L0.out_dim);
+  bool few = lo.few && c->weight_cache != nullptr && few_shape(m, rows);     // (training forwards too)
+  for (int l = 0; l < m->n_enc_layers; ++l) few = few && cl.has[l];
+  for (int l = 0; l < m->n_enc_layers; ++l) {
+    const mtmc_layer& Ll = m->enc_node[l];
+    int k, sk = 1;
+    if (few) k = l == 0 ? MTMC_GEMM_FEW_L0 : MTMC_GEMM_FEW_WAVE;
+    else if (l == 0 && pre0) k = MTMC_GEMM_PRESPLIT_256;
+    else if (l >= 1 && lo.staged[l] && mtmc::staged_layer(rows, Ll.in_dim, Ll.out_dim)) k = MTMC_GEMM_STAGED_128;
+    else if (l >= 1 && !lo.training && mtmc::rows_layer(N, Ll.in_dim, Ll.out_dim) && mtmc::rows_layer(rows, Ll.in_dim, Ll.out_dim))
+      k = MTMC_GEMM_ROWS_16;        // narrow last layers of many-row graphs
+    else {                          // the slab was sized for N rows; a shard with fewer rows may plan a larger split: then none
+      int sk_full = 1, sk_here = 1;
+      mtmc::gemm_plan(N, Ll.in_dim, Ll.out_dim, &sk_full);
+      const int cfg = rows > 0 ? mtmc::gemm_plan(rows, Ll.in_dim, Ll.out_dim, &sk_here) : 0;
+      k = cfg == 2 ? MTMC_GEMM_INLOOP_128 : cfg == 1 ? MTMC_GEMM_INLOOP_64 : MTMC_GEMM_GENERIC;
+      if (sk_here > 1 && (size_t)sk_here * rows <= (size_t)(sk_full > 1 ? sk_full : 0) * N) sk = sk_here;
+    }
+    p->enc_kernel[l] = k;
+    p->enc_split_k[l] = sk;
+    p->w_cached[l] = c->weight_cache != nullptr && cl.has[l] && !in_loop_kernel(k) && k != MTMC_GEMM_ROWS_16;
+  }
+  p->l0_panels = 1;
+  if (p->enc_kernel[0] == MTMC_GEMM_PRESPLIT_256 && mtmc::knobs().l0_pipeline > 0)
+    p->l0_panels = l0_panels(rows, L0.out_dim, p->l0_cuts, &p->l0_bm);
+  // Few-row graphs: the last node-encoder layer is a handful of workgroups (S02: 8), and the edge branch's second kernel (enc2:
+  // moments of the edge encoder's hidden layer, needed from the first round on) is independent of the whole encoder chain -- it
+  // can ride in that launch as passenger workgroups (GemmParams / FewWaveParams::pass_*; -1 launch per forward): on the
+  // 64 x 64-tile in-loop kernel, or on the few-row kernel's 256-thread form (enc2_body's workgroup size)
+  const int last = m->n_enc_layers - 1, kl = p->enc_kernel[last];
+  p->enc2_may_ride = E > 0 && E <= mtmc::kSmallEdges &&
+                     (kl == MTMC_GEMM_INLOOP_64 || (kl == MTMC_GEMM_FEW_WAVE && mtmc::few_wave_threads(m->enc_node[last].in_dim) == 256));
+  p->edges_per_thread = mtmc::plan_edges_per_thread(E);
+  p->lazy_edges = !lo.training && E > mtmc::kSmallEdges;
+  p->fold_node_stat = mtmc::fold_node_stat(E);
+  // Row-complete shard: local edges over the rows the call owns; anything else (one GPU, or an edge-range shard that shares
+  // rows with its neighbours): the whole graph's E / N.  (Round 2 divided the LOCAL edge count by the GLOBAL node count:
+  // 8 ranks of config 5 saw 12 instead of 100 and left the matrix-core kernel.)
+  if (c->row_hi > 0) p->avg_degree = c->row_hi > c->row_lo ? (double)E / (double)(c->row_hi - c->row_lo) : 0.0;
+  else p->avg_degree = N > 0 ? (double)c->n_edges_total / (double)N : 0.0;
+  // the layout has the sub-run index (table size, edge count) AND the call's own degree pays
+  p->col_blocks = (m->num_enc_steps > 0 && lo.col_blocks > 0 &&
+                   mtmc::plan_col_blocks(N, E, p->avg_degree, lo.training) == lo.col_blocks) ? lo.col_blocks : 0;
+  const bool drop_n = lo.training && m->dropout_upd_node > 0.f;
+  p->pass_c = mtmc::plan_pass_c(m->agg, (c->flags & MTMC_F_DETERMINISTIC) != 0, drop_n, E, N, p->avg_degree);
+  // the public value names what launch_pass_c launches: the sorted kernel is MFMA_SORTED, the any-order kernel MFMA_ANY
+  // (on a many-edge list it still has the walk launched behind it for unsorted rows)
+  p->pass_c_pub = p->pass_c == 1 ? (mtmc::pass_c_sorted_taken(N) ? MTMC_PASS_C_MFMA_SORTED : MTMC_PASS_C_MFMA_ANY) : p->pass_c;
+}
+
 struct Ctx {
   const mtmc_mpn_model* m;
   const mtmc_mpn_call* c;
   Layout lo;
   char* ws;
   hipStream_t stream;
-  char* wc = nullptr;                // the weight-plane cache of an eval-mode call, or nullptr (training / none given)
+  char* wc = nullptr;                // the call's weight-plane cache (eval and training forwards), or nullptr (none given)
   CacheLayout cl;
+  CallPlan plan;                     // which kernels this call runs (make_ctx)
   template <typename T> T* wc_at(size_t off) const { return reinterpret_cast<T*>(wc + off); }
   const SidePipe* pipe = nullptr;    // set by mtmc_mpn_forward: layer 0 runs in row panels (split of panel i+1 beside GEMM i)
   bool enc2_rides = false;           // set by mtmc_mpn_forward (few-row graphs): MTMC_PH_EDGE_ENC's work rides as passenger
@@ -287,6 +385,7 @@ inline int make_ctx(const mtmc_mpn_model* m, const mtmc_mpn_call* c, Ctx* ctx) {
       return fail(MTMC_E_WORKSPACE, "weight_cache has %zu bytes, %zu needed (mtmc_mpn_weight_cache_bytes)", c->weight_cache_bytes, ctx->cl.total);
     ctx->wc = static_cast<char*>(c->weight_cache);
   }
+  make_plan(m, c, ctx->lo, ctx->cl, &ctx->plan);
   return MTMC_OK;
 }
 
@@ -337,23 +436,6 @@ inline float* round_Q(const Ctx& x, int r) { return x.at<float>(x.lo.training ? 
 inline float* round_z(const Ctx& x, int r) { return x.at<float>(x.lo.training ? x.lo.z_tr[r] : x.lo.e_buf[r & 1]); }
 inline float* round_e(const Ctx& x, int r) { return x.at<float>(x.lo.training ? x.lo.e_tr[r] : x.lo.e_buf[r & 1]); }
 
-// edges per source row of this call's edges -- what the pass-C dispatch needs.  Row-complete shard: local edges over the
-// rows the call owns; anything else (one GPU, or an edge-range shard that shares rows with its neighbours): the whole
-// graph's E / N.  (Round 2 divided the LOCAL edge count by the GLOBAL node count: 8 ranks of config 5 saw 12 instead of
-// 100 and left the matrix-core kernel.)
-inline double avg_degree(const mtmc_mpn_call* c) {
-  if (c->row_hi > 0) return c->row_hi > c->row_lo ? (double)c->n_edges / (double)(c->row_hi - c->row_lo) : 0.0;
-  return c->n_nodes > 0 ? (double)c->n_edges_total / (double)c->n_nodes : 0.0;
-}
-// eval mode, many local edges: e' is never stored (passes B/C and the next round's pass A recompute it from z1)
-inline bool lazy_edges(const mtmc_mpn_call* c) { return !c->training && c->n_edges > mtmc::kSmallEdges; }
-
-// column blocks of this call's pass A: the layout has the index (table size, edge count) AND the call's own degree pays
-inline int call_col_blocks(const Ctx& x) {
-  if (x.lo.col_blocks <= 0) return 0;
-  return mtmc::plan_col_blocks(x.c->n_nodes, x.c->n_edges, avg_degree(x.c), x.c->training != 0) == x.lo.col_blocks ? x.lo.col_blocks : 0;
-}
-
 inline mtmc::RoundParams round_params(const Ctx& x, int r) {
   const mtmc_mpn_model* m = x.m;
   const int hn = (m->reattach_nodes ? 2 : 1) * MTMC_NODE_DIM;
@@ -364,7 +446,7 @@ inline mtmc::RoundParams round_params(const Ctx& x, int r) {
   p.drop_e = make_drop(x, m->dropout_upd_edge); p.drop_n = make_drop(x, m->dropout_upd_node);
   p.drop_stream = mtmc::kDropRound + 2 * r;
   p.P = round_P(x, r); p.Q = round_Q(x, r);
-  p.seg = x.at<double>(x.lo.pub.seg_off); p.fold_z2 = mtmc::fold_node_stat(x.c->n_edges) ? 1 : 0;
+  p.seg = x.at<double>(x.lo.pub.seg_off); p.fold_z2 = x.plan.fold_node_stat ? 1 : 0;
   p.ue_w = m->upd_edge.weight; p.ue_b = m->upd_edge.bias; p.ue_g = m->upd_edge.gamma; p.ue_bt = m->upd_edge.beta;
   p.ue_ld = m->upd_edge.in_dim; p.ue_eoff = 2 * hn;
   p.un_w = m->upd_node.weight; p.un_b = m->upd_node.bias; p.un_g = m->upd_node.gamma; p.un_bt = m->upd_node.beta;
@@ -372,7 +454,7 @@ inline mtmc::RoundParams round_params(const Ctx& x, int r) {
   p.cls_w = m->cls.weight; p.cls_b = m->cls.bias; p.n_classes = m->cls.out_dim;
   p.stats = x.at<double>(x.lo.pub.stat_round_off) + (size_t)r * mtmc::kRoundBlock;
   // (few-edge graphs are latency-bound: there the extra statistics gather in two prologues costs more than the bytes save)
-  p.lazy_e = lazy_edges(x.c) ? 1 : 0;
+  p.lazy_e = x.plan.lazy_edges ? 1 : 0;
   p.prev_stats = r > 0 ? p.stats - mtmc::kRoundBlock : nullptr;
   p.h_acc = agg_target(x, r);
   const int step = r + 1;
@@ -384,76 +466,22 @@ inline mtmc::RoundParams round_params(const Ctx& x, int r) {
   p.det = (x.c->flags & MTMC_F_DETERMINISTIC) ? 1 : 0; p.flags = x.at<int>(x.lo.pub.flags_off);
   p.deg = x.at<int>(x.lo.pub.deg_off); p.row_start = x.at<int>(x.lo.row_start); p.carry = x.at<float>(x.lo.carry);
   p.n_nodes = x.c->n_nodes;
-  p.avg_degree = avg_degree(x.c);
-  p.col_blocks = call_col_blocks(x);
+  p.avg_degree = x.plan.avg_degree;
+  p.mfma_c = x.plan.pass_c;
+  p.col_blocks = x.plan.col_blocks;
   p.col_sub = x.at<int>(x.lo.col_sub); p.cb_row_lo = proj_lo(x.c); p.cb_row_hi = proj_hi(x.c);
   p.enc = enc_params(x);
   return p;
 }
 
-// layer 0 on pre-split operands: the layout has the planes (whole graph many-row) AND this call's rows are many too
-inline bool use_presplit0(const Ctx& x) {
-  return x.lo.presplit0 && mtmc::presplit_layer0(x.c->node_hi - x.c->node_lo, x.m->enc_node[0].in_dim, x.m->enc_node[0].out_dim);
-}
-
-// layer l >= 1 on the role-split kernel: the layout has its weight planes AND this call's rows are many too
-inline bool use_staged(const Ctx& x, int l) {
-  return l >= 1 && x.lo.staged[l] && mtmc::staged_layer(x.c->node_hi - x.c->node_lo, x.m->enc_node[l].in_dim, x.m->enc_node[l].out_dim);
-}
-
-// layer l >= 1 on the row-streaming kernel (narrow last layers of many-row graphs, eval mode)
-inline bool use_rows(const Ctx& x, int l) {
-  return l >= 1 && !x.lo.training && mtmc::rows_layer(x.c->n_nodes, x.m->enc_node[l].in_dim, x.m->enc_node[l].out_dim) &&
-         mtmc::rows_layer(x.c->node_hi - x.c->node_lo, x.m->enc_node[l].in_dim, x.m->enc_node[l].out_dim);
-}
-
-// every layer on the few-row kernels (gemm_few.hip): eval mode, a weight-plane cache, few rows here AND in the whole graph
-inline bool use_few(const Ctx& x) {
-  if (!x.lo.few || !x.wc) return false;
-  for (int l = 0; l < x.m->n_enc_layers; ++l) if (!x.cl.has[l]) return false;
-  return few_shape(x.m, x.c->node_hi - x.c->node_lo);
-}
 // where layer l's weight planes / inverse row scales are: the cache when the call has one, else the workspace (made per call)
 inline _Float16* w_planes(const Ctx& x, int l) {
-  if (x.wc && x.cl.has[l]) return x.wc_at<_Float16>(x.cl.planes[l]);
+  if (x.plan.w_cached[l]) return x.wc_at<_Float16>(x.cl.planes[l]);
   return x.at<_Float16>(l == 0 ? x.lo.wh : x.lo.wh_l[l]);
 }
 inline float* w_inv(const Ctx& x, int l) {
-  if (x.wc && x.cl.has[l]) return x.wc_at<float>(x.cl.inv[l]);
+  if (x.plan.w_cached[l]) return x.wc_at<float>(x.cl.inv[l]);
   return x.at<float>(l == 0 ? x.lo.inv_w : x.lo.inv_w_l[l]);
-}
-
-// Row panels of the pipelined layer 0: cuts[0..np] (multiples of the tile height), np <= kMaxPanels; *bm = the tile height
-// of every panel (what the whole matrix would pick).  One round = 256 workgroups = 256 / tiles_n row tiles.
-inline int l0_panels(int64_t rows, int Nout, int64_t* cuts, int* bm) {
-  const int tiles_n = (Nout + 255) / 256;
-  *bm = mtmc::presplit_tile_rows(rows, tiles_n);
-  const int64_t per_round = (int64_t)(256 / tiles_n > 0 ? 256 / tiles_n : 1) * *bm;
-  const int mode = mtmc::knobs().l0_pipeline;
-  int np = 0;
-  int64_t at = 0, k = 1;
-  cuts[0] = 0;
-  while (at < rows) {
-    int64_t take = per_round * (mode == 3 ? 2 : mode == 2 ? 1 : k);
-    if (np == kMaxPanels - 1 || at + take > rows) take = rows - at;
-    at += take;
-    cuts[++np] = at;
-    if (k < 8) k *= 2;
-  }
-  return np;
-}
-
-// Few-row graphs: the last node-encoder layer is a handful of workgroups (S02: 8) on the in-loop kernel, and the edge branch's
-// second kernel (enc2: moments of the edge encoder's hidden layer, needed from the first round on) is independent of the whole
-// encoder chain -- it rides in that launch as passenger workgroups (GemmParams::pass_*; -1 launch per forward).
-inline bool enc2_can_ride(const Ctx& x) {
-  const int last = x.m->n_enc_layers - 1;
-  const int64_t rows = x.c->node_hi - x.c->node_lo;
-  if (x.c->n_edges <= 0 || rows <= 0 || x.c->n_edges > mtmc::kSmallEdges) return false;
-  if (use_few(x)) return last >= 1 && mtmc::few_wave_threads(x.m->enc_node[last].in_dim) == 256;   // (enc2_body: 256 threads)
-  if ((last == 0 && use_presplit0(x)) || use_staged(x, last) || use_rows(x, last)) return false;
-  int sk;
-  return mtmc::gemm_plan(rows, x.m->enc_node[last].in_dim, x.m->enc_node[last].out_dim, &sk) == 1;
 }
 
 enum { kPhMemset = -1, kPhPrep = -2 };   // the two halves of MTMC_PH_BEGIN, for the forked forward
@@ -470,6 +498,153 @@ inline void fill_prep_edge(const Ctx& x, mtmc::PrepEdge* p) {
 
 inline const int* scale_deg(const Ctx& x) {   // the degree mean aggregation divides by
   return x.at<int>((x.c->flags & MTMC_F_GLOBAL_DEG) ? x.lo.pub.deg_global_off : x.lo.pub.deg_off);
+}
+
+// MTMC_PH_EDGE_ENC's work as passenger workgroups of an encoder layer's launch (GemmParams / FewWaveParams::pass_*)
+template <typename P> inline void ride_enc2(const Ctx& x, P* q) {
+  const int64_t blocks = (x.c->n_edges + 255) / 256;
+  q->pass_blocks = (int)(blocks > 2048 ? 2048 : blocks);
+  q->pass_enc = enc_params(x); q->pass_attr = x.c->edge_attr; q->pass_edges = x.c->n_edges;
+  q->pass_e_total = (double)x.c->n_edges_total; q->pass_stat = x.at<double>(x.lo.pub.stat_enc2_off);
+}
+
+// The node-encoder layer launches of MTMC_PH_NODE_ENC, one per form of CallPlan::enc_kernel.
+// Few-row graphs (gemm_few.hip): one launch per layer, never split along K.
+inline int launch_enc_few(const Ctx& x, int l) {
+  const mtmc_mpn_model* m = x.m;
+  const mtmc_layer& Lr = m->enc_node[l];
+  hipStream_t s = x.stream;
+  int rc;
+  if (l == 0) {
+    mtmc::FewL0Params q;
+    q.Ah = x.at<_Float16>(x.lo.xh); q.inv_a = x.at<float>(x.lo.inv_a);
+    q.Wh = w_planes(x, 0); q.inv_w = w_inv(x, 0);
+    q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[0]); q.ldy = Lr.out_dim;
+    q.stats_out = x.at<double>(x.lo.stat_enc_layer[0]);
+    q.M = x.plan.rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
+    rc = mtmc::launch_few_l0(q, s);
+  } else {
+    mtmc::FewWaveParams q;
+    q.A = x.at<float>(x.lo.Y[l - 1]); q.lda = m->enc_node[l - 1].out_dim;
+    q.stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]);
+    q.gamma_in = m->enc_node[l - 1].gamma; q.beta_in = m->enc_node[l - 1].beta; q.count = (double)x.c->n_nodes;
+    q.Wh = w_planes(x, l); q.inv_w = w_inv(x, l);
+    q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[l]); q.ldy = Lr.out_dim;
+    q.stats_out = x.at<double>(x.lo.stat_enc_layer[l]);
+    q.M = x.plan.rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
+    q.drop_in = make_drop(x, m->dropout_enc); q.drop_stream = mtmc::kDropEncNode + l - 1;
+    if (x.enc2_rides && l == m->n_enc_layers - 1) ride_enc2(x, &q);
+    rc = mtmc::launch_few_wave(q, s);
+  }
+  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: few-row kernel refused the shape or the launch", l);
+  return MTMC_OK;
+}
+
+// Many-row graphs, layer 0 on the operand planes made in MTMC_PH_BEGIN -- or, in the pipelined forward (x.pipe), in row panels.
+inline int launch_enc_presplit0(const Ctx& x) {
+  const mtmc_mpn_call* c = x.c;
+  const mtmc_layer& Lr = x.m->enc_node[0];
+  const int64_t rows = x.plan.rows;
+  hipStream_t s = x.stream;
+  mtmc::SplitGemmParams q;
+  q.Ah = x.at<_Float16>(x.lo.xh); q.inv_a = x.at<float>(x.lo.inv_a);
+  q.Wh = w_planes(x, 0); q.inv_w = w_inv(x, 0);
+  q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[0]); q.ldy = Lr.out_dim;
+  q.stats_out = x.at<double>(x.lo.stat_enc_layer[0]);
+  q.amax_y = x.at<unsigned>(x.lo.amax) + (1 + MTMC_MAX_ENC_LAYERS) * mtmc::kAmaxRep;
+  q.M = rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
+  PanelTiming& pt = panel_timing();
+  if (x.pipe) {
+    // Row panels: the side stream splits panel after panel (HBM-bound), the main stream multiplies panel i as soon as
+    // its planes are there (matrix-bound): the split pass leaves the critical path except for the first panel.
+    // Panel = whole rounds of workgroups of the tile height the whole matrix would get, so no round is paid twice.
+    const int np = x.plan.l0_panels;
+    const int64_t* cuts = x.plan.l0_cuts;
+    q.bm = x.plan.l0_bm;
+    q.M_rows = rows;
+    if (hipEventRecord(x.pipe->fork, s) != hipSuccess || hipStreamWaitEvent(x.pipe->stream, x.pipe->fork, 0) != hipSuccess)
+      return fail(MTMC_E_HIP, "encoder layer 0: fork onto the side stream failed");
+    // from here on the side stream is forked off `s` (inside a capture: part of it): every way out joins it again
+    auto join_and = [&](int code, const char* what) {
+      if (hipEventRecord(x.pipe->ready[0], x.pipe->stream) == hipSuccess) (void)hipStreamWaitEvent(s, x.pipe->ready[0], 0);
+      return fail(code, "%s", what);
+    };
+    for (int i = 0; i < np; ++i) {
+      mtmc::launch_split_rows_range(c->x, c->x_row_stride, rows, Lr.in_dim, x.at<void>(x.lo.xh), x.at<float>(x.lo.inv_a),
+                                    cuts[i], cuts[i + 1], x.pipe->stream);
+      if (hipEventRecord(x.pipe->ready[i], x.pipe->stream) != hipSuccess) return join_and(MTMC_E_HIP, "hipEventRecord failed");
+    }
+    if (pt.on) pt.n = 0;
+    for (int i = 0; i < np; ++i) {               // (the wait on the last panel's event also joins the side stream)
+      if (hipStreamWaitEvent(s, x.pipe->ready[i], 0) != hipSuccess) return join_and(MTMC_E_HIP, "hipStreamWaitEvent failed");
+      q.m_lo = cuts[i]; q.M = cuts[i + 1];
+      if (pt.on) (void)hipEventRecord(pt.ev[2 * i], s);
+      const int rc = mtmc::launch_gemm_presplit(q, s);
+      if (pt.on) { (void)hipEventRecord(pt.ev[2 * i + 1], s); pt.n = i + 1; }
+      if (rc != 0) return join_and(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer 0: pre-split GEMM refused a panel");
+    }
+    return MTMC_OK;
+  }
+  if (pt.on) { pt.n = 0; (void)hipEventRecord(pt.ev[0], s); }
+  const int rc = mtmc::launch_gemm_presplit(q, s);
+  if (pt.on) { (void)hipEventRecord(pt.ev[1], s); pt.n = 1; }
+  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer 0: pre-split GEMM refused the shape or the launch");
+  return MTMC_OK;
+}
+
+// Many-row graphs, layers >= 1 on the role-split kernel (gemm_staged.hip).
+inline int launch_enc_staged(const Ctx& x, int l) {
+  const mtmc_mpn_model* m = x.m;
+  const mtmc_layer& Lr = m->enc_node[l];
+  unsigned* amax = x.at<unsigned>(x.lo.amax);
+  mtmc::StagedGemmParams q;
+  q.A = x.at<float>(x.lo.Y[l - 1]); q.lda = m->enc_node[l - 1].out_dim;
+  q.stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]);
+  q.gamma_in = m->enc_node[l - 1].gamma; q.beta_in = m->enc_node[l - 1].beta; q.count = (double)x.c->n_nodes;
+  q.amax_a = amax + (1 + MTMC_MAX_ENC_LAYERS + (l - 1)) * mtmc::kAmaxRep;
+  q.Wh = w_planes(x, l); q.inv_w = w_inv(x, l);
+  q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[l]); q.ldy = Lr.out_dim;
+  q.stats_out = x.at<double>(x.lo.stat_enc_layer[l]);
+  q.amax_y = amax + (1 + MTMC_MAX_ENC_LAYERS + l) * mtmc::kAmaxRep;
+  q.M = x.plan.rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
+  const int rc = mtmc::launch_gemm_staged(q, x.stream);
+  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: role-split GEMM refused the shape or the launch", l);
+  return MTMC_OK;
+}
+
+// The in-loop operand split (gemm_bn.hip; MTMC_PH_NODE_COMBINE adds up the slab's K slices), or the row-streaming kernel
+// (gemm_rows.hip) of the narrow last layers of many-row graphs.
+inline int launch_enc_gemm(const Ctx& x, int l, int phase) {
+  const mtmc_mpn_model* m = x.m;
+  const mtmc_mpn_call* c = x.c;
+  const mtmc_layer& Lr = m->enc_node[l];
+  mtmc::GemmParams g;
+  if (l == 0) {
+    g.A = c->x; g.lda = c->x_row_stride; g.stats_in = nullptr; g.gamma_in = nullptr; g.beta_in = nullptr;
+  } else {
+    g.A = x.at<float>(x.lo.Y[l - 1]); g.lda = m->enc_node[l - 1].out_dim;
+    g.stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]);
+    g.gamma_in = m->enc_node[l - 1].gamma; g.beta_in = m->enc_node[l - 1].beta;
+  }
+  g.W = Lr.weight; g.bias = Lr.bias; g.Y = x.at<float>(x.lo.Y[l]); g.ldy = Lr.out_dim;
+  g.count = (double)c->n_nodes; g.stats_out = x.at<double>(x.lo.stat_enc_layer[l]);
+  g.M = x.plan.rows; g.K = Lr.in_dim; g.Nout = Lr.out_dim;
+  g.drop_in = make_drop(x, m->dropout_enc); g.drop_stream = mtmc::kDropEncNode + l - 1;
+  unsigned* amax = x.at<unsigned>(x.lo.amax);
+  g.amax_a = l == 0 ? amax : amax + (1 + MTMC_MAX_ENC_LAYERS + (l - 1)) * mtmc::kAmaxRep;
+  g.amax_w = x.at<unsigned>(x.lo.amax_w) + l * mtmc::kAmaxRep;
+  g.amax_y = amax + (1 + MTMC_MAX_ENC_LAYERS + l) * mtmc::kAmaxRep;
+  if (x.enc2_rides && phase == MTMC_PH_NODE_ENC && l == m->n_enc_layers - 1) ride_enc2(x, &g);
+  g.split_k = 1;
+  if (x.plan.enc_kernel[l] == MTMC_GEMM_ROWS_16) {
+    g.slab = nullptr;
+    if (mtmc::launch_gemm_rows(g, x.stream) != 0) return fail(MTMC_E_ARG, "encoder layer %d: row-streaming GEMM refused the shape", l);
+    return MTMC_OK;
+  }
+  g.slab = x.plan.enc_split_k[l] > 1 ? x.at<float>(x.lo.slab) : nullptr;
+  if (mtmc::launch_gemm_bn(g, x.stream, phase == MTMC_PH_NODE_ENC ? 1 : 2) != MTMC_OK)
+    return fail(MTMC_E_ARG, "encoder layer %d: unsupported GEMM shape", l);
+  return MTMC_OK;
 }
 
 inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
@@ -489,55 +664,49 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
       if (phase != kPhPrep && c->training && (c->flags & MTMC_F_SEED_ON_DEVICE))      // seed word <- counter++ (one thread)
         mtmc::launch_seed_tick(reinterpret_cast<unsigned long long*>((uintptr_t)c->seed), x.at<unsigned long long>(x.lo.seed_word), s);
       if (phase != kPhMemset) {
+        const CallPlan& pl = x.plan;
+        const int64_t rows = pl.rows;
         mtmc::PrepParams p;
         fill_prep_edge(x, &p);
         // passenger jobs: operand |.|max values / operand splits of the node encoder (this rank's rows of x; the weights)
         unsigned* amax = x.at<unsigned>(x.lo.amax);
         p.n_jobs = 0;
-        const bool pre0 = use_presplit0(x), few = use_few(x);
-        const int64_t rows = c->node_hi - c->node_lo;
         // (training forwards: the jobs also publish the tensors' |.|max -- the backward's GEMMs scale by |x|max and |W_l|max)
         unsigned* amax_w0 = x.at<unsigned>(x.lo.amax_w);
-        auto cache_job = [&](int l) {     // layer l's planes in the cache: verify every 8-row chunk, split the ones that changed
-          p.jobs[p.n_jobs++] = {m->enc_node[l].weight, m->enc_node[l].out_dim, m->enc_node[l].in_dim, m->enc_node[l].in_dim,
-                                c->training ? amax_w0 + l * mtmc::kAmaxRep : nullptr, 0, 0,
-                                mtmc::kJobSplit, x.wc_at<_Float16>(x.cl.planes[l]), x.wc_at<float>(x.cl.inv[l]),
-                                x.wc_at<unsigned long long>(x.cl.fp[l])};
-        };
         if (rows > 0) {
-          if (few)         // the planes of x, 8 rows per passenger workgroup (no |x|max: one scale per row)
+          if (pl.enc_kernel[0] == MTMC_GEMM_FEW_L0)     // the planes of x, 8 rows per passenger workgroup (no |x|max: one scale per row)
             p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, c->training ? amax : nullptr, 0, 0, mtmc::kJobSplit,
                                   x.at<_Float16>(x.lo.xh), x.at<float>(x.lo.inv_a), nullptr};
-          else if (!pre0)
+          else if (pl.enc_kernel[0] != MTMC_GEMM_PRESPLIT_256)
             p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, amax, 0, 0, mtmc::kJobAmax, nullptr, nullptr, nullptr};
           for (int l = 0; l < m->n_enc_layers; ++l) {
-            const bool planes = few || (l == 0 ? pre0 : use_staged(x, l));
-            if (planes) {
-              if (x.wc && x.cl.has[l]) cache_job(l);            // (no cache: launch_split_rows below)
-            } else if (!use_rows(x, l)) {                       // in-loop kernel: |W_l|max (row-streaming: in the kernel)
-              p.jobs[p.n_jobs++] = {m->enc_node[l].weight, m->enc_node[l].out_dim, m->enc_node[l].in_dim, m->enc_node[l].in_dim,
-                                    x.at<unsigned>(x.lo.amax_w) + l * mtmc::kAmaxRep, 0, 0, mtmc::kJobAmax, nullptr, nullptr, nullptr};
-            }
+            const mtmc_layer& Ll = m->enc_node[l];
+            if (pl.w_cached[l])         // layer l's planes in the cache: verify every 8-row chunk, split the ones that changed
+              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, c->training ? amax_w0 + l * mtmc::kAmaxRep : nullptr, 0, 0,
+                                    mtmc::kJobSplit, x.wc_at<_Float16>(x.cl.planes[l]), x.wc_at<float>(x.cl.inv[l]),
+                                    x.wc_at<unsigned long long>(x.cl.fp[l])};
+            else if (in_loop_kernel(pl.enc_kernel[l]))   // |W_l|max (row-streaming: in the kernel; planes without a cache: below)
+              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, amax_w0 + l * mtmc::kAmaxRep, 0, 0, mtmc::kJobAmax,
+                                    nullptr, nullptr, nullptr};
           }
         }
         mtmc::launch_prep(p, s);
-        if (L > 0 && c->n_edges > 0 && call_col_blocks(x) > 0) {   // sub-run boundaries of the column-blocked pass A, once per forward
+        if (pl.col_blocks > 0) {        // sub-run boundaries of the column-blocked pass A, once per forward
           const mtmc::RoundParams rp = round_params(x, 0);
           mtmc::launch_colblock_index(rp, x.at<int>(x.lo.col_sub), rp.col_blocks, rp.cb_row_lo, rp.cb_row_hi, s);
         }
-        if (pre0) {     // instead of the |.|max of x and W0: their fp16 planes and row scales (one pass over each)
+        if (pl.enc_kernel[0] == MTMC_GEMM_PRESPLIT_256) {     // instead of the |.|max of x and W0: their fp16 planes and row scales
           if (!x.pipe)  // (pipelined layer 0: the x planes are made panel by panel in MTMC_PH_NODE_ENC 0)
             mtmc::launch_split_rows(c->x, c->x_row_stride, rows, m->enc_node[0].in_dim, x.at<void>(x.lo.xh),
                                     x.at<float>(x.lo.inv_a), s);
-          if (!(x.wc && x.cl.has[0]))
+          if (!pl.w_cached[0])
             mtmc::launch_split_rows(m->enc_node[0].weight, m->enc_node[0].in_dim, m->enc_node[0].out_dim,
                                     m->enc_node[0].in_dim, x.at<void>(x.lo.wh), x.at<float>(x.lo.inv_w), s);
         }
-        if (rows > 0)
-          for (int l = 1; l < m->n_enc_layers; ++l)
-            if (use_staged(x, l) && !(x.wc && x.cl.has[l]))
-              mtmc::launch_split_rows(m->enc_node[l].weight, m->enc_node[l].in_dim, m->enc_node[l].out_dim,
-                                      m->enc_node[l].in_dim, x.at<void>(x.lo.wh_l[l]), x.at<float>(x.lo.inv_w_l[l]), s);
+        for (int l = 1; l < m->n_enc_layers; ++l)
+          if (pl.enc_kernel[l] == MTMC_GEMM_STAGED_128 && !pl.w_cached[l])
+            mtmc::launch_split_rows(m->enc_node[l].weight, m->enc_node[l].in_dim, m->enc_node[l].out_dim,
+                                    m->enc_node[l].in_dim, x.at<void>(x.lo.wh_l[l]), x.at<float>(x.lo.inv_w_l[l]), s);
       }
       break;
     }
@@ -548,145 +717,15 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
     case MTMC_PH_NODE_ENC:
     case MTMC_PH_NODE_COMBINE: {
       if (arg < 0 || arg >= m->n_enc_layers) return fail(MTMC_E_ARG, "encoder layer %d out of range", arg);
-      const int64_t rows = c->node_hi - c->node_lo;
-      if (rows == 0) break;
-      const mtmc_layer& Lr = m->enc_node[arg];
-      if (use_few(x)) {                                          // few-row graphs: one launch per layer, never split along K
-        if (phase == MTMC_PH_NODE_COMBINE) break;
-        int rc;
-        if (arg == 0) {
-          mtmc::FewL0Params q;
-          q.Ah = x.at<_Float16>(x.lo.xh); q.inv_a = x.at<float>(x.lo.inv_a);
-          q.Wh = w_planes(x, 0); q.inv_w = w_inv(x, 0);
-          q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[0]); q.ldy = Lr.out_dim;
-          q.stats_out = x.at<double>(x.lo.stat_enc_layer[0]);
-          q.M = rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
-          rc = mtmc::launch_few_l0(q, s);
-        } else {
-          mtmc::FewWaveParams q;
-          q.A = x.at<float>(x.lo.Y[arg - 1]); q.lda = m->enc_node[arg - 1].out_dim;
-          q.stats_in = x.at<double>(x.lo.stat_enc_layer[arg - 1]);
-          q.gamma_in = m->enc_node[arg - 1].gamma; q.beta_in = m->enc_node[arg - 1].beta; q.count = (double)c->n_nodes;
-          q.Wh = w_planes(x, arg); q.inv_w = w_inv(x, arg);
-          q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[arg]); q.ldy = Lr.out_dim;
-          q.stats_out = x.at<double>(x.lo.stat_enc_layer[arg]);
-          q.M = rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
-          q.drop_in = make_drop(x, m->dropout_enc); q.drop_stream = mtmc::kDropEncNode + arg - 1;
-          if (x.enc2_rides && arg == m->n_enc_layers - 1) {
-            const int64_t blocks = (c->n_edges + 255) / 256;
-            q.pass_blocks = (int)(blocks > 2048 ? 2048 : blocks);
-            q.pass_enc = enc_params(x); q.pass_attr = c->edge_attr; q.pass_edges = c->n_edges;
-            q.pass_e_total = (double)c->n_edges_total; q.pass_stat = x.at<double>(x.lo.pub.stat_enc2_off);
-          }
-          rc = mtmc::launch_few_wave(q, s);
-        }
-        if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: few-row kernel refused the shape or the launch", arg);
-        break;
-      }
-      if (arg == 0 && use_presplit0(x)) {
-        if (phase == MTMC_PH_NODE_COMBINE) break;                // never split along K
-        mtmc::SplitGemmParams q;
-        q.Ah = x.at<_Float16>(x.lo.xh); q.inv_a = x.at<float>(x.lo.inv_a);
-        q.Wh = w_planes(x, 0); q.inv_w = w_inv(x, 0);
-        q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[0]); q.ldy = Lr.out_dim;
-        q.stats_out = x.at<double>(x.lo.stat_enc_layer[0]);
-        q.amax_y = x.at<unsigned>(x.lo.amax) + (1 + MTMC_MAX_ENC_LAYERS) * mtmc::kAmaxRep;
-        q.M = rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
-        if (x.pipe) {
-          // Row panels: the side stream splits panel after panel (HBM-bound), the main stream multiplies panel i as soon as
-          // its planes are there (matrix-bound): the split pass leaves the critical path except for the first panel.
-          // Panel = whole rounds of workgroups of the tile height the whole matrix would get, so no round is paid twice.
-          int64_t cuts[kMaxPanels + 1];
-          const int np = l0_panels(rows, Lr.out_dim, cuts, &q.bm);
-          q.M_rows = rows;
-          if (hipEventRecord(x.pipe->fork, s) != hipSuccess || hipStreamWaitEvent(x.pipe->stream, x.pipe->fork, 0) != hipSuccess)
-            return fail(MTMC_E_HIP, "encoder layer 0: fork onto the side stream failed");
-          // from here on the side stream is forked off `s` (inside a capture: part of it): every way out joins it again
-          auto join_and = [&](int code, const char* what) {
-            if (hipEventRecord(x.pipe->ready[0], x.pipe->stream) == hipSuccess) (void)hipStreamWaitEvent(s, x.pipe->ready[0], 0);
-            return fail(code, "%s", what);
-          };
-          for (int i = 0; i < np; ++i) {
-            mtmc::launch_split_rows_range(c->x, c->x_row_stride, rows, Lr.in_dim, x.at<void>(x.lo.xh), x.at<float>(x.lo.inv_a),
-                                          cuts[i], cuts[i + 1], x.pipe->stream);
-            if (hipEventRecord(x.pipe->ready[i], x.pipe->stream) != hipSuccess) return join_and(MTMC_E_HIP, "hipEventRecord failed");
-          }
-          PanelTiming& pt = panel_timing();
-          if (pt.on) pt.n = 0;
-          for (int i = 0; i < np; ++i) {               // (the wait on the last panel's event also joins the side stream)
-            if (hipStreamWaitEvent(s, x.pipe->ready[i], 0) != hipSuccess) return join_and(MTMC_E_HIP, "hipStreamWaitEvent failed");
-            q.m_lo = cuts[i]; q.M = cuts[i + 1];
-            if (pt.on) (void)hipEventRecord(pt.ev[2 * i], s);
-            const int rc = mtmc::launch_gemm_presplit(q, s);
-            if (pt.on) { (void)hipEventRecord(pt.ev[2 * i + 1], s); pt.n = i + 1; }
-            if (rc != 0) return join_and(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer 0: pre-split GEMM refused a panel");
-          }
-          break;
-        }
-        PanelTiming& pt = panel_timing();
-        if (pt.on) { pt.n = 0; (void)hipEventRecord(pt.ev[0], s); }
-        const int rc = mtmc::launch_gemm_presplit(q, s);
-        if (pt.on) { (void)hipEventRecord(pt.ev[1], s); pt.n = 1; }
-        if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer 0: pre-split GEMM refused the shape or the launch");
-        break;
-      }
-      if (use_staged(x, arg)) {
-        if (phase == MTMC_PH_NODE_COMBINE) break;                // never split along K
-        unsigned* amax = x.at<unsigned>(x.lo.amax);
-        mtmc::StagedGemmParams q;
-        q.A = x.at<float>(x.lo.Y[arg - 1]); q.lda = m->enc_node[arg - 1].out_dim;
-        q.stats_in = x.at<double>(x.lo.stat_enc_layer[arg - 1]);
-        q.gamma_in = m->enc_node[arg - 1].gamma; q.beta_in = m->enc_node[arg - 1].beta; q.count = (double)c->n_nodes;
-        q.amax_a = amax + (1 + MTMC_MAX_ENC_LAYERS + (arg - 1)) * mtmc::kAmaxRep;
-        q.Wh = w_planes(x, arg); q.inv_w = w_inv(x, arg);
-        q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[arg]); q.ldy = Lr.out_dim;
-        q.stats_out = x.at<double>(x.lo.stat_enc_layer[arg]);
-        q.amax_y = amax + (1 + MTMC_MAX_ENC_LAYERS + arg) * mtmc::kAmaxRep;
-        q.M = rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
-        const int rc = mtmc::launch_gemm_staged(q, s);
-        if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: role-split GEMM refused the shape or the launch", arg);
-        break;
-      }
-      mtmc::GemmParams g;
-      if (arg == 0) {
-        g.A = c->x; g.lda = c->x_row_stride; g.stats_in = nullptr; g.gamma_in = nullptr; g.beta_in = nullptr;
-      } else {
-        g.A = x.at<float>(x.lo.Y[arg - 1]); g.lda = m->enc_node[arg - 1].out_dim;
-        g.stats_in = x.at<double>(x.lo.stat_enc_layer[arg - 1]);
-        g.gamma_in = m->enc_node[arg - 1].gamma; g.beta_in = m->enc_node[arg - 1].beta;
-      }
-      g.W = Lr.weight; g.bias = Lr.bias; g.Y = x.at<float>(x.lo.Y[arg]); g.ldy = Lr.out_dim;
-      g.count = (double)c->n_nodes; g.stats_out = x.at<double>(x.lo.stat_enc_layer[arg]);
-      g.M = rows; g.K = Lr.in_dim; g.Nout = Lr.out_dim;
-      g.drop_in = make_drop(x, m->dropout_enc); g.drop_stream = mtmc::kDropEncNode + arg - 1;
-      {
-        unsigned* amax = x.at<unsigned>(x.lo.amax);
-        g.amax_a = arg == 0 ? amax : amax + (1 + MTMC_MAX_ENC_LAYERS + (arg - 1)) * mtmc::kAmaxRep;
-        g.amax_w = x.at<unsigned>(x.lo.amax_w) + arg * mtmc::kAmaxRep;
-        g.amax_y = amax + (1 + MTMC_MAX_ENC_LAYERS + arg) * mtmc::kAmaxRep;
-      }
-      if (x.enc2_rides && phase == MTMC_PH_NODE_ENC && arg == m->n_enc_layers - 1) {
-        const int64_t blocks = (c->n_edges + 255) / 256;
-        g.pass_blocks = (int)(blocks > 2048 ? 2048 : blocks);
-        g.pass_enc = enc_params(x); g.pass_attr = c->edge_attr; g.pass_edges = c->n_edges;
-        g.pass_e_total = (double)c->n_edges_total; g.pass_stat = x.at<double>(x.lo.pub.stat_enc2_off);
-      }
-      if (use_rows(x, arg)) {
-        if (phase == MTMC_PH_NODE_COMBINE) break;                // never split along K
-        g.slab = nullptr; g.split_k = 1;
-        if (mtmc::launch_gemm_rows(g, s) != 0) return fail(MTMC_E_ARG, "encoder layer %d: row-streaming GEMM refused the shape", arg);
-        break;
-      }
-      {  // the slab was sized for N rows; a shard with fewer rows may plan a larger split
-        int sk_full, sk_here;
-        mtmc::gemm_plan(c->n_nodes, g.K, g.Nout, &sk_full);
-        mtmc::gemm_plan(rows, g.K, g.Nout, &sk_here);
-        g.slab = (sk_here > 1 && (size_t)sk_here * rows <= (size_t)(sk_full > 1 ? sk_full : 0) * c->n_nodes)
-                     ? x.at<float>(x.lo.slab) : nullptr;
-        g.split_k = 1;
-      }
-      if (mtmc::launch_gemm_bn(g, s, phase == MTMC_PH_NODE_ENC ? 1 : 2) != MTMC_OK)
-        return fail(MTMC_E_ARG, "encoder layer %d: unsupported GEMM shape", arg);
+      if (x.plan.rows == 0) break;
+      const int k = x.plan.enc_kernel[arg];
+      if (phase == MTMC_PH_NODE_COMBINE && !in_loop_kernel(k)) break;   // only the in-loop kernel splits along K
+      int rc;
+      if (k == MTMC_GEMM_FEW_L0 || k == MTMC_GEMM_FEW_WAVE) rc = launch_enc_few(x, arg);
+      else if (k == MTMC_GEMM_PRESPLIT_256) rc = launch_enc_presplit0(x);
+      else if (k == MTMC_GEMM_STAGED_128) rc = launch_enc_staged(x, arg);
+      else rc = launch_enc_gemm(x, arg, phase);
+      if (rc) return rc;
       break;
     }
     case MTMC_PH_NODE_H0: {
@@ -719,7 +758,7 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
       p.n_nodes = c->n_nodes;
       p.node_begin = proj_lo(c); p.node_end = proj_hi(c);
       p.edge_deg = x.at<int>(x.lo.pub.deg_off); p.un_b = m->upd_node.bias;
-      p.z2_stats = mtmc::fold_node_stat(c->n_edges)
+      p.z2_stats = x.plan.fold_node_stat
                        ? x.at<double>(x.lo.pub.stat_round_off) + (size_t)arg * mtmc::kRoundBlock + mtmc::kRoundZ2Off : nullptr;
       mtmc::launch_node_proj(p, s);
       break;
@@ -737,7 +776,7 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
     }
     case MTMC_PH_ROUND_STAT: {     // few-edge lists: nothing (the statistics came out of MTMC_PH_ROUND_PROJ + MTMC_PH_ROUND_B)
       if (arg < 0 || arg >= L) return fail(MTMC_E_ARG, "round %d out of range", arg);
-      if (mtmc::fold_node_stat(c->n_edges)) break;
+      if (x.plan.fold_node_stat) break;
       mtmc::NodeStatParams p;
       p.Q = round_Q(x, arg); p.deg = x.at<int>(x.lo.pub.deg_off); p.seg = x.at<double>(x.lo.pub.seg_off);
       p.un_w = m->upd_node.weight; p.un_b = m->upd_node.bias; p.un_ld = m->upd_node.in_dim;

@@ -1700,7 +1700,6 @@ bool pass_c_sorted_taken(int64_t n_nodes) { return !knobs().pass_c_general && n_
 void launch_pass_c(const RoundParams& p0, hipStream_t s) {
   RoundParams p = p0;
   p.det_len = 32;
-  p.mfma_c = plan_pass_c(p.agg, p.det != 0, p.drop_n.on != 0, p.n_edges, p.n_nodes, p.avg_degree);
   const int span_env = knobs().pass_c_span, max_blocks = knobs().pass_c_blocks;
   if (p.mfma_c == 1 && pass_c_sorted_taken(p.n_nodes)) {
     // many-edge sorted lists: a grid of twice what is resident (104 registers: four blocks per CU; the block prologue -- 74 replicated

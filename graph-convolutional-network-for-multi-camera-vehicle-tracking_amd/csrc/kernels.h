@@ -78,7 +78,7 @@ struct RoundParams {
   // eval mode: e' = relu(bn(z1)) is never written -- pass C and the next round's pass A recompute it from z1 (4 FMAs)
   // with the round's z1 statistics; pass B only reduces it.  16 B/edge/round less traffic.  prev_stats: round r-1's block
   int lazy_e; const double* prev_stats;
-  int mfma_c;                // set by launch_pass_c: the matrix-core pass C takes row-sorted lists
+  int mfma_c;                // the call's plan_pass_c (round_params); launch_pass_c turns 1 into 3 / 4 for the sorted kernel
   int stream_z1;             // set by launch_pass_a: z1 is stored non-temporally (lists whose z1 outgrows the Infinity Cache)
   int det_len;               // set by launch_pass_c: edges per carry chunk of the deterministic sums (32, or a span of the sorted kernel)
   int det; const int* flags; const int* deg; const int* row_start; float* carry; int64_t n_nodes;   // deterministic sums
@@ -230,7 +230,7 @@ int plan_col_blocks(int64_t n_nodes, int64_t n_edges, double avg_degree, bool tr
 void launch_colblock_index(const RoundParams& p, int* sub, int B, int64_t row_lo, int64_t row_hi, hipStream_t s);
 void launch_pass_b(const RoundParams& p, hipStream_t s);
 void launch_pass_c(const RoundParams& p, hipStream_t s);
-// Which pass-C kernel a call takes (host-only decision, also behind mtmc_mpn_plan): 0 = the half-wave walk; 1 = the
+// Which pass-C kernel a call takes (host-only, once per call: api_internal.h make_plan): 0 = the half-wave walk; 1 = the
 // matrix-core kernel with the walk launched behind it for unsorted rows (many-edge lists); 2 = the matrix-core kernel
 // alone (few-edge lists).  avg_degree: edges per source row of THIS call's edges (RoundParams::avg_degree).
 int plan_pass_c(int agg, bool deterministic, bool dropout, int64_t n_edges, int64_t n_nodes, double avg_degree);
