@@ -8,14 +8,29 @@
 // (10.8 MB for the reference model, in workgroups that ride in prep_kernel's launch) and, per 8-row chunk, compares a 64-bit
 // fingerprint of the chunk's bits with the one stored beside the planes; only a chunk whose fingerprint differs is split
 // and stored again.  Nothing on the host decides validity, so there is no stale state to get wrong: a changed weight
-// changes the fingerprint of its chunk (any single changed word always does: the per-word multipliers are odd, hence
-// invertible mod 2^64; several changed words collide with probability 2^-63).
+// changes the fingerprint of its chunk.  The fingerprint is a sum mod 2^64 of one term per PAIR of words (two adjacent k of
+// one row, read as the u64 the row holds there): fp_mix(pair + key), fp_mix a bijective 64-bit mixer and the key distinct
+// per pair position in the chunk.  A change inside one pair -- any single changed word in particular -- always changes the
+// sum (fp_mix is a bijection); a change of several pairs is missed with probability about 2^-64 per chunk, whatever its
+// structure (swaps, +d/-d, sign flips: tests/test_weight_fingerprint.py).  Round 5's linear hash gave positions with equal
+// products (2i+1)(2t+1) one multiplier, so swapping two of them went unseen.  One mix per two words, not per word, keeps
+// the added ALU small: same registers, and the headline forward within its run-to-run spread.  tests/wcache_util.py
+// mirrors the hash bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "lds_dma.h"
 
 namespace mtmc {
+
+constexpr unsigned long long kFpKey = 0x9E3779B97F4A7C15ull;   // pair position p of a chunk: key p * kFpKey (distinct)
+
+// the splitmix64 finaliser: a bijection of the 64-bit words
+__device__ __forceinline__ unsigned long long fp_mix(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
 
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int off) {
   const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
@@ -57,19 +72,20 @@ __device__ __forceinline__ void split_rows_body(const float* __restrict__ X, int
   }
   unsigned long long mine = 0;
   if (fp) {
-    // linear hash over Z / 2^64 with an odd multiplier per position: (word index in the lane) x (thread in the workgroup)
+    // the pair (k, k+1) of word slot 2c, 2c+1 of this thread sits at pair position threadIdx.x * 32 + c of the chunk
+    const unsigned long long key = (unsigned long long)threadIdx.x * 32ull * kFpKey;
     unsigned long long h = 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        const unsigned w[4] = {__float_as_uint(v[j][q].x), __float_as_uint(v[j][q].y), __float_as_uint(v[j][q].z),
-                               __float_as_uint(v[j][q].w)};
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-          h += (unsigned long long)w[t] * (0x9E3779B97F4A7C15ull * (unsigned long long)(2 * ((j * 2 + q) * 4 + t) + 1) | 1ull);
+        const int c = (j * 2 + q) * 2;
+        const unsigned long long u0 = ((unsigned long long)__float_as_uint(v[j][q].y) << 32) | __float_as_uint(v[j][q].x);
+        const unsigned long long u1 = ((unsigned long long)__float_as_uint(v[j][q].w) << 32) | __float_as_uint(v[j][q].z);
+        h += fp_mix(u0 + key + (unsigned long long)c * kFpKey);
+        h += fp_mix(u1 + key + (unsigned long long)(c + 1) * kFpKey);
       }
-    h = live ? h * ((0xD6E8FEB86659FD93ull * (unsigned long long)(2 * threadIdx.x + 1)) | 1ull) : 0ull;
+    h = live ? h : 0ull;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) h += shfl_xor_u64(h, off);
     if (lane == 0) smem[threadIdx.x >> 6] = h;

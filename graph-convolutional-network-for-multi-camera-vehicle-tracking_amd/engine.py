@@ -179,7 +179,8 @@ class ForwardEngine:
         eval-mode forward re-reads the weights on the device and compares a 64-bit fingerprint per 8 weight rows with the one
         stored beside the planes (csrc/split_body.h), so in-place updates, writes through `param.data`, another module of the
         same configuration at recycled addresses and graph replays after a weight change all get the planes of the weights
-        they run with (round 4 keyed the cache on (data_ptr, _version) on the host)."""
+        they run with (round 4 keyed the cache on (data_ptr, _version) on the host).  A single changed word is
+        always seen; a change of several words is missed with probability about 2^-64 per 8-row chunk."""
         key = (dev, stream_ptr)
         buf = self._wc.get(key)
         if buf is None:

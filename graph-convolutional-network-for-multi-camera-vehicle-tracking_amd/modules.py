@@ -125,8 +125,9 @@ class MOTMPNet(nn.Module):
         self.deterministic = False          # True: order-independent sum/mean aggregation on row-sorted edge lists
         # Eval mode: the fp16 operand planes of the node-encoder WEIGHTS are kept from one forward to the next in a buffer the
         # library verifies against the weights' content on the device on every call (64-bit fingerprints per 8 weight rows,
-        # engine.weight_plane_cache): any way of changing a weight -- optimizer steps, `param.data` writes, a new module at the
-        # old addresses -- is seen.  False: no cache (few-row graphs then run the split-K kernels of rounds 1-4).
+        # engine.weight_plane_cache): optimizer steps, `param.data` writes, a new module at the old addresses are all seen -- any
+        # single changed word always, a change of several words up to a chance of about 2^-64 per 8 rows.  False: no cache
+        # (few-row graphs then run the split-K kernels of rounds 1-4).
         self.cache_weight_planes = True
         # Training: None -- every forward draws its Dropout seed from torch's CPU generator (follows torch.manual_seed), a host
         # value.  An int64 [1] tensor on the model's device -- the seed is read from it ON THE DEVICE and it moves on by one per

@@ -119,8 +119,9 @@ typedef struct mtmc_mpn_call {
                                 aligned, ZERO-FILLED once by the caller and then left alone between calls.  The library keeps
                                 what it derives from the node-encoder WEIGHTS alone in it (fp16 operand planes, row scales) and
                                 verifies it against the weights' CONTENT on every call -- a 64-bit fingerprint per 8 weight rows,
-                                taken on the device -- so the caller promises nothing about the weights: a changed weight is
-                                split again, an unchanged one is not.  One cache per stream that runs forwards concurrently.
+                                taken on the device -- so the caller promises nothing about the weights: a single changed word
+                                is always seen, a change of several words is missed with probability about 2^-64 per 8 rows;
+                                a changed chunk is split again, an unchanged one is not.  One cache per stream that runs forwards concurrently.
                                 Few-row graphs need it for the kernels of csrc/gemm_few.hip (without: the split-K kernels).   */
   size_t weight_cache_bytes;
 } mtmc_mpn_call;

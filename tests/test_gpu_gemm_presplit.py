@@ -5,6 +5,8 @@ ragged edges, rows of very different magnitude, zero rows.  Same bound as the in
 import pytest
 import torch
 
+import wcache_util
+
 pytestmark = pytest.mark.gpu
 
 
@@ -143,14 +145,9 @@ def test_plane_layout_and_split_are_as_documented(M, K):
     A[M // 2] = 0.0                                              # a zero row: scale stays finite
     W = torch.randn(40, K, generator=g).cuda()
     _, _, _, work = _run(lib, A, W, torch.zeros(40, device="cuda"), "product")
-    planes = work[:M * K * 4].view(torch.float16).view(2, K // 32, M, 4, 8)      # [piece][k-tile][row][slot][8]
+    planes = work[:M * K * 4].view(torch.float16)                 # [piece][k-tile][row][slot][8]
     inv = work[M * K * 4:M * K * 4 + M * 4].view(torch.float32)
-    r = torch.arange(M, device="cuda")
-    swz = torch.tensor([0, 2, 3, 1], device="cuda")[(r >> 2) & 3]
-    slot = torch.arange(4, device="cuda").unsqueeze(0) ^ swz.unsqueeze(1)                     # [row][logical slot] -> stored slot
-    idx = slot.view(1, 1, M, 4, 1).expand(2, K // 32, M, 4, 8)
-    logical = torch.gather(planes, 3, idx)                       # [piece][k-tile][row][logical slot][8]
-    h = logical.permute(0, 2, 1, 3, 4).reshape(2, M, K).double()
+    h = wcache_util.decode_planes(planes, M, K)                  # swz(r) undone: [piece][row][k]
     rec = (h[0] + h[1]) * inv.double().unsqueeze(1)
     amax = A.abs().amax(dim=1).double()
     assert (rec - A.double()).abs().max().item() <= 0.0 + (amax * 2.0 ** -21).max().item()
