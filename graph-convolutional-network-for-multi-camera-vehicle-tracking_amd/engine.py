@@ -6,16 +6,12 @@ from __future__ import annotations
 
 import ctypes as C
 import types
-from typing import List, Tuple
+from typing import List
 
 import torch
 
 from . import _lib
 from .config import MpnSpec
-
-
-def _lin(mlp, spec_layer):
-    return mlp.fc_layers[spec_layer.lin_slot], (mlp.fc_layers[spec_layer.bn_slot] if spec_layer.bn_slot is not None else None)
 
 
 def _check_param(p: torch.Tensor, dev) -> int:
@@ -38,18 +34,42 @@ def layer_slots(spec: MpnSpec):
     return out
 
 
-def module_layers(module):
-    """(slot, Linear, BatchNorm or None, LayerSpec) of a MOTMPNet module tree, in layer_slots order."""
-    m, s = module, module.spec
-    out = []
-    for i, layer in enumerate(s.enc_node):
-        out.append((("enc_node", i),) + _lin(m.encoder.node_mlp, layer) + (layer,))
-    for i, layer in enumerate(s.enc_edge):
-        out.append((("enc_edge", i),) + _lin(m.encoder.edge_mlp, layer) + (layer,))
-    out.append((("upd_edge", None),) + _lin(m.MPNet.edge_model.edge_mlp, s.upd_edge[0]) + (s.upd_edge[0],))
-    out.append((("upd_node", None),) + _lin(m.MPNet.node_model.node_mlp, s.upd_node[0]) + (s.upd_node[0],))
-    out.append((("cls", None),) + _lin(m.classifier.edge_mlp, s.cls_edge[0]) + (s.cls_edge[0],))
+def n_classified_steps(spec: MpnSpec) -> int:
+    """How many steps' logits one forward returns (the first dimension of mp_forward's logits)."""
+    return min(spec.num_class_steps, spec.num_enc_steps) if spec.num_enc_steps > 0 else 1
+
+
+def _row_range(row_range):
+    """mtmc_mpn_call::row_lo / row_hi.  (0, 0) means "all rows", so the empty range goes down as (k, k) with k > 0."""
+    if row_range is None:
+        return 0, 0
+    lo, hi = int(row_range[0]), int(row_range[1])
+    return (lo, hi) if hi > lo else (max(lo, 1), max(lo, 1))
+
+
+def _fill_model(out, spec: MpnSpec, slots, pointers, dropout):
+    """mtmc_mpn_model from the configuration: the layers' dimensions, n_enc_layers, agg, step counts, reattach flags and,
+    with `dropout`, the three Dropout rates (else 0).  `pointers(slot, idx, layer)` gives the layer's (weight, bias, gamma,
+    beta), the last two None where it has no BatchNorm."""
+    if len(spec.enc_node) > _lib.MAX_ENC_LAYERS:
+        raise NotImplementedError("mtmc_mpn: node encoder deeper than 8 layers")
+    for slot, idx, layer in slots:
+        dst = getattr(out, slot) if idx is None else getattr(out, slot)[idx]
+        dst.weight, dst.bias, dst.gamma, dst.beta = pointers(slot, idx, layer)
+        dst.in_dim, dst.out_dim = layer.in_dim, layer.out_dim
+    if dropout:
+        out.dropout_enc = float(spec.enc_node[0].dropout_p or 0.0)
+        out.dropout_upd_edge = float(spec.upd_edge[0].dropout_p or 0.0)
+        out.dropout_upd_node = float(spec.upd_node[0].dropout_p or 0.0)
+    out.n_enc_layers = len(spec.enc_node)
+    out.agg = _lib.AGG[spec.agg]
+    out.num_enc_steps, out.num_class_steps = spec.num_enc_steps, spec.num_class_steps
+    out.reattach_nodes, out.reattach_edges = int(spec.reattach_nodes), int(spec.reattach_edges)
     return out
+
+
+def _placeholder_pointers(slot, idx, layer):
+    return (256, 256) + ((256, 256) if layer.bn_slot is not None else (None, None))
 
 
 def ordered_params(module) -> List[torch.Tensor]:
@@ -94,73 +114,58 @@ class ForwardEngine:
         self._ws = {}
         self._slots = layer_slots(self.spec)
         self._ms_key, self._ms = None, None
-        self._wc = {}                   # (device, stream) -> the weight-plane cache buffer of eval-mode calls on that stream
-        self.weight_cache = True        # hand the library a weight-plane cache (torch_ops.NO_WEIGHT_CACHE / module.cache_weight_planes)
-        self.flags = 0                  # MTMC_F_* for the calls this engine prepares (torch op argument)
+        self._wc = {}                   # (device, stream) -> the weight-plane cache buffer of the calls on that stream
 
     # -- parameters -> mtmc_mpn_model ------------------------------------------------------------
     def param_layers(self):
-        """(struct slot, Linear, BatchNorm or None, LayerSpec) for every layer of the bound module."""
+        """((struct slot, index or None), Linear, BatchNorm or None, LayerSpec) for every layer of the bound module, in
+        layer_slots order.  Re-read per call: sub-modules / Parameters may have been replaced."""
         if self.module is None:
             raise RuntimeError("mtmc_mpn: this engine was built from a spec; pass the parameter list explicitly")
-        return module_layers(self.module)          # re-read per call: sub-modules / Parameters may have been replaced
+        m = self.module
+        mlps = {"enc_node": m.encoder.node_mlp, "enc_edge": m.encoder.edge_mlp, "upd_edge": m.MPNet.edge_model.edge_mlp,
+                "upd_node": m.MPNet.node_model.node_mlp, "cls": m.classifier.edge_mlp}
+        return [((slot, idx), mlps[slot].fc_layers[l.lin_slot],
+                 mlps[slot].fc_layers[l.bn_slot] if l.bn_slot is not None else None, l) for slot, idx, l in self._slots]
 
     def params(self) -> List[torch.Tensor]:
         if self.module is None:
             raise RuntimeError("mtmc_mpn: no parameters given")
         return ordered_params(self.module)         # never cached: see MOTMPNet.forward
 
-    def model_struct(self, dev, params=None) -> _lib.Model:
+    def model_struct(self, dev, params=None, dropout=True) -> _lib.Model:
+        """mtmc_mpn_model over these parameters (default: the bound module's); `dropout=False`: with the three Dropout rates
+        at 0.  Always a copy of the cached struct: whatever a caller writes into it stays with that call."""
         params = self.params() if params is None else params
         # the struct only changes when a parameter's storage does: key it on the device pointers -- and on what _check_param
         # looks at, since an allocator can hand a recycled address to a tensor of another dtype or shape (e.g. after .half())
         key = (dev,) + tuple((t.data_ptr(), t.dtype, t.shape, t.stride()) for t in params)
-        if key == self._ms_key:
-            return _lib.Model.from_buffer_copy(self._ms)
-        s = self.spec
-        out = _lib.Model()
-        if len(s.enc_node) > _lib.MAX_ENC_LAYERS:
-            raise NotImplementedError("mtmc_mpn: node encoder deeper than 8 layers")
-        it = iter(params)
-        try:
-            for slot, idx, layer in self._slots:
-                dst = getattr(out, slot) if idx is None else getattr(out, slot)[idx]
+        if key != self._ms_key:
+            it = iter(params)
+
+            def pointers(slot, idx, layer):
                 w, b = next(it), next(it)
                 if tuple(w.shape) != (layer.out_dim, layer.in_dim) or tuple(b.shape) != (layer.out_dim,):
                     raise RuntimeError(f"mtmc_mpn: parameter shapes of {slot}[{idx}] do not match the configuration")
-                dst.weight, dst.bias = _check_param(w, dev), _check_param(b, dev)
-                if layer.bn_slot is not None:
-                    dst.gamma, dst.beta = _check_param(next(it), dev), _check_param(next(it), dev)
-                else:
-                    dst.gamma = dst.beta = None
-                dst.in_dim, dst.out_dim = layer.in_dim, layer.out_dim
-        except StopIteration:
-            raise RuntimeError("mtmc_mpn: parameter list shorter than the configuration needs") from None
-        out.dropout_enc = float(s.enc_node[0].dropout_p or 0.0)
-        out.dropout_upd_edge = float(s.upd_edge[0].dropout_p or 0.0)
-        out.dropout_upd_node = float(s.upd_node[0].dropout_p or 0.0)
-        out.n_enc_layers = len(s.enc_node)
-        out.agg = _lib.AGG[s.agg]
-        out.num_enc_steps, out.num_class_steps = s.num_enc_steps, s.num_class_steps
-        out.reattach_nodes, out.reattach_edges = int(s.reattach_nodes), int(s.reattach_edges)
-        self._ms_key, self._ms = key, out
-        return _lib.Model.from_buffer_copy(out)
-
-    def shape_model(self) -> _lib.Model:
-        """The configuration's dimensions and flags with PLACEHOLDER parameter pointers (non-NULL, never dereferenced):
-        for the host-only size queries (workspace bytes, gradient layout) that shape inference needs without tensors."""
-        s = self.spec
-        out = _lib.Model()
-        for slot, idx, layer in self._slots:
-            dst = getattr(out, slot) if idx is None else getattr(out, slot)[idx]
-            dst.weight = dst.bias = 256
-            dst.gamma = dst.beta = 256 if layer.bn_slot is not None else None
-            dst.in_dim, dst.out_dim = layer.in_dim, layer.out_dim
-        out.n_enc_layers = len(s.enc_node)
-        out.agg = _lib.AGG[s.agg]
-        out.num_enc_steps, out.num_class_steps = s.num_enc_steps, s.num_class_steps
-        out.reattach_nodes, out.reattach_edges = int(s.reattach_nodes), int(s.reattach_edges)
+                ptrs = _check_param(w, dev), _check_param(b, dev)
+                if layer.bn_slot is None:
+                    return ptrs + (None, None)
+                return ptrs + (_check_param(next(it), dev), _check_param(next(it), dev))
+            try:
+                out = _fill_model(_lib.Model(), self.spec, self._slots, pointers, dropout=True)
+            except StopIteration:
+                raise RuntimeError("mtmc_mpn: parameter list shorter than the configuration needs") from None
+            self._ms_key, self._ms = key, out
+        out = _lib.Model.from_buffer_copy(self._ms)
+        if not dropout:
+            out.dropout_enc = out.dropout_upd_edge = out.dropout_upd_node = 0.0
         return out
+
+    def shape_model(self, dropout=False) -> _lib.Model:
+        """The configuration's dimensions and flags with PLACEHOLDER parameter pointers (non-NULL, never dereferenced): for
+        the host-only queries that need no tensors -- workspace bytes and gradient layout for shape inference, and, with the
+        Dropout rates (`dropout=True`: a training call's pass C depends on one), the kernel plan."""
+        return _fill_model(_lib.Model(), self.spec, self._slots, _placeholder_pointers, dropout)
 
     def workspace(self, model, n, e, dev, stream_ptr) -> torch.Tensor:
         need = self.lib.mtmc_mpn_workspace_bytes(C.byref(model), n, e)
@@ -176,7 +181,7 @@ class ForwardEngine:
     def weight_plane_cache(self, model, dev, stream_ptr) -> torch.Tensor:
         """mtmc_mpn_call::weight_cache: a zero-filled buffer per (device, stream) in which the library keeps the fp16 planes /
         row scales it derives from the node-encoder weights.  NOTHING here decides whether its content is still valid: every
-        eval-mode forward re-reads the weights on the device and compares a 64-bit fingerprint per 8 weight rows with the one
+        forward (eval or training) re-reads the weights on the device and compares a 64-bit fingerprint per 8 weight rows with the one
         stored beside the planes (csrc/split_body.h), so in-place updates, writes through `param.data`, another module of the
         same configuration at recycled addresses and graph replays after a weight change all get the planes of the weights
         they run with (round 4 keyed the cache on (data_ptr, _version) on the host).  A single changed word is
@@ -189,6 +194,12 @@ class ForwardEngine:
                 _lib.check(_lib.E_ARG)
             buf = self._wc[key] = torch.zeros(need + 256, dtype=torch.uint8, device=dev)
         return buf
+
+    def take_stream_buffers(self, dev, stream_ptr) -> list:
+        """Remove and return the workspace and the weight-plane cache of one stream (those that exist): for a captured graph,
+        whose kernels use them for as long as it lives -- a later, larger forward on that stream would otherwise replace them."""
+        key = (dev, stream_ptr)
+        return [buf for buf in (self._ws.pop(key, None), self._wc.pop(key, None)) if buf is not None]
 
     # -- the call -----------------------------------------------------------------------------------
     def check_inputs(self, x, edge_index, edge_attr):
@@ -210,12 +221,34 @@ class ForwardEngine:
         if edge_index.dtype != torch.int64:
             raise RuntimeError("mtmc_mpn: edge_index must be int64")
 
+    def call_struct(self, n_nodes, n_edges, n_edges_total=None, node_lo=0, node_hi=None, row_range=None, training=False,
+                    flags=None, weight_cache=None) -> _lib.Call:
+        """The pointer-free part of mtmc_mpn_call: sizes, ranges, mode and the per-call settings -- all that the kernel plan
+        depends on (mtmc_mpn_plan_call reads nothing else).  `flags` (MTMC_F_*) and `weight_cache` are this call's alone;
+        where the caller gives none, they are what the bound module says (`deterministic`, `cache_weight_planes`), and 0 and
+        True for an engine built from a spec.  A wanted weight-plane cache is marked with a placeholder pointer (the plan
+        query only tests it for NULL): prepare() puts the stream's buffer there."""
+        if flags is None:
+            flags = _lib.F_DETERMINISTIC if getattr(self.module, "deterministic", False) else 0
+        if weight_cache is None:
+            weight_cache = getattr(self.module, "cache_weight_planes", True)
+        call = _lib.Call()
+        call.n_nodes, call.n_edges = int(n_nodes), int(n_edges)
+        call.n_edges_total = int(n_edges if n_edges_total is None else n_edges_total)
+        call.node_lo, call.node_hi = int(node_lo), int(n_nodes if node_hi is None else node_hi)
+        call.row_lo, call.row_hi = _row_range(row_range)
+        call.training, call.flags = int(bool(training)), int(flags)
+        if weight_cache:
+            call.weight_cache, call.weight_cache_bytes = 256, 1 << 62
+        return call
+
     def prepare(self, x, edge_index, edge_attr, training=False, n_edges_total=None, node_range=None, tape=False,
-                seed=0, row_range=None, params=None, tape_ws=None):
+                seed=0, row_range=None, params=None, tape_ws=None, flags=None, weight_cache=None):
         """Validate, allocate outputs/workspace and fill the two C structs of one call.
-        `tape=True`: training-mode layout in a fresh workspace that the backward will read (kept by autograd).
+        `tape=True`: training-mode layout in a fresh workspace that the backward will read (kept by autograd); with
+        `training=False` the statistics are still the batch's, but Dropout is the identity (eval mode under grad mode).
         `row_range=(lo, hi)`: multi-GPU, row-complete edge shard -- project / take node statistics of these rows only
-        (mtmc_mpn_call::row_lo / row_hi)."""
+        (mtmc_mpn_call::row_lo / row_hi).  `flags`, `weight_cache`: this call's settings (call_struct)."""
         self.check_inputs(x, edge_index, edge_attr)
         s, dev = self.spec, x.device
         e = edge_index.shape[1]
@@ -232,13 +265,13 @@ class ForwardEngine:
             edge_attr = edge_attr.contiguous()
         if e > 0 and edge_index.stride(1) < 1:
             edge_index = edge_index.contiguous()
-        n_out = min(s.num_class_steps, s.num_enc_steps) if s.num_enc_steps > 0 else 1
+        n_out = n_classified_steps(s)
         n_cls = s.cls_edge[0].out_dim
         logits = torch.empty((n_out, e, n_cls), dtype=torch.float32, device=dev)
         h = torch.empty((n, s.node_dim), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-        model = self.model_struct(dev, params)
+        model = self.model_struct(dev, params, dropout=training or not tape)
         if tape_ws is not None:                        # backward: the tape the forward op returned
             ws = tape_ws
         elif tape:
@@ -248,25 +281,20 @@ class ForwardEngine:
             ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
         else:
             ws = self.workspace(model, n, e, dev, stream)
-        call = _lib.Call()
+        # (no cache for a backward; training forwards have one: every chunk whose weights the step changed is split again)
+        call = self.call_struct(n, e, n_edges_total, node_lo, node_hi, row_range, tape, flags,
+                                False if tape_ws is not None else weight_cache)
         call.x, call.x_row_stride = x.data_ptr(), x.stride(0)
         call.row = edge_index[0].data_ptr() if e > 0 else None
         call.col = edge_index[1].data_ptr() if e > 0 else None
         call.idx_stride = edge_index.stride(1) if e > 0 else 1
         call.edge_attr = edge_attr.data_ptr() if e > 0 else ws.data_ptr()
-        call.n_nodes, call.n_edges = n, e
-        call.n_edges_total = e if n_edges_total is None else n_edges_total
-        call.node_lo, call.node_hi = node_lo, node_hi
-        if row_range is not None:                      # (k, k) with k > 0 is the empty range; (0, 0) means "all"
-            rlo, rhi = int(row_range[0]), int(row_range[1])
-            call.row_lo, call.row_hi = (rlo, rhi) if rhi > rlo else (max(rlo, 1), max(rlo, 1))
         call.logits = logits.data_ptr() if logits.numel() else ws.data_ptr()
         call.h_out = h.data_ptr()
         call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel()
-        call.training, call.seed = (1 if tape else 0), int(seed) & 0xFFFFFFFFFFFFFFFF
-        call.flags = int(self.flags) | (_lib.F_DETERMINISTIC if getattr(self.module, "deterministic", False) else 0)
+        call.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         keep = (x, edge_index, edge_attr)        # the structs hold raw pointers: keep the tensors alive
-        if self.weight_cache and tape_ws is None:      # (training forwards too: every chunk whose weights the step changed is split again)
+        if call.weight_cache:
             wc = self.weight_plane_cache(model, dev, stream)
             call.weight_cache, call.weight_cache_bytes = wc.data_ptr(), wc.numel()
             keep = keep + (wc,)
@@ -277,19 +305,11 @@ class ForwardEngine:
     def plan(self, n_nodes, n_edges, n_edges_total=None, node_range=None, row_range=None, training=False, flags=0,
              params=None, device=None, weight_cache=True) -> types.SimpleNamespace:
         """Which kernels a call of these sizes would run (mtmc_mpn_plan_call: host-only, nothing is launched and no GPU
-        is needed) -- lets a multi-GPU host, or a test, check that a shard takes the kernels the whole graph would."""
-        params = self.params() if params is None else params
-        model = self.model_struct(params[0].device if device is None else device, params)
-        call = _lib.Call()
-        call.n_nodes, call.n_edges = int(n_nodes), int(n_edges)
-        call.n_edges_total = int(n_edges if n_edges_total is None else n_edges_total)
-        call.node_lo, call.node_hi = (0, int(n_nodes)) if node_range is None else (int(node_range[0]), int(node_range[1]))
-        if row_range is not None:
-            rlo, rhi = int(row_range[0]), int(row_range[1])
-            call.row_lo, call.row_hi = (rlo, rhi) if rhi > rlo else (max(rlo, 1), max(rlo, 1))
-        call.training, call.flags = int(bool(training)), int(flags)
-        if weight_cache:                               # (tested for NULL by the query, never read)
-            call.weight_cache, call.weight_cache_bytes = 256, 1 << 62
+        is needed) -- lets a multi-GPU host, or a test, check that a shard takes the kernels the whole graph would.
+        No pointer is read, so the configuration is all it needs: `params` and `device` are accepted and ignored."""
+        model = self.shape_model(dropout=True)
+        node_lo, node_hi = (0, None) if node_range is None else node_range[:2]
+        call = self.call_struct(n_nodes, n_edges, n_edges_total, node_lo, node_hi, row_range, training, flags, weight_cache)
         out = _lib.Plan()
         _lib.check(self.lib.mtmc_mpn_plan_call(C.byref(model), C.byref(call), C.byref(out)))
         n_layers = len(self.spec.enc_node)
@@ -381,20 +401,13 @@ class ForwardEngine:
         return lay
 
     def run_phases(self, prep, after_phase=None, before_phase=None):
-        """Phase-by-phase forward (same kernels as __call__): the multi-GPU host interleaves collectives
-        through `after_phase(phase, arg)`, bench.py brackets phases with events."""
-        with torch.cuda.device(prep.dev):
+        """Phase-by-phase forward (the kernels of mtmc_mpn_forward, one library call per phase): bench.py brackets the phases
+        with events through `before_phase(phase, arg)` / `after_phase(phase, arg)`."""
+        with torch.cuda.device(prep.dev):             # (the callbacks record their events on the call's device)
             for ph, arg in self.phase_list():
                 if before_phase is not None:
                     before_phase(ph, arg)
-                _lib.check(self.lib.mtmc_mpn_run_phase(C.byref(prep.model), C.byref(prep.call), ph, arg))
+                self.run_phase(prep, ph, arg)
                 if after_phase is not None:
                     after_phase(ph, arg)
-        return [prep.logits[i] for i in range(prep.n_out)], prep.h
-
-    def __call__(self, x, edge_index, edge_attr, training=False) -> Tuple[List[torch.Tensor], torch.Tensor]:
-        """The bound module's forward, through the registered op (torch.ops.mtmc_mpn.mp_forward)."""
-        if self.module is None:
-            raise RuntimeError("mtmc_mpn: engine built from a spec has no module to call")
-        out, h = self.module(types.SimpleNamespace(x=x, edge_index=edge_index, edge_attr=edge_attr))
-        return out["classified_edges"], h
+        return self.outputs(prep)

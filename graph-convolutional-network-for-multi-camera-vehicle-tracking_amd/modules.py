@@ -123,9 +123,9 @@ class MOTMPNet(nn.Module):
         self.num_class_steps = s.num_class_steps
         self.check_indices = False          # True: synchronise and raise IndexError on out-of-range edge_index
         self.deterministic = False          # True: order-independent sum/mean aggregation on row-sorted edge lists
-        # Eval mode: the fp16 operand planes of the node-encoder WEIGHTS are kept from one forward to the next in a buffer the
-        # library verifies against the weights' content on the device on every call (64-bit fingerprints per 8 weight rows,
-        # engine.weight_plane_cache): optimizer steps, `param.data` writes, a new module at the old addresses are all seen -- any
+        # The fp16 operand planes of the node-encoder WEIGHTS are kept from one forward to the next (eval and training alike;
+        # a backward has no cache) in a buffer the library verifies against the weights' content on the device on every call
+        # (64-bit fingerprints per 8 weight rows, engine.weight_plane_cache): optimizer steps, `param.data` writes, a new module at the old addresses are all seen -- any
         # single changed word always, a change of several words up to a chance of about 2^-64 per 8 rows.  False: no cache
         # (few-row graphs then run the split-K kernels of rounds 1-4).
         self.cache_weight_planes = True
@@ -158,11 +158,8 @@ class MOTMPNet(nn.Module):
             with torch.cuda.graph(graph, stream=side):    # captured on the SAME stream: nothing of the engine's is allocated inside
                 out = self.forward(data)
             torch.cuda.current_stream(dev).wait_stream(side)
-            # the buffers the captured kernels use must live exactly as long as the graph: take them out of the engine's
-            # per-stream dictionaries (nothing else uses this stream; a later, larger forward would otherwise replace them)
-            key = (dev, side.cuda_stream)
-            held = [buf for buf in (op_engine._ws.pop(key, None), op_engine._wc.pop(key, None)) if buf is not None]
-            held.append(side)
+            # the buffers the captured kernels use must live exactly as long as the graph (nothing else uses this stream)
+            held = op_engine.take_stream_buffers(dev, side.cuda_stream) + [side]
 
         def replay():
             graph.replay()
@@ -224,9 +221,7 @@ class MOTMPNet(nn.Module):
             loss = step()
         torch.cuda.current_stream(dev).wait_stream(side)
         from . import torch_ops
-        eng = torch_ops.engine_for(self._config_key)
-        key = (dev, side.cuda_stream)
-        held = [buf for buf in (eng._ws.pop(key, None), eng._wc.pop(key, None)) if buf is not None] + [side]
+        held = torch_ops.engine_for(self._config_key).take_stream_buffers(dev, side.cuda_stream) + [side]
 
         def replay():
             graph.replay()

@@ -21,13 +21,13 @@ from __future__ import annotations
 
 import ctypes as C
 import json
-from typing import List, Optional, Tuple
+import types
 
 import torch
-from torch import Tensor
 
 from . import _lib
 from . import config as _config
+from .engine import ForwardEngine, _check_param, layer_slots, n_classified_steps
 
 CHECK_INDICES = 1 << 16          # host-side flag bit of `flags`: synchronise and raise IndexError on bad edge_index
 NO_WEIGHT_CACHE = 1 << 17        # host-side: no weight-plane cache for this call (engine.weight_plane_cache)
@@ -46,7 +46,6 @@ def engine_for(config: str):
         ok, why = _config.check_supported(spec)
         if not ok:
             raise NotImplementedError("mtmc_mpn HIP path does not cover this GRAPH_NET_PARAMS: " + why)
-        from .engine import ForwardEngine
         eng = _ENGINES[config] = ForwardEngine(spec)
     return eng
 
@@ -56,33 +55,15 @@ _GRAD_LAYOUTS = {}
 
 def grad_layout(spec):
     """(offset, numel, shape) of every parameter gradient inside the flat buffer mp_backward returns (256-byte pieces;
-    the rule of mtmc_mpn_grad_layout in csrc/api_train.hip)."""
+    the rule of mtmc_mpn_grad_layout in csrc/api_train.hip), and the buffer's length."""
+    slots = layer_slots(spec)
     key = tuple((slot, idx, layer.in_dim, layer.out_dim, layer.bn_slot is not None)
-                for slot, idx, layer in _layer_slots(spec))      # by content: id(spec) can be reused after a collection
+                for slot, idx, layer in slots)                    # by content: id(spec) can be reused after a collection
     hit = _GRAD_LAYOUTS.get(key)
     if hit is not None:
         return hit
-    res = _grad_layout(spec)
-    _GRAD_LAYOUTS[key] = res
-    return res
-
-
-def _grad_views(flat, layout):
-    """The 34 gradient tensors as views of the flat buffer: one as_strided each (a slice + a view per tensor was 68 dispatcher
-    calls per backward, a tenth of the launch-by-launch step's host time on a slow host)."""
-    base = flat.storage_offset()
-    return [flat.as_strided(shp, (shp[1], 1) if len(shp) == 2 else (1,), base + o) for o, _, shp in layout]
-
-
-def _layer_slots(spec):
-    from .engine import layer_slots
-    return layer_slots(spec)
-
-
-def _grad_layout(spec):
-    from .engine import layer_slots
     out, total = [], 0
-    for _, _, layer in layer_slots(spec):
+    for _, _, layer in slots:
         shapes = [(layer.out_dim, layer.in_dim), (layer.out_dim,)]
         if layer.bn_slot is not None:
             shapes += [(layer.out_dim,), (layer.out_dim,)]
@@ -92,7 +73,24 @@ def _grad_layout(spec):
                 n *= d
             out.append((total, n, shp))
             total += (n + 63) // 64 * 64
+    _GRAD_LAYOUTS[key] = out, total
     return out, total
+
+
+def _grad_list(flat, spec):
+    """The 34 parameter gradients as views of the flat buffer: one as_strided each (a slice + a view per tensor was 68
+    dispatcher calls per backward, a tenth of the launch-by-launch step's host time on a slow host).  Without message-passing
+    rounds the update MLPs took no part: None for theirs, as autograd gives the reference."""
+    base = flat.storage_offset()
+    grads = [flat.as_strided(shp, (shp[1], 1) if len(shp) == 2 else (1,), base + o) for o, _, shp in grad_layout(spec)[0]]
+    if spec.num_enc_steps == 0:
+        i = 0
+        for slot, _, layer in layer_slots(spec):
+            k = 4 if layer.bn_slot is not None else 2
+            if slot in ("upd_edge", "upd_node"):
+                grads[i:i + k] = [None] * k
+            i += k
+    return grads
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -112,21 +110,14 @@ torch.library.define("mtmc_mpn::scatter_mean", "(Tensor src, Tensor index, int d
 torch.library.define("mtmc_mpn::scatter_max", "(Tensor src, Tensor index, int dim, int? dim_size) -> (Tensor, Tensor)")
 
 
-def _n_out(spec):
-    return min(spec.num_class_steps, spec.num_enc_steps) if spec.num_enc_steps > 0 else 1
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # the forward
 # ---------------------------------------------------------------------------------------------------------------
 def _forward_prep(x, edge_index, edge_attr, params, config, training, seed, flags, tape):
     """One forward: returns the prepared call (structs, outputs, workspace = tape)."""
     eng = engine_for(config)
-    eng.flags = int(flags) & 0xFFFF
-    eng.weight_cache = not (int(flags) & NO_WEIGHT_CACHE)
-    prep = eng.prepare(x, edge_index, edge_attr, tape=bool(tape), seed=seed, params=list(params))
-    if tape and not training:                  # eval-mode statistics / identity Dropout, but still differentiable
-        prep.model.dropout_enc = prep.model.dropout_upd_edge = prep.model.dropout_upd_node = 0.0
+    prep = eng.prepare(x, edge_index, edge_attr, training=training, tape=bool(tape), seed=seed, params=list(params),
+                       flags=flags & 0xFFFF, weight_cache=not (flags & NO_WEIGHT_CACHE))
     with torch.cuda.device(prep.dev):
         _lib.check(eng.lib.mtmc_mpn_forward(C.byref(prep.model), C.byref(prep.call)))
         if flags & CHECK_INDICES:
@@ -154,7 +145,7 @@ def _mp_forward_fake(x, edge_index, edge_attr, params, config, training, seed, f
     if tape:                                   # the real op returns the training workspace: size it from the dimensions
         model = eng.shape_model()
         tape_bytes = int(eng.lib.mtmc_mpn_train_workspace_bytes(C.byref(model), int(x.shape[0]), int(e))) + 256
-    return (x.new_empty((_n_out(spec), e, spec.cls_edge[0].out_dim)), x.new_empty((x.shape[0], spec.node_dim)),
+    return (x.new_empty((n_classified_steps(spec), e, spec.cls_edge[0].out_dim)), x.new_empty((x.shape[0], spec.node_dim)),
             x.new_empty((tape_bytes,), dtype=torch.uint8))
 
 
@@ -163,12 +154,10 @@ def _mp_backward(tape, x, edge_index, edge_attr, params, config, training, seed,
     """prep: the forward's prepared call (the lean autograd path keeps it: same tensors, same structs); None: rebuilt.
     d_steps: the gradients of the classified steps as separate [E, C] tensors (None entries: no gradient), instead of d_logits."""
     eng = engine_for(config)
-    eng.flags = int(flags) & 0xFFFF
     spec = eng.spec
     if prep is None:
-        prep = eng.prepare(x, edge_index, edge_attr, tape=True, seed=seed, params=list(params), tape_ws=tape)
-        if not training:
-            prep.model.dropout_enc = prep.model.dropout_upd_edge = prep.model.dropout_upd_node = 0.0
+        prep = eng.prepare(x, edge_index, edge_attr, training=training, tape=True, seed=seed, params=list(params),
+                           tape_ws=tape, flags=flags & 0xFFFF, weight_cache=not (flags & NO_WEIGHT_CACHE))
     dev = prep.dev
     _, total = grad_layout(spec)                          # == mtmc_mpn_grad_layout (tests/test_torch_ops_registration.py)
     flat = torch.empty(total, dtype=torch.float32, device=dev)
@@ -176,7 +165,7 @@ def _mp_backward(tape, x, edge_index, edge_attr, params, config, training, seed,
     dattr = torch.empty((prep.e, spec.enc_edge[0].in_dim), device=dev) if need_attr else flat.new_empty(0)
     dl = d_logits.contiguous().float() if d_logits is not None else None
     dh = d_h.contiguous().float() if d_h is not None else None
-    n_steps = _n_out(spec)
+    n_steps = n_classified_steps(spec)
     step_bytes = 4 * prep.e * spec.cls_edge[0].out_dim
     if d_steps is not None:
         d_steps = [t.contiguous().float() if t is not None and t.numel() else None for t in d_steps]   # (kept alive to the call)
@@ -220,17 +209,7 @@ def _autograd_backward(ctx, d_logits, d_h, _d_tape):
     # version counter.  A repeated backward recomputes the same gradients (tests/test_gpu_training.py).
     flat, dx, dattr = torch.ops.mtmc_mpn.mp_backward(tape.data, x, edge_index, edge_attr, params, ctx.config, ctx.training,
                                                       ctx.seed, ctx.flags, d_logits, d_h, ctx.need_x, ctx.need_attr)
-    spec = engine_for(ctx.config).spec
-    layout, _ = grad_layout(spec)
-    grads = _grad_views(flat, layout)
-    if spec.num_enc_steps == 0:               # the update MLPs took no part: None, as autograd gives the reference
-        from .engine import layer_slots
-        i = 0
-        for slot, _, layer in layer_slots(spec):
-            k = 4 if layer.bn_slot is not None else 2
-            if slot in ("upd_edge", "upd_node"):
-                grads[i:i + k] = [None] * k
-            i += k
+    grads = _grad_list(flat, engine_for(ctx.config).spec)
     return (dx if ctx.need_x else None, None, dattr if ctx.need_attr else None, grads, None, None, None, None, None)
 
 
@@ -267,7 +246,6 @@ class _MpForwardLean(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *d_out):
-        import types
         d_steps, d_h = d_out[:-1], d_out[-1]
         ws, *rest = ctx.saved_tensors
         keep, params = rest[:ctx.n_keep], rest[ctx.n_keep:]
@@ -276,16 +254,7 @@ class _MpForwardLean(torch.autograd.Function):
         x, edge_index, edge_attr = keep[0], keep[1], keep[2]
         flat, dx, dattr = _mp_backward(ws, x, edge_index, edge_attr, params, ctx.config, ctx.training, ctx.seed, ctx.flags,
                                        None, d_h, ctx.need_x, ctx.need_attr, prep=prep, d_steps=d_steps)
-        spec = engine_for(ctx.config).spec
-        layout, _ = grad_layout(spec)
-        grads = _grad_views(flat, layout)
-        if spec.num_enc_steps == 0:           # the update MLPs took no part: None, as autograd gives the reference
-            i = 0
-            for slot, _, layer in _layer_slots(spec):
-                k = 4 if layer.bn_slot is not None else 2
-                if slot in ("upd_edge", "upd_node"):
-                    grads[i:i + k] = [None] * k
-                i += k
+        grads = _grad_list(flat, engine_for(ctx.config).spec)
         return (dx if ctx.need_x else None, None, dattr if ctx.need_attr else None, None, None, None, None, *grads)
 
 
@@ -301,7 +270,6 @@ def mp_forward_lean(x, edge_index, edge_attr, params, config, training, seed, fl
 @torch.library.impl("mtmc_mpn::encode_nodes", "CUDA")
 def _encode_nodes(x, params, config):
     from . import ops
-    from .engine import _check_param
     eng = engine_for(config)
     layers = eng.spec.enc_node
     if x.dim() != 2 or x.shape[1] != layers[0].in_dim or len(params) != 4 * len(layers):

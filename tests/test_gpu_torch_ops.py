@@ -157,3 +157,69 @@ def test_a_replaced_parameter_is_the_one_used_and_the_one_that_gets_the_gradient
     out.sum().backward()
     assert cls.bias.grad is not None and old.grad is None
     assert torch.allclose(cls.bias.grad, torch.full_like(cls.bias, float(out.shape[0])))
+
+
+def test_modules_of_one_configuration_keep_their_own_settings():
+    """Two modules of one configuration share one op engine (torch_ops.engine_for).  `deterministic` and
+    `cache_weight_planes` are per-call arguments to it: alternating the modules' forwards, every call carries its own
+    module's flags and cache setting -- settings that pick other kernels on this graph -- and computes what the module
+    computes when it runs alone."""
+    from mtmc_mpn import _lib
+    c = Case("g4_s02_L3")
+    plain, det = c.model().cuda().eval(), c.model().cuda().eval()
+    plain.cache_weight_planes = False
+    det.deterministic = True
+    _, x, ei, ea = _inputs(c)
+    data = types.SimpleNamespace(x=x, edge_index=ei, edge_attr=ea)
+    want = {id(plain): (0, False), id(det): (_lib.F_DETERMINISTIC, True)}
+    with torch.no_grad():
+        alone = {}
+        for m in (plain, det):
+            for _ in range(2):
+                out, h = m(data)
+            alone[id(m)] = ([t.clone() for t in out["classified_edges"]], h.clone())
+        eng = torch_ops.engine_for(plain._config_key)
+        assert eng is torch_ops.engine_for(det._config_key)
+        n, e = x.shape[0], ei.shape[1]
+        p_plain, p_det = (eng.plan(n, e, flags=f, weight_cache=wc) for f, wc in (want[id(plain)], want[id(det)]))
+        assert p_plain.pass_c != p_det.pass_c and p_plain.enc_kernel != p_det.enc_kernel      # the settings matter here
+        seen, prepare = [], eng.prepare
+
+        def spy(*args, **kw):
+            prep = prepare(*args, **kw)
+            seen.append((prep.call.flags, bool(prep.call.weight_cache)))
+            return prep
+        eng.prepare = spy
+        try:
+            order = [plain, det, det, plain, det, plain]
+            results = [m(data) for m in order]
+        finally:
+            del eng.prepare
+        torch.cuda.synchronize()
+    assert seen == [want[id(m)] for m in order]
+    assert not hasattr(eng, "flags") and not hasattr(eng, "weight_cache")
+    for m, (out, h) in zip(order, results):
+        ref_out, ref_h = alone[id(m)]
+        if m is det:                               # fixed-order aggregation on a row-sorted list: h repeats bit for bit
+            assert torch.equal(h, ref_h)
+        assert (h - ref_h).abs().max().item() <= 1e-6 * ref_h.abs().max().item()
+        for a, b in zip(out["classified_edges"], ref_out):
+            assert (a - b).abs().max().item() <= 2e-6
+
+
+def test_prepare_gives_an_eval_mode_tape_identity_dropout():
+    """prepare(tape=True, training=False) -- grad mode under .eval() -- zeroes the three Dropout rates in the struct of that
+    call alone; the training call after it, and a call without a tape, carry the configured ones."""
+    c = Case("g3_cams324_L2")
+    m = c.model().cuda().eval()
+    _, x, ei, ea = _inputs(c)
+    eng = engine.ForwardEngine(m)
+    rates = lambda model: (model.dropout_enc, model.dropout_upd_edge, model.dropout_upd_node)      # noqa: E731
+    configured = rates(eng.model_struct(x.device))
+    assert all(r > 0 for r in configured)
+    for _ in range(2):
+        evl = eng.prepare(x, ei, ea, tape=True)
+        assert rates(evl.model) == (0.0, 0.0, 0.0) and evl.call.training == 1
+        trn = eng.prepare(x, ei, ea, tape=True, training=True)
+        assert rates(trn.model) == configured and trn.call.training == 1
+        assert rates(eng.prepare(x, ei, ea).model) == configured

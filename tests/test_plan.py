@@ -114,3 +114,39 @@ def test_plan_rejects_inconsistent_ranges(eng):
         eng.plan(100, 50, 10)                           # more local edges than the graph has
     with pytest.raises(RuntimeError):
         eng.plan(100, 50, node_range=(10, 200))
+
+
+DET = _lib.F_DETERMINISTIC
+PLAN_CASES = [                                         # the sizes of the tests above, with the keywords they use
+    (450, 150_454, {}), (450, 150_454, dict(weight_cache=False)), (450, 150_454, dict(flags=DET)),
+    (450, 75_000, dict(n_edges_total=150_454, node_range=(0, 225))),
+    (1002, 751_202, {}), (1480, 1_642_800, {}), (2000, 100_000, {}), (100_000, 10_000_000, {}),
+    (100_000, 10_000_000, dict(flags=DET)), (N5, E5, {}), (N5, E5, dict(training=True)), (1_000_000, 20_000_000, {}),
+    (440, 180_000, dict(training=True)), (440, 180_000, dict(training=True, weight_cache=False)),
+    (1480, 1_642_800, dict(training=True)),
+    (N5, E5 // 8, dict(n_edges_total=E5, node_range=(0, N5 // 8), row_range=(0, N5 // 8))),
+    (100_000, 600_000, dict(n_edges_total=10_000_000, node_range=(0, 50_000), row_range=(0, 50_000))),
+    (100_000, 0, dict(n_edges_total=10_000_000, node_range=(0, 0), row_range=(7, 7))),
+    (1 << 24, 300_000_000, dict(n_edges_total=2_000_000_000, node_range=(0, 1 << 21), row_range=(0, 1 << 21), flags=DET)),
+]
+
+
+@pytest.mark.parametrize("n,e,kw", PLAN_CASES)
+def test_plan_needs_the_configuration_only(eng, n, e, kw):
+    """The plan query reads no pointer: an engine built from the spec alone (what torch.ops.mtmc_mpn.* use; no module, no
+    parameters, no device) plans every call as the module-bound engine does, and as the struct filled from the module's real
+    tensors does.  `params=` / `device=` are still accepted."""
+    import ctypes as C
+    import torch
+    bound = vars(eng.plan(n, e, **kw))
+    assert vars(engine.ForwardEngine(eng.spec).plan(n, e, **kw)) == bound
+    assert vars(eng.plan(n, e, params=eng.params(), device=torch.device("cpu"), **kw)) == bound
+    lo, hi = kw.get("node_range", (0, n))[:2]
+    call = eng.call_struct(n, e, kw.get("n_edges_total"), lo, hi, kw.get("row_range"), kw.get("training", False),
+                           kw.get("flags", 0), kw.get("weight_cache", True))
+    real, out = eng.model_struct(torch.device("cpu")), _lib.Plan()
+    _lib.check(_lib.load().mtmc_mpn_plan_call(C.byref(real), C.byref(call), C.byref(out)))
+    assert list(out.enc_kernel)[:4] == bound["enc_kernel"] and list(out.enc_split_k)[:4] == bound["enc_split_k"]
+    for name in ("edges_per_thread", "lazy_edges", "pass_c", "avg_degree", "pass_a_col_blocks", "layer0_panels",
+                 "enc2_passenger", "node_stat_folded"):
+        assert getattr(out, name) == bound[name], name
