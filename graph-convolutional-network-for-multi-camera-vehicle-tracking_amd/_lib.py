@@ -86,7 +86,8 @@ EXPORTS = ["mtmc_mpn_abi_version", "mtmc_mpn_last_error", "mtmc_mpn_workspace_by
            "mtmc_build_graph", "mtmc_postprocess_workspace_bytes", "mtmc_postprocess",
            "mtmc_cross_entropy_forward", "mtmc_cross_entropy_backward",
            "mtmc_cross_entropy_steps_forward", "mtmc_cross_entropy_steps_backward", "mtmc_mpn_backward_steps", "mtmc_mpn_backward_flat", "mtmc_mpn_grad_layout", "mtmc_linear_raw", "mtmc_edge_confusion",
-           "mtmc_linear_presplit_raw", "mtmc_linear_staged_raw", "mtmc_linear_few_raw", "mtmc_mpn_weight_cache_bytes"]
+           "mtmc_linear_presplit_raw", "mtmc_linear_staged_raw", "mtmc_linear_few_raw", "mtmc_mpn_weight_cache_bytes",
+           "mtmc_graph_backward_workspace_bytes", "mtmc_build_graph_backward"]
 
 _lib = None
 
@@ -124,6 +125,11 @@ def load() -> C.CDLL:
     lib.mtmc_graph_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.mtmc_build_graph.restype = C.c_int32
     lib.mtmc_build_graph.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
+        [C.c_int32, C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
+    lib.mtmc_graph_backward_workspace_bytes.restype = C.c_size_t
+    lib.mtmc_graph_backward_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.mtmc_build_graph_backward.restype = C.c_int32
+    lib.mtmc_build_graph_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
         [C.c_int32, C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
     lib.mtmc_mpn_backward_steps.restype = C.c_int32
     lib.mtmc_mpn_backward_steps.argtypes = [C.POINTER(Model), C.POINTER(Call), C.POINTER(C.c_void_p), C.c_void_p,

@@ -37,18 +37,9 @@ def camera_tables(cam_ids):
             np.asarray(out_off, dtype=np.int64), np.asarray(block_off, dtype=np.int64), len(uniq))
 
 
-def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: bool = True):
-    """node_feats: [N, F] float32 on a ROCm GPU (the stacked per-tracklet ReID features); cam_ids: N camera ids
-    (host list / array, as the reference keeps them); node_labels: optional N identities (edge labels for training)."""
-    if not (isinstance(node_feats, torch.Tensor) and node_feats.is_cuda):
-        raise RuntimeError("mtmc_mpn.build_graph: node_feats must be on a ROCm GPU (no CPU path)")
-    if node_feats.dim() != 2 or node_feats.dtype != torch.float32 or node_feats.shape[1] % 32:
-        raise RuntimeError("mtmc_mpn.build_graph: node_feats must be float32 [N, F] with F a multiple of 32")
+def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool):
+    """The raw library call: (x, edge_pairs [E,2], edge_attr, edge_labels, labels_dev) and what a backward needs again."""
     n, f = node_feats.shape
-    if len(cam_ids) != n:
-        raise RuntimeError("mtmc_mpn.build_graph: one camera id per node expected")
-    if n > MAX_NODES:
-        raise NotImplementedError(f"mtmc_mpn.build_graph: the Gram-matrix builder handles up to {MAX_NODES} nodes")
     dev = node_feats.device
     feats = node_feats if (node_feats.stride(1) == 1 and node_feats.stride(0) % 4 == 0) else node_feats.contiguous()
     in_list, in_off, out_list, out_off, block_off, n_cams = camera_tables(cam_ids)
@@ -77,5 +68,67 @@ def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: boo
             ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise RuntimeError(f"mtmc_mpn.build_graph failed (code {rc})")
-    return types.SimpleNamespace(x=x, edge_index=edge_pairs.t(), edge_attr=edge_attr, edge_labels=edge_labels,
-                                 y=labels_dev)
+    return (x, edge_pairs, edge_attr, edge_labels, labels_dev), (feats, (t_in, t_inoff, t_out, t_outoff, t_blk), n_cams, e)
+
+
+class _BuildGraph(torch.autograd.Function):
+    """`build_graph` with its HIP backward to the node features (`mtmc_build_graph_backward`): the reference's fine-tuning
+    chain (train.py:304-342) without its two [E, F] gathers -- one [N, N] x [N, F] product on the matrix cores."""
+
+    @staticmethod
+    def forward(ctx, node_feats, cam_ids, node_labels, l2norm):
+        (x, edge_pairs, edge_attr, edge_labels, labels_dev), (feats, tables, n_cams, e) = \
+            _build(node_feats.detach(), cam_ids, node_labels, l2norm)
+        edge_index = edge_pairs.t()
+        ctx.save_for_backward(feats, x, edge_attr, *tables)
+        ctx.meta = (bool(l2norm), n_cams, e)
+        ctx.mark_non_differentiable(*[t for t in (edge_index, edge_labels, labels_dev) if t is not None])
+        return x, edge_index, edge_attr, edge_labels, labels_dev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x, _g_index, g_attr, _g_labels, _g_y):
+        feats, x, edge_attr, t_in, t_inoff, t_out, t_outoff, t_blk = ctx.saved_tensors
+        l2norm, n_cams, e = ctx.meta
+        n, f = x.shape
+        dev = x.device
+        if e == 0:
+            g_attr = None
+        if g_x is None and g_attr is None:
+            return torch.zeros((n, f), dtype=torch.float32, device=dev), None, None, None
+        g_x = g_x.contiguous().float() if g_x is not None else None
+        g_attr = g_attr.contiguous().float() if g_attr is not None else None
+        lib = _lib.load()
+        d_feats = torch.empty((n, f), dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.mtmc_graph_backward_workspace_bytes(n, f) + 256, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.mtmc_build_graph_backward(
+                feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
+                t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
+                n_cams, e, x.data_ptr(), edge_attr.data_ptr() if e else None,
+                g_x.data_ptr() if g_x is not None else None, g_attr.data_ptr() if g_attr is not None else None,
+                d_feats.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mtmc_mpn.build_graph backward failed (code {rc})")
+        return d_feats, None, None, None
+
+
+def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: bool = True):
+    """node_feats: [N, F] float32 on a ROCm GPU (the stacked per-tracklet ReID features); cam_ids: N camera ids
+    (host list / array, as the reference keeps them); node_labels: optional N identities (edge labels for training).
+    With grad mode on and `node_feats.requires_grad`, `x` and `edge_attr` carry the gradient back to `node_feats`."""
+    if not (isinstance(node_feats, torch.Tensor) and node_feats.is_cuda):
+        raise RuntimeError("mtmc_mpn.build_graph: node_feats must be on a ROCm GPU (no CPU path)")
+    if node_feats.dim() != 2 or node_feats.dtype != torch.float32 or node_feats.shape[1] % 32:
+        raise RuntimeError("mtmc_mpn.build_graph: node_feats must be float32 [N, F] with F a multiple of 32")
+    n, f = node_feats.shape
+    if len(cam_ids) != n:
+        raise RuntimeError("mtmc_mpn.build_graph: one camera id per node expected")
+    if n > MAX_NODES:
+        raise NotImplementedError(f"mtmc_mpn.build_graph: the Gram-matrix builder handles up to {MAX_NODES} nodes")
+    if torch.is_grad_enabled() and node_feats.requires_grad:
+        x, edge_index, edge_attr, edge_labels, labels_dev = _BuildGraph.apply(node_feats, cam_ids, node_labels, l2norm)
+    else:
+        (x, edge_pairs, edge_attr, edge_labels, labels_dev), _ = _build(node_feats, cam_ids, node_labels, l2norm)
+        edge_index = edge_pairs.t()
+    return types.SimpleNamespace(x=x, edge_index=edge_index, edge_attr=edge_attr, edge_labels=edge_labels, y=labels_dev)

@@ -328,6 +328,23 @@ int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_
                          float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Backward of the construction to the node features (the reference's CNN_MODEL.finetune chain, train.py:304-342:
+ * autograd through F.normalize(dim=0), F.pairwise_distance and 1 - F.cosine_similarity along the edge list).
+ * feats, l2norm and the five camera tables as in the forward call (in_list per camera and out_list per camera
+ * ascending, as graph_build.camera_tables writes them); x [N][F] and edge_attr [E][2] as the forward produced them;
+ * d_x [N][F] and d_edge_attr [E][2]: incoming gradients, either may be NULL (= zero), both only when n_edges == 0;
+ * d_feats_out [N][F] contiguous, distinct from x and d_x.  One dense product (M + M^T) . x on the fp32 matrix cores
+ * with M [N][N] filled from 16 bytes per edge -- no [E][F] intermediate; workspace O(N^2 + N + F).  Everything is
+ * enqueued on `stream`, nothing synchronises.  MTMC_E_ARG on null / misaligned pointers (16 bytes for the matrices,
+ * 8 for the edge arrays, 256 for the workspace) or sizes outside the forward's, MTMC_E_WORKSPACE on a short workspace.
+ * The workspace query returns 0 outside 1 <= n_nodes <= 46000 or for a feat_dim that is no multiple of 32. */
+size_t mtmc_graph_backward_workspace_bytes(int64_t n_nodes, int32_t feat_dim);
+int32_t mtmc_build_graph_backward(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
+                                  const int32_t* in_list, const int32_t* in_off, const int32_t* out_list,
+                                  const int64_t* out_off, const int64_t* block_off, int32_t n_cams, int64_t n_edges,
+                                  const float* x, const float* edge_attr, const float* d_x, const float* d_edge_attr,
+                                  float* d_feats_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the training callers' loss: F.cross_entropy / nn.CrossEntropyLoss(weight, reduction) on [n][n_classes<=4]
  * logits (reference train.py:88-93, :109-142, :178-186).  mode 0 = mean, 1 = sum, 2 = none.
  * forward: per_sample[i] = w[y_i] * (logsumexp(x_i) - x_i[y_i]) (NULL to skip); sums = f64[2*MTMC_STAT_REPLICAS]
