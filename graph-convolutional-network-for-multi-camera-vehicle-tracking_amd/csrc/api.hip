@@ -244,50 +244,52 @@ int32_t mtmc_mlp_layer_forward(const mtmc_layer* layer, const float* x, int64_t 
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (bn && hipMemsetAsync(stats_scratch, 0, 2 * (size_t)layer->out_dim * sizeof(double), s) != hipSuccess)
     return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  mtmc::GemmParams g;
-  g.A = x; g.lda = x_row_stride; g.W = layer->weight; g.bias = layer->bias; g.Y = y; g.ldy = layer->out_dim;
-  g.stats_in = nullptr; g.gamma_in = nullptr; g.beta_in = nullptr; g.count = (double)rows;
-  g.stats_out = bn ? stats_scratch : nullptr; g.M = rows; g.K = layer->in_dim; g.Nout = layer->out_dim;
-  g.slab = nullptr; g.split_k = 1; g.drop_in = {0, 0, 1.f, 0}; g.drop_stream = 0;
+  mtmc::GemmParams g =
+      mtmc::plain_gemm(x, x_row_stride, layer->weight, layer->bias, y, layer->out_dim, rows, layer->in_dim, layer->out_dim);
+  if (bn) g.stats_out = stats_scratch;
   if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "unsupported layer shape");
-  if (bn) {
-    mtmc::Drop nodrop = {0, 0, 1.f, 0};
-    mtmc::launch_bn_relu_rows(y, layer->out_dim, rows, layer->out_dim, stats_scratch, layer->gamma, layer->beta, (double)rows, y, nodrop, 0, 0, s);
-  }
+  if (bn)
+    mtmc::launch_bn_relu_rows(y, layer->out_dim, rows, layer->out_dim, stats_scratch, layer->gamma, layer->beta, (double)rows, y,
+                              mtmc::kNoDrop, 0, 0, s);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "mlp layer launch failed: %s", hipGetErrorString(e));
 }
 
-// Diagnostics / unit tests: Y[M][N] = A[M][K] . W[N][K]^T + bias through the node encoder's GEMM dispatch exactly as
-// the forward uses it for layer 0 (operand |.|max gathered by prep_kernel's passenger workgroups, fp16 two-piece
-// kernel where it applies).  scratch: u32[48], stats: f64[2*N] or NULL.
+// ---- Diagnostics / unit tests: one encoder layer on the kernel the forward would run it on.  In all four, scratch: u32[48] =
+// the |A|max, |W|max, |Y|max words; stats: f64[2*N] column sum / sumsq of Y, or NULL; work: kernels.h raw_work unless said.
+static int raw_begin(uint32_t* scratch, double* stats, int N, hipStream_t s) {
+  return mtmc::clear_raw(scratch, stats, N, s) ? MTMC_OK : fail(MTMC_E_HIP, "hipMemsetAsync failed");
+}
+static int raw_end(int rc) {       // rc: the launcher's answer (0 ok, MTMC_E_HIP, anything else: shape refused)
+  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "unsupported shape or launch refused");
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "launch failed: %s", hipGetErrorString(e));
+}
+// |A|max -> scratch[0] and (W given) |W|max -> scratch[1], by prep_kernel's passenger workgroups as in the forward
+static void raw_amax(const float* A, int64_t lda, int64_t M, const float* W, int K, int N, uint32_t* scratch, hipStream_t s) {
+  mtmc::PrepParams p = {};
+  p.jobs[p.n_jobs++] = {A, M, K, lda, scratch, 0, 0};
+  if (W) p.jobs[p.n_jobs++] = {W, N, K, K, scratch + mtmc::kAmaxRep, 0, 0};
+  mtmc::launch_prep(p, s);
+}
+
+// Y[M][N] = A[M][K] . W[N][K]^T + bias through the node encoder's GEMM dispatch exactly as the forward uses it for layer 0
+// (fp16 two-piece kernel where it applies).
 int32_t mtmc_linear_raw(const float* A, int64_t lda, const float* W, const float* bias, float* Y, int64_t M, int32_t K,
                         int32_t N, uint32_t* scratch, double* stats, void* stream) {
   if (!A || !W || !bias || !Y || !scratch || M < 1 || K < 32 || K % 32 || N < 1) return fail(MTMC_E_ARG, "bad arguments");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, 3 * mtmc::kAmaxRep * sizeof(uint32_t), s) != hipSuccess) return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  if (stats && hipMemsetAsync(stats, 0, 2 * (size_t)N * sizeof(double), s) != hipSuccess) return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  mtmc::PrepParams p = {};
-  p.n_edges = 0; p.n_jobs = 2;
-  p.jobs[0] = {A, M, K, lda, scratch, 0, 0};
-  p.jobs[1] = {W, N, K, K, scratch + mtmc::kAmaxRep, 0, 0};
-  mtmc::launch_prep(p, s);
-  mtmc::GemmParams g;
-  g.A = A; g.lda = lda; g.W = W; g.bias = bias; g.Y = Y; g.ldy = N;
-  g.stats_in = nullptr; g.gamma_in = nullptr; g.beta_in = nullptr; g.count = (double)M;
-  g.stats_out = stats; g.M = M; g.K = K; g.Nout = N;
-  g.slab = nullptr; g.split_k = 1; g.drop_in = {0, 0, 1.f, 0}; g.drop_stream = 0;
-  g.amax_a = scratch; g.amax_w = scratch + mtmc::kAmaxRep; g.amax_y = scratch + 2 * mtmc::kAmaxRep;
-  if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "unsupported shape");
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "launch failed: %s", hipGetErrorString(e));
+  if (int rc = raw_begin(scratch, stats, N, s)) return rc;
+  raw_amax(A, lda, M, W, K, N, scratch, s);
+  mtmc::GemmParams g = mtmc::plain_gemm(A, lda, W, bias, Y, N, M, K, N, scratch, scratch + mtmc::kAmaxRep, scratch + 2 * mtmc::kAmaxRep);
+  g.stats_out = stats;
+  return raw_end(mtmc::launch_gemm_bn(g, s));
 }
 
-// Diagnostics / unit tests: one encoder layer >= 1 as the forward runs it on many-row graphs:
-// Y[M][N] = relu(bn(A))[M][K] . W[N][K]^T + bias, bn = BatchNorm with the given column statistics (f64 sum[K] | sumsq[K] over
-// `count` rows) and gamma / beta -- on the role-split kernel (gemm_staged.hip: N % 256 == 0, or N = 128) or, for the narrow last layer
-// (K = 128, N = 32), the row-streaming kernel (gemm_rows.hip).  work: >= 4*N*K + 4*N + 256 bytes (the weight planes of the
-// role-split kernel); scratch: u32[48]; stats: f64[2*N] or NULL.
+// A layer >= 1 of a many-row graph: Y[M][N] = relu(bn(A))[M][K] . W[N][K]^T + bias, bn = BatchNorm with the given column
+// statistics (f64 sum[K] | sumsq[K] over `count` rows) and gamma / beta -- on the role-split kernel (gemm_staged.hip:
+// N % 256 == 0, or N = 128) or, for the narrow last layer (K = 128, N = 32), the row-streaming kernel (gemm_rows.hip).
+// work: >= 4*N*K + 4*N + 256 bytes (the role-split kernel's weight planes, their row scales on the next 256-byte boundary).
 int32_t mtmc_linear_staged_raw(const float* A, int64_t lda, const double* stats_in, const float* gamma_in, const float* beta_in,
                                double count, const float* W, const float* bias, float* Y, int64_t M, int32_t K, int32_t N,
                                void* work, uint64_t work_bytes, uint32_t* scratch, double* stats, void* stream) {
@@ -298,37 +300,24 @@ int32_t mtmc_linear_staged_raw(const float* A, int64_t lda, const double* stats_
   const uint64_t iw_off = ((uint64_t)N * K * 4 + 255) / 256 * 256;
   if (work_bytes < iw_off + (uint64_t)N * 4) return fail(MTMC_E_ARG, "work buffer too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, 3 * mtmc::kAmaxRep * sizeof(uint32_t), s) != hipSuccess) return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  if (stats && hipMemsetAsync(stats, 0, 2 * (size_t)N * sizeof(double), s) != hipSuccess) return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  mtmc::PrepParams pp = {};
-  pp.n_edges = 0; pp.n_jobs = 1;
-  pp.jobs[0] = {A, M, K, lda, scratch, 0, 0};
-  mtmc::launch_prep(pp, s);
-  int rc;
+  if (int rc = raw_begin(scratch, stats, N, s)) return rc;
+  raw_amax(A, lda, M, nullptr, K, N, scratch, s);
   if (narrow) {
-    mtmc::GemmParams g;
-    g.A = A; g.lda = lda; g.W = W; g.bias = bias; g.Y = Y; g.ldy = N;
-    g.stats_in = stats_in; g.gamma_in = gamma_in; g.beta_in = beta_in; g.count = count;
-    g.stats_out = stats; g.M = M; g.K = K; g.Nout = N;
-    g.slab = nullptr; g.split_k = 1; g.drop_in = {0, 0, 1.f, 0}; g.drop_stream = 0;
-    g.amax_a = scratch; g.amax_w = nullptr; g.amax_y = scratch + 2 * mtmc::kAmaxRep;
-    rc = mtmc::launch_gemm_rows(g, s);
-  } else {
-    unsigned char* wk = static_cast<unsigned char*>(work);
-    mtmc::launch_split_rows(W, K, N, K, wk, reinterpret_cast<float*>(wk + iw_off), s);
-    mtmc::StagedGemmParams g;
-    g.A = A; g.lda = lda; g.stats_in = stats_in; g.gamma_in = gamma_in; g.beta_in = beta_in; g.count = count;
-    g.amax_a = scratch; g.Wh = reinterpret_cast<const _Float16*>(wk); g.inv_w = reinterpret_cast<const float*>(wk + iw_off);
-    g.bias = bias; g.Y = Y; g.ldy = N; g.stats_out = stats; g.amax_y = scratch + 2 * mtmc::kAmaxRep;
-    g.M = M; g.K = K; g.Nout = N;
-    rc = mtmc::launch_gemm_staged(g, s);
+    mtmc::GemmParams g = mtmc::plain_gemm(A, lda, W, bias, Y, N, M, K, N, scratch, nullptr, scratch + 2 * mtmc::kAmaxRep);
+    g.stats_in = stats_in; g.gamma_in = gamma_in; g.beta_in = beta_in; g.count = count; g.stats_out = stats;
+    return raw_end(mtmc::launch_gemm_rows(g, s));
   }
-  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "unsupported shape or launch refused");
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "launch failed: %s", hipGetErrorString(e));
+  mtmc::StagedGemmParams g;
+  mtmc::set_in(&g, A, lda, stats_in, gamma_in, beta_in, count);
+  g.amax_a = scratch;
+  float* inv_w = reinterpret_cast<float*>(static_cast<char*>(work) + iw_off);
+  mtmc::launch_split_rows(W, K, N, K, work, inv_w, s);
+  g.Wh = static_cast<_Float16*>(work); g.inv_w = inv_w;
+  mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
+  return raw_end(mtmc::launch_gemm_staged(g, s));
 }
 
-// Diagnostics / unit tests: one encoder layer as the forward runs it on few-row graphs (gemm_few.hip).
+// A layer of a few-row graph (gemm_few.hip): layer 0 (stats_in == NULL: x is split into planes too) or a layer >= 1.
 int32_t mtmc_linear_few_raw(const float* A, int64_t lda, const double* stats_in, const float* gamma_in, const float* beta_in,
                             double count, const float* W, const float* bias, float* Y, int64_t M, int32_t K, int32_t N,
                             void* work, uint64_t work_bytes, double* stats, void* stream) {
@@ -336,58 +325,44 @@ int32_t mtmc_linear_few_raw(const float* A, int64_t lda, const double* stats_in,
   if (!A || !W || !bias || !Y || !work || M < 1 || K < 32 || K > 2048 || N < 1 || lda < K || (lda & 3) || ((uintptr_t)A & 15) ||
       (l0 ? !mtmc::few_l0_shape(K, N) : (!mtmc::few_wave_shape(K, N) || !gamma_in || !beta_in)))
     return fail(MTMC_E_ARG, "bad arguments");
-  const uint64_t a_bytes = l0 ? (uint64_t)M * K * 4 : 0, w_bytes = (uint64_t)N * K * 4;
-  const uint64_t ia_off = a_bytes, wh_off = (ia_off + (uint64_t)M * 4 + 255) / 256 * 256, iw_off = wh_off + w_bytes;
-  if (work_bytes < iw_off + (uint64_t)N * 4) return fail(MTMC_E_ARG, "work buffer too small");
+  const mtmc::RawWork wk = mtmc::raw_work(work, M, K, N, l0);
+  if (work_bytes < wk.bytes) return fail(MTMC_E_ARG, "work buffer too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (stats && hipMemsetAsync(stats, 0, 2 * (size_t)N * sizeof(double), s) != hipSuccess) return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  unsigned char* wk = static_cast<unsigned char*>(work);
-  mtmc::launch_split_rows(W, K, N, K, wk + wh_off, reinterpret_cast<float*>(wk + iw_off), s);
-  int rc;
+  if (int rc = raw_begin(nullptr, stats, N, s)) return rc;
+  mtmc::launch_split_rows(W, K, N, K, wk.Wh, wk.inv_w, s);
   if (l0) {
-    mtmc::launch_split_rows(A, lda, M, K, wk, reinterpret_cast<float*>(wk + ia_off), s);
+    mtmc::launch_split_rows(A, lda, M, K, wk.Ah, wk.inv_a, s);
     mtmc::FewL0Params g;
-    g.Ah = reinterpret_cast<const _Float16*>(wk); g.inv_a = reinterpret_cast<const float*>(wk + ia_off);
-    g.Wh = reinterpret_cast<const _Float16*>(wk + wh_off); g.inv_w = reinterpret_cast<const float*>(wk + iw_off);
-    g.bias = bias; g.Y = Y; g.ldy = N; g.stats_out = stats; g.M = M; g.K = K; g.Nout = N;
-    rc = mtmc::launch_few_l0(g, s);
-  } else {
-    mtmc::FewWaveParams g;
-    g.A = A; g.lda = lda; g.stats_in = stats_in; g.gamma_in = gamma_in; g.beta_in = beta_in; g.count = count;
-    g.Wh = reinterpret_cast<const _Float16*>(wk + wh_off); g.inv_w = reinterpret_cast<const float*>(wk + iw_off);
-    g.bias = bias; g.Y = Y; g.ldy = N; g.stats_out = stats; g.M = M; g.K = K; g.Nout = N;
-    rc = mtmc::launch_few_wave(g, s);
+    g.Ah = wk.Ah; g.inv_a = wk.inv_a; g.Wh = wk.Wh; g.inv_w = wk.inv_w;
+    mtmc::set_out(&g, bias, Y, N, M, K, N, stats);
+    return raw_end(mtmc::launch_few_l0(g, s));
   }
-  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "unsupported shape or launch refused");
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "launch failed: %s", hipGetErrorString(e));
+  mtmc::FewWaveParams g;
+  mtmc::set_in(&g, A, lda, stats_in, gamma_in, beta_in, count);
+  g.Wh = wk.Wh; g.inv_w = wk.inv_w;
+  mtmc::set_out(&g, bias, Y, N, M, K, N, stats);
+  return raw_end(mtmc::launch_few_wave(g, s));
 }
 
+// Layer 0 of a many-row graph on pre-split operands (gemm_presplit.hip); reuse_planes: the planes in `work` are those of the
+// call before (times the GEMM alone).
 int32_t mtmc_linear_presplit_raw(const float* A, int64_t lda, const float* W, const float* bias, float* Y, int64_t M,
                                  int32_t K, int32_t N, void* work, uint64_t work_bytes, uint32_t* scratch, double* stats,
                                  int32_t reuse_planes, void* stream) {
   if (!A || !W || !bias || !Y || !work || !scratch || M < 1 || K < 64 || K % 64 || K > 2048 || N < 1)
     return fail(MTMC_E_ARG, "bad arguments");
-  const uint64_t a_bytes = (uint64_t)M * K * 4, w_bytes = (uint64_t)N * K * 4;
-  const uint64_t ia_off = a_bytes, wh_off = (ia_off + (uint64_t)M * 4 + 255) / 256 * 256, iw_off = wh_off + w_bytes;
-  if (work_bytes < iw_off + (uint64_t)N * 4) return fail(MTMC_E_ARG, "work buffer too small");
+  const mtmc::RawWork wk = mtmc::raw_work(work, M, K, N, true);
+  if (work_bytes < wk.bytes) return fail(MTMC_E_ARG, "work buffer too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, 3 * mtmc::kAmaxRep * sizeof(uint32_t), s) != hipSuccess) return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  if (stats && hipMemsetAsync(stats, 0, 2 * (size_t)N * sizeof(double), s) != hipSuccess) return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  unsigned char* wk = static_cast<unsigned char*>(work);
+  if (int rc = raw_begin(scratch, stats, N, s)) return rc;
   if (!reuse_planes) {
-    mtmc::launch_split_rows(A, lda, M, K, wk, reinterpret_cast<float*>(wk + ia_off), s);
-    mtmc::launch_split_rows(W, K, N, K, wk + wh_off, reinterpret_cast<float*>(wk + iw_off), s);
+    mtmc::launch_split_rows(A, lda, M, K, wk.Ah, wk.inv_a, s);
+    mtmc::launch_split_rows(W, K, N, K, wk.Wh, wk.inv_w, s);
   }
   mtmc::SplitGemmParams g;
-  g.Ah = reinterpret_cast<const _Float16*>(wk); g.inv_a = reinterpret_cast<const float*>(wk + ia_off);
-  g.Wh = reinterpret_cast<const _Float16*>(wk + wh_off); g.inv_w = reinterpret_cast<const float*>(wk + iw_off);
-  g.bias = bias; g.Y = Y; g.ldy = N; g.stats_out = stats; g.amax_y = scratch + 2 * mtmc::kAmaxRep;
-  g.M = M; g.K = K; g.Nout = N;
-  const int rc = mtmc::launch_gemm_presplit(g, s);
-  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "unsupported shape or launch refused");
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "launch failed: %s", hipGetErrorString(e));
+  g.Ah = wk.Ah; g.inv_a = wk.inv_a; g.Wh = wk.Wh; g.inv_w = wk.inv_w;
+  mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
+  return raw_end(mtmc::launch_gemm_presplit(g, s));
 }
 
 }  // extern "C"

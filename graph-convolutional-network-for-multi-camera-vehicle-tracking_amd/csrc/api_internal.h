@@ -2,6 +2,7 @@
 // error text, workspace carving, per-phase parameter blocks and the phase launcher.
 #pragma once
 #include "kernels.h"
+#include "train_kernels.h"
 
 #include <mutex>
 #include <stdarg.h>
@@ -39,10 +40,11 @@ struct Layout {
   bool training;
   std::vector<size_t> z_tr, e_tr, h_tr;       // per round: z1 [E][4], e' [E][4], aggregated h [N][32]
   std::vector<size_t> P_tr, Q_tr;             // per round: the node projections [2][N][4], [N][32]
-  size_t xh, inv_a, wh, inv_w; bool presplit0;   // layer 0 on pre-split operands (many-row graphs): fp16 planes + row scales
+  size_t xh, inv_a;                            // fp16 planes + row scales of x: layer 0 on pre-split operands (w_ws[0]), or few
   bool few;                                    // few-row graphs (gemm_few.hip): xh / inv_a hold the planes of x (W: weight-plane cache)
-  size_t wh_l[MTMC_MAX_ENC_LAYERS], inv_w_l[MTMC_MAX_ENC_LAYERS]; bool staged[MTMC_MAX_ENC_LAYERS];   // layers >= 1 on the
-                                               // role-split kernel (gemm_staged.hip): the layer's weight planes + row scales
+  // layer l's weight planes + row scales live in the workspace: many-row graphs in eval mode, layer 0 on pre-split operands
+  // (gemm_presplit.hip), layers >= 1 on the role-split kernel (gemm_staged.hip).  (A call with a weight-plane cache reads that.)
+  size_t wh[MTMC_MAX_ENC_LAYERS], inv_w[MTMC_MAX_ENC_LAYERS]; bool w_ws[MTMC_MAX_ENC_LAYERS];
   size_t g_e[2], g_e0, g_h[2], g_h0, g_P, g_Q, g_de2, g_arg;   // gradients wrt e_r, e0, h_r, h0, P, Q; A^T dz2 [E][4]
   size_t bst;                                  // f64[2L+1][kStatRep][kBwdStride] backward statistics blocks
   size_t bwd_zero, bwd_zero_end;               // the range the backward clears with one memset
@@ -77,6 +79,11 @@ inline bool few_shape(const mtmc_mpn_model* m, int64_t rows) {
   return mtmc::few_rows_path(rows, m->n_enc_layers, in_dim, out_dim);
 }
 
+// width of [h0 | h], the node part of the update MLPs' inputs
+inline int node_in_width(const mtmc_mpn_model* m) { return (m->reattach_nodes ? 2 : 1) * MTMC_NODE_DIM; }
+// the first step (round + 1) whose edge state is classified (mpn.py:277; num_class_steps > num_enc_steps classifies every round)
+inline int first_cls_step(const mtmc_mpn_model* m) { return std::max(1, m->num_enc_steps - m->num_class_steps + 1); }
+
 inline int check_model(const mtmc_mpn_model* m) {
   if (!m) return fail(MTMC_E_ARG, "model is NULL");
   if (m->struct_bytes != sizeof(mtmc_mpn_model))
@@ -93,7 +100,7 @@ inline int check_model(const mtmc_mpn_model* m) {
   if ((m->enc_edge[0].in_dim != 1 && m->enc_edge[0].in_dim != 2) || m->enc_edge[0].out_dim != 4 ||
       m->enc_edge[1].in_dim != 4 || m->enc_edge[1].out_dim != 4)
     return fail(MTMC_E_ARG, "edge encoder must be in(1|2)->4->4");
-  const int hn = (m->reattach_nodes ? 2 : 1) * MTMC_NODE_DIM, he = (m->reattach_edges ? 2 : 1) * MTMC_EDGE_DIM;
+  const int hn = node_in_width(m), he = (m->reattach_edges ? 2 : 1) * MTMC_EDGE_DIM;
   if (m->upd_edge.in_dim != 2 * hn + he || m->upd_edge.out_dim != 4) return fail(MTMC_E_ARG, "edge update layer must be [4, %d]", 2 * hn + he);
   if (m->upd_node.in_dim != hn + 4 || m->upd_node.out_dim != MTMC_NODE_DIM) return fail(MTMC_E_ARG, "node update layer must be [32, %d]", hn + 4);
   if (m->cls.in_dim != 4 || m->cls.out_dim < 1 || m->cls.out_dim > MTMC_MAX_CLASSES) return fail(MTMC_E_ARG, "classifier must be [C<=4, 4]");
@@ -154,24 +161,20 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
   lo->slab = take(slab);
   // Layer 0 of a many-row graph runs on operands split ONCE into fp16 pairs (gemm_presplit.hip): planes of x [2][N][K]
   // and of W0 [2][out][K] plus one power-of-two scale per row.  An x-sized region; eval mode only.
-  lo->presplit0 = !training && mtmc::presplit_layer0(N, m->enc_node[0].in_dim, m->enc_node[0].out_dim);
   lo->few = few_shape(m, N);                  // (the call also needs a weight-plane cache: make_plan; training forwards too)
-  if (lo->presplit0 || lo->few) {
-    const size_t K0 = m->enc_node[0].in_dim, O0 = m->enc_node[0].out_dim;
-    lo->xh = take((size_t)2 * N * K0 * sizeof(uint16_t));
+  for (int l = 0; l < m->n_enc_layers; ++l) {
+    const int K = m->enc_node[l].in_dim, O = m->enc_node[l].out_dim;
+    lo->w_ws[l] = !training && (l == 0 ? mtmc::presplit_layer0(N, K, O) : mtmc::staged_layer(N, K, O));
+  }
+  if (lo->w_ws[0] || lo->few) {
+    lo->xh = take((size_t)2 * N * m->enc_node[0].in_dim * sizeof(uint16_t));
     lo->inv_a = take((size_t)N * sizeof(float));
-    if (lo->presplit0) {                       // (without a weight-plane cache the planes of W0 are made per call, here)
-      lo->wh = take((size_t)2 * O0 * K0 * sizeof(uint16_t));
-      lo->inv_w = take(O0 * sizeof(float));
-    }
   }
-  for (int l = 1; l < m->n_enc_layers; ++l) {
-    lo->staged[l] = !training && mtmc::staged_layer(N, m->enc_node[l].in_dim, m->enc_node[l].out_dim);
-    if (lo->staged[l]) {
-      lo->wh_l[l] = take((size_t)2 * m->enc_node[l].out_dim * m->enc_node[l].in_dim * sizeof(uint16_t));
-      lo->inv_w_l[l] = take((size_t)m->enc_node[l].out_dim * sizeof(float));
+  for (int l = 0; l < m->n_enc_layers; ++l)    // (without a weight-plane cache the layer's weight planes are made per call, here)
+    if (lo->w_ws[l]) {
+      lo->wh[l] = take((size_t)2 * m->enc_node[l].out_dim * m->enc_node[l].in_dim * sizeof(uint16_t));
+      lo->inv_w[l] = take((size_t)m->enc_node[l].out_dim * sizeof(float));
     }
-  }
   if (training) {
     for (int r = 0; r < L; ++r) {
       lo->z_tr.push_back(take((size_t)E * 4 * sizeof(float)));
@@ -190,9 +193,9 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
     lo->bwd_zero = off;
     lo->bst = take((size_t)(2 * L + 1) * mtmc::kStatRep * kBwdStride * sizeof(double));   // per round: node, edge; + encoder
     lo->bst_n = take(bn_stats * sizeof(double));
-    lo->gacc = take((size_t)16 * 256 * sizeof(float));                   // [kGradRep][kGaccN] small-gradient replicas
+    lo->gacc = take((size_t)mtmc::kGradRep * mtmc::kGaccN * sizeof(float));   // small-gradient replicas
     lo->amax_bwd = take((size_t)2 * MTMC_MAX_ENC_LAYERS * mtmc::kAmaxRep * sizeof(uint32_t));   // |dY_l|max, |a_{l-1}|max
-    lo->g_P = take((size_t)(L > 0 ? L : 1) * 16 * N * 8 * sizeof(float)); // per round: [kGradRep = 16][N][8]
+    lo->g_P = take((size_t)(L > 0 ? L : 1) * mtmc::kGradRep * N * 8 * sizeof(float));   // per round: [kGradRep][N][8]
     lo->g_Q = take((size_t)(L > 0 ? L : 1) * N * 32 * sizeof(float));     // per round
     lo->zeros = take(maxd * sizeof(float));
     lo->g_h0 = take((size_t)N * 32 * sizeof(float));
@@ -268,13 +271,13 @@ inline bool in_loop_kernel(int k) { return k == MTMC_GEMM_GENERIC || k == MTMC_G
 
 // From the call's sizes, ranges, flags and mode, the layout and the knobs.  No pointer of the call is read (weight_cache is
 // only tested for NULL), so the host-only query builds the same plan.  The layout says what the WHOLE graph qualifies for
-// (presplit0, few, staged[l]); a layer takes a kernel when this call's rows qualify too.
+// (few, w_ws[l]); a layer takes a kernel when this call's rows qualify too.
 inline void make_plan(const mtmc_mpn_model* m, const mtmc_mpn_call* c, const Layout& lo, const CacheLayout& cl, CallPlan* p) {
   *p = CallPlan();
   const int64_t N = c->n_nodes, E = c->n_edges, rows = c->node_hi - c->node_lo;
   const mtmc_layer& L0 = m->enc_node[0];
   p->rows = rows;
-  const bool pre0 = lo.presplit0 && mtmc::presplit_layer0(rows, L0.in_dim, L0.out_dim);
+  const bool pre0 = lo.w_ws[0] && mtmc::presplit_layer0(rows, L0.in_dim, L0.out_dim);
   bool few = lo.few && c->weight_cache != nullptr && few_shape(m, rows);     // (training forwards too)
   for (int l = 0; l < m->n_enc_layers; ++l) few = few && cl.has[l];
   for (int l = 0; l < m->n_enc_layers; ++l) {
@@ -282,7 +285,7 @@ inline void make_plan(const mtmc_mpn_model* m, const mtmc_mpn_call* c, const Lay
     int k, sk = 1;
     if (few) k = l == 0 ? MTMC_GEMM_FEW_L0 : MTMC_GEMM_FEW_WAVE;
     else if (l == 0 && pre0) k = MTMC_GEMM_PRESPLIT_256;
-    else if (l >= 1 && lo.staged[l] && mtmc::staged_layer(rows, Ll.in_dim, Ll.out_dim)) k = MTMC_GEMM_STAGED_128;
+    else if (l >= 1 && lo.w_ws[l] && mtmc::staged_layer(rows, Ll.in_dim, Ll.out_dim)) k = MTMC_GEMM_STAGED_128;
     else if (l >= 1 && !lo.training && mtmc::rows_layer(N, Ll.in_dim, Ll.out_dim) && mtmc::rows_layer(rows, Ll.in_dim, Ll.out_dim))
       k = MTMC_GEMM_ROWS_16;        // narrow last layers of many-row graphs
     else {                          // the slab was sized for N rows; a shard with fewer rows may plan a larger split: then none
@@ -438,7 +441,7 @@ inline float* round_e(const Ctx& x, int r) { return x.at<float>(x.lo.training ? 
 
 inline mtmc::RoundParams round_params(const Ctx& x, int r) {
   const mtmc_mpn_model* m = x.m;
-  const int hn = (m->reattach_nodes ? 2 : 1) * MTMC_NODE_DIM;
+  const int hn = node_in_width(m);
   mtmc::RoundParams p;
   p.row32 = x.at<int>(x.lo.row32); p.col32 = x.at<int>(x.lo.col32);
   p.attr = x.c->edge_attr;
@@ -457,9 +460,7 @@ inline mtmc::RoundParams round_params(const Ctx& x, int r) {
   p.lazy_e = x.plan.lazy_edges ? 1 : 0;
   p.prev_stats = r > 0 ? p.stats - mtmc::kRoundBlock : nullptr;
   p.h_acc = agg_target(x, r);
-  const int step = r + 1;
-  int first_cls = m->num_enc_steps - m->num_class_steps + 1;   // mpn.py:277; Cs > L classifies every round
-  if (first_cls < 1) first_cls = 1;
+  const int step = r + 1, first_cls = first_cls_step(m);
   p.logits = step >= first_cls ? x.c->logits + (size_t)(step - first_cls) * x.c->n_edges * m->cls.out_dim : nullptr;
   p.n_edges = x.c->n_edges; p.e_total = (double)x.c->n_edges_total;
   p.first_round = r == 0; p.reattach_edges = m->reattach_edges; p.agg = m->agg;
@@ -477,11 +478,11 @@ inline mtmc::RoundParams round_params(const Ctx& x, int r) {
 // where layer l's weight planes / inverse row scales are: the cache when the call has one, else the workspace (made per call)
 inline _Float16* w_planes(const Ctx& x, int l) {
   if (x.plan.w_cached[l]) return x.wc_at<_Float16>(x.cl.planes[l]);
-  return x.at<_Float16>(l == 0 ? x.lo.wh : x.lo.wh_l[l]);
+  return x.at<_Float16>(x.lo.wh[l]);
 }
 inline float* w_inv(const Ctx& x, int l) {
   if (x.plan.w_cached[l]) return x.wc_at<float>(x.cl.inv[l]);
-  return x.at<float>(l == 0 ? x.lo.inv_w : x.lo.inv_w_l[l]);
+  return x.at<float>(x.lo.inv_w[l]);
 }
 
 enum { kPhMemset = -1, kPhPrep = -2 };   // the two halves of MTMC_PH_BEGIN, for the forked forward
@@ -500,8 +501,35 @@ inline const int* scale_deg(const Ctx& x) {   // the degree mean aggregation div
   return x.at<int>((x.c->flags & MTMC_F_GLOBAL_DEG) ? x.lo.pub.deg_global_off : x.lo.pub.deg_off);
 }
 
-// MTMC_PH_EDGE_ENC's work as passenger workgroups of an encoder layer's launch (GemmParams / FewWaveParams::pass_*)
-template <typename P> inline void ride_enc2(const Ctx& x, P* q) {
+// The |.|max words (u32[kAmaxRep] each) of x, of layer l's raw output Y_l and of W_l (Layout::amax, amax_w)
+inline unsigned* amax_x(const Ctx& x) { return x.at<unsigned>(x.lo.amax); }
+inline unsigned* amax_y(const Ctx& x, int l) { return amax_x(x) + (1 + MTMC_MAX_ENC_LAYERS + l) * mtmc::kAmaxRep; }
+inline unsigned* amax_w(const Ctx& x, int l) { return x.at<unsigned>(x.lo.amax_w) + l * mtmc::kAmaxRep; }
+inline unsigned* amax_in(const Ctx& x, int l) { return l == 0 ? amax_x(x) : amax_y(x, l - 1); }   // of layer l's input
+
+// The parts of node-encoder layer l's parameter block (kernels.h), each filled from the call in one place.
+// Input: x for layer 0, else the previous layer's raw Y with its statistics, BatchNorm and Dropout
+inline void fill_in(const Ctx& x, int l, mtmc::ActIn* q) {
+  if (l == 0) {
+    q->A = x.c->x; q->lda = x.c->x_row_stride;
+  } else {
+    const mtmc_layer& Pv = x.m->enc_node[l - 1];
+    q->A = x.at<float>(x.lo.Y[l - 1]); q->lda = Pv.out_dim;
+    q->stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]); q->gamma_in = Pv.gamma; q->beta_in = Pv.beta;
+  }
+  q->count = (double)x.c->n_nodes;
+  q->drop_in = make_drop(x, x.m->dropout_enc); q->drop_stream = mtmc::kDropEncNode + l - 1;
+}
+inline void fill_out(const Ctx& x, int l, mtmc::LayerOut* q) {
+  const mtmc_layer& Lr = x.m->enc_node[l];
+  q->bias = Lr.bias; q->Y = x.at<float>(x.lo.Y[l]); q->ldy = Lr.out_dim;
+  q->stats_out = x.at<double>(x.lo.stat_enc_layer[l]); q->amax_y = amax_y(x, l);
+  q->M = x.plan.rows; q->K = Lr.in_dim; q->Nout = Lr.out_dim;
+}
+inline void fill_w(const Ctx& x, int l, mtmc::PlanesW* q) { q->Wh = w_planes(x, l); q->inv_w = w_inv(x, l); }
+inline void fill_x(const Ctx& x, mtmc::PlanesA* q) { q->Ah = x.at<_Float16>(x.lo.xh); q->inv_a = x.at<float>(x.lo.inv_a); }
+// MTMC_PH_EDGE_ENC's work as passenger workgroups of the last encoder layer's launch
+inline void ride_enc2(const Ctx& x, mtmc::Enc2Ride* q) {
   const int64_t blocks = (x.c->n_edges + 255) / 256;
   q->pass_blocks = (int)(blocks > 2048 ? 2048 : blocks);
   q->pass_enc = enc_params(x); q->pass_attr = x.c->edge_attr; q->pass_edges = x.c->n_edges;
@@ -511,30 +539,16 @@ template <typename P> inline void ride_enc2(const Ctx& x, P* q) {
 // The node-encoder layer launches of MTMC_PH_NODE_ENC, one per form of CallPlan::enc_kernel.
 // Few-row graphs (gemm_few.hip): one launch per layer, never split along K.
 inline int launch_enc_few(const Ctx& x, int l) {
-  const mtmc_mpn_model* m = x.m;
-  const mtmc_layer& Lr = m->enc_node[l];
-  hipStream_t s = x.stream;
   int rc;
   if (l == 0) {
     mtmc::FewL0Params q;
-    q.Ah = x.at<_Float16>(x.lo.xh); q.inv_a = x.at<float>(x.lo.inv_a);
-    q.Wh = w_planes(x, 0); q.inv_w = w_inv(x, 0);
-    q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[0]); q.ldy = Lr.out_dim;
-    q.stats_out = x.at<double>(x.lo.stat_enc_layer[0]);
-    q.M = x.plan.rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
-    rc = mtmc::launch_few_l0(q, s);
+    fill_x(x, &q); fill_w(x, 0, &q); fill_out(x, 0, &q);
+    rc = mtmc::launch_few_l0(q, x.stream);
   } else {
     mtmc::FewWaveParams q;
-    q.A = x.at<float>(x.lo.Y[l - 1]); q.lda = m->enc_node[l - 1].out_dim;
-    q.stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]);
-    q.gamma_in = m->enc_node[l - 1].gamma; q.beta_in = m->enc_node[l - 1].beta; q.count = (double)x.c->n_nodes;
-    q.Wh = w_planes(x, l); q.inv_w = w_inv(x, l);
-    q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[l]); q.ldy = Lr.out_dim;
-    q.stats_out = x.at<double>(x.lo.stat_enc_layer[l]);
-    q.M = x.plan.rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
-    q.drop_in = make_drop(x, m->dropout_enc); q.drop_stream = mtmc::kDropEncNode + l - 1;
-    if (x.enc2_rides && l == m->n_enc_layers - 1) ride_enc2(x, &q);
-    rc = mtmc::launch_few_wave(q, s);
+    fill_in(x, l, &q); fill_w(x, l, &q); fill_out(x, l, &q);
+    if (x.enc2_rides && l == x.m->n_enc_layers - 1) ride_enc2(x, &q);
+    rc = mtmc::launch_few_wave(q, x.stream);
   }
   if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: few-row kernel refused the shape or the launch", l);
   return MTMC_OK;
@@ -547,12 +561,7 @@ inline int launch_enc_presplit0(const Ctx& x) {
   const int64_t rows = x.plan.rows;
   hipStream_t s = x.stream;
   mtmc::SplitGemmParams q;
-  q.Ah = x.at<_Float16>(x.lo.xh); q.inv_a = x.at<float>(x.lo.inv_a);
-  q.Wh = w_planes(x, 0); q.inv_w = w_inv(x, 0);
-  q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[0]); q.ldy = Lr.out_dim;
-  q.stats_out = x.at<double>(x.lo.stat_enc_layer[0]);
-  q.amax_y = x.at<unsigned>(x.lo.amax) + (1 + MTMC_MAX_ENC_LAYERS) * mtmc::kAmaxRep;
-  q.M = rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
+  fill_x(x, &q); fill_w(x, 0, &q); fill_out(x, 0, &q);
   PanelTiming& pt = panel_timing();
   if (x.pipe) {
     // Row panels: the side stream splits panel after panel (HBM-bound), the main stream multiplies panel i as soon as
@@ -594,19 +603,9 @@ inline int launch_enc_presplit0(const Ctx& x) {
 
 // Many-row graphs, layers >= 1 on the role-split kernel (gemm_staged.hip).
 inline int launch_enc_staged(const Ctx& x, int l) {
-  const mtmc_mpn_model* m = x.m;
-  const mtmc_layer& Lr = m->enc_node[l];
-  unsigned* amax = x.at<unsigned>(x.lo.amax);
   mtmc::StagedGemmParams q;
-  q.A = x.at<float>(x.lo.Y[l - 1]); q.lda = m->enc_node[l - 1].out_dim;
-  q.stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]);
-  q.gamma_in = m->enc_node[l - 1].gamma; q.beta_in = m->enc_node[l - 1].beta; q.count = (double)x.c->n_nodes;
-  q.amax_a = amax + (1 + MTMC_MAX_ENC_LAYERS + (l - 1)) * mtmc::kAmaxRep;
-  q.Wh = w_planes(x, l); q.inv_w = w_inv(x, l);
-  q.bias = Lr.bias; q.Y = x.at<float>(x.lo.Y[l]); q.ldy = Lr.out_dim;
-  q.stats_out = x.at<double>(x.lo.stat_enc_layer[l]);
-  q.amax_y = amax + (1 + MTMC_MAX_ENC_LAYERS + l) * mtmc::kAmaxRep;
-  q.M = x.plan.rows; q.K = Lr.in_dim; q.Nout = Lr.out_dim;
+  fill_in(x, l, &q); fill_w(x, l, &q); fill_out(x, l, &q);
+  q.amax_a = amax_in(x, l);
   const int rc = mtmc::launch_gemm_staged(q, x.stream);
   if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: role-split GEMM refused the shape or the launch", l);
   return MTMC_OK;
@@ -615,33 +614,15 @@ inline int launch_enc_staged(const Ctx& x, int l) {
 // The in-loop operand split (gemm_bn.hip; MTMC_PH_NODE_COMBINE adds up the slab's K slices), or the row-streaming kernel
 // (gemm_rows.hip) of the narrow last layers of many-row graphs.
 inline int launch_enc_gemm(const Ctx& x, int l, int phase) {
-  const mtmc_mpn_model* m = x.m;
-  const mtmc_mpn_call* c = x.c;
-  const mtmc_layer& Lr = m->enc_node[l];
   mtmc::GemmParams g;
-  if (l == 0) {
-    g.A = c->x; g.lda = c->x_row_stride; g.stats_in = nullptr; g.gamma_in = nullptr; g.beta_in = nullptr;
-  } else {
-    g.A = x.at<float>(x.lo.Y[l - 1]); g.lda = m->enc_node[l - 1].out_dim;
-    g.stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]);
-    g.gamma_in = m->enc_node[l - 1].gamma; g.beta_in = m->enc_node[l - 1].beta;
-  }
-  g.W = Lr.weight; g.bias = Lr.bias; g.Y = x.at<float>(x.lo.Y[l]); g.ldy = Lr.out_dim;
-  g.count = (double)c->n_nodes; g.stats_out = x.at<double>(x.lo.stat_enc_layer[l]);
-  g.M = x.plan.rows; g.K = Lr.in_dim; g.Nout = Lr.out_dim;
-  g.drop_in = make_drop(x, m->dropout_enc); g.drop_stream = mtmc::kDropEncNode + l - 1;
-  unsigned* amax = x.at<unsigned>(x.lo.amax);
-  g.amax_a = l == 0 ? amax : amax + (1 + MTMC_MAX_ENC_LAYERS + (l - 1)) * mtmc::kAmaxRep;
-  g.amax_w = x.at<unsigned>(x.lo.amax_w) + l * mtmc::kAmaxRep;
-  g.amax_y = amax + (1 + MTMC_MAX_ENC_LAYERS + l) * mtmc::kAmaxRep;
-  if (x.enc2_rides && phase == MTMC_PH_NODE_ENC && l == m->n_enc_layers - 1) ride_enc2(x, &g);
-  g.split_k = 1;
+  fill_in(x, l, &g); fill_out(x, l, &g);
+  g.W = x.m->enc_node[l].weight; g.amax_a = amax_in(x, l); g.amax_w = amax_w(x, l);
+  if (x.enc2_rides && phase == MTMC_PH_NODE_ENC && l == x.m->n_enc_layers - 1) ride_enc2(x, &g);
   if (x.plan.enc_kernel[l] == MTMC_GEMM_ROWS_16) {
-    g.slab = nullptr;
     if (mtmc::launch_gemm_rows(g, x.stream) != 0) return fail(MTMC_E_ARG, "encoder layer %d: row-streaming GEMM refused the shape", l);
     return MTMC_OK;
   }
-  g.slab = x.plan.enc_split_k[l] > 1 ? x.at<float>(x.lo.slab) : nullptr;
+  if (x.plan.enc_split_k[l] > 1) g.slab = x.at<float>(x.lo.slab);
   if (mtmc::launch_gemm_bn(g, x.stream, phase == MTMC_PH_NODE_ENC ? 1 : 2) != MTMC_OK)
     return fail(MTMC_E_ARG, "encoder layer %d: unsupported GEMM shape", l);
   return MTMC_OK;
@@ -669,24 +650,22 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
         mtmc::PrepParams p;
         fill_prep_edge(x, &p);
         // passenger jobs: operand |.|max values / operand splits of the node encoder (this rank's rows of x; the weights)
-        unsigned* amax = x.at<unsigned>(x.lo.amax);
         p.n_jobs = 0;
         // (training forwards: the jobs also publish the tensors' |.|max -- the backward's GEMMs scale by |x|max and |W_l|max)
-        unsigned* amax_w0 = x.at<unsigned>(x.lo.amax_w);
         if (rows > 0) {
           if (pl.enc_kernel[0] == MTMC_GEMM_FEW_L0)     // the planes of x, 8 rows per passenger workgroup (no |x|max: one scale per row)
-            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, c->training ? amax : nullptr, 0, 0, mtmc::kJobSplit,
+            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, c->training ? amax_x(x) : nullptr, 0, 0, mtmc::kJobSplit,
                                   x.at<_Float16>(x.lo.xh), x.at<float>(x.lo.inv_a), nullptr};
           else if (pl.enc_kernel[0] != MTMC_GEMM_PRESPLIT_256)
-            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, amax, 0, 0, mtmc::kJobAmax, nullptr, nullptr, nullptr};
+            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, amax_x(x), 0, 0, mtmc::kJobAmax, nullptr, nullptr, nullptr};
           for (int l = 0; l < m->n_enc_layers; ++l) {
             const mtmc_layer& Ll = m->enc_node[l];
             if (pl.w_cached[l])         // layer l's planes in the cache: verify every 8-row chunk, split the ones that changed
-              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, c->training ? amax_w0 + l * mtmc::kAmaxRep : nullptr, 0, 0,
+              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, c->training ? amax_w(x, l) : nullptr, 0, 0,
                                     mtmc::kJobSplit, x.wc_at<_Float16>(x.cl.planes[l]), x.wc_at<float>(x.cl.inv[l]),
                                     x.wc_at<unsigned long long>(x.cl.fp[l])};
             else if (in_loop_kernel(pl.enc_kernel[l]))   // |W_l|max (row-streaming: in the kernel; planes without a cache: below)
-              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, amax_w0 + l * mtmc::kAmaxRep, 0, 0, mtmc::kJobAmax,
+              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, amax_w(x, l), 0, 0, mtmc::kJobAmax,
                                     nullptr, nullptr, nullptr};
           }
         }
@@ -695,18 +674,16 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
           const mtmc::RoundParams rp = round_params(x, 0);
           mtmc::launch_colblock_index(rp, x.at<int>(x.lo.col_sub), rp.col_blocks, rp.cb_row_lo, rp.cb_row_hi, s);
         }
-        if (pl.enc_kernel[0] == MTMC_GEMM_PRESPLIT_256) {     // instead of the |.|max of x and W0: their fp16 planes and row scales
-          if (!x.pipe)  // (pipelined layer 0: the x planes are made panel by panel in MTMC_PH_NODE_ENC 0)
-            mtmc::launch_split_rows(c->x, c->x_row_stride, rows, m->enc_node[0].in_dim, x.at<void>(x.lo.xh),
-                                    x.at<float>(x.lo.inv_a), s);
-          if (!pl.w_cached[0])
-            mtmc::launch_split_rows(m->enc_node[0].weight, m->enc_node[0].in_dim, m->enc_node[0].out_dim,
-                                    m->enc_node[0].in_dim, x.at<void>(x.lo.wh), x.at<float>(x.lo.inv_w), s);
+        // instead of the |.|max of x and W0: their fp16 planes and row scales
+        // (pipelined layer 0: the x planes are made panel by panel in MTMC_PH_NODE_ENC 0)
+        if (pl.enc_kernel[0] == MTMC_GEMM_PRESPLIT_256 && !x.pipe)
+          mtmc::launch_split_rows(c->x, c->x_row_stride, rows, m->enc_node[0].in_dim, x.at<void>(x.lo.xh),
+                                  x.at<float>(x.lo.inv_a), s);
+        for (int l = 0; l < m->n_enc_layers; ++l) {     // the weight planes of the layers whose kernels want them, unless cached
+          const mtmc_layer& Ll = m->enc_node[l];
+          if ((pl.enc_kernel[l] == MTMC_GEMM_PRESPLIT_256 || pl.enc_kernel[l] == MTMC_GEMM_STAGED_128) && !pl.w_cached[l])
+            mtmc::launch_split_rows(Ll.weight, Ll.in_dim, Ll.out_dim, Ll.in_dim, w_planes(x, l), w_inv(x, l), s);
         }
-        for (int l = 1; l < m->n_enc_layers; ++l)
-          if (pl.enc_kernel[l] == MTMC_GEMM_STAGED_128 && !pl.w_cached[l])
-            mtmc::launch_split_rows(m->enc_node[l].weight, m->enc_node[l].in_dim, m->enc_node[l].out_dim,
-                                    m->enc_node[l].in_dim, x.at<void>(x.lo.wh_l[l]), x.at<float>(x.lo.inv_w_l[l]), s);
       }
       break;
     }
@@ -752,7 +729,7 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
       p.deg = (m->agg == MTMC_AGG_MEAN && arg > 0) ? scale_deg(x) : nullptr;
       p.ue_w = m->upd_edge.weight; p.ue_ld = m->upd_edge.in_dim;
       p.un_w = m->upd_node.weight; p.un_ld = m->upd_node.in_dim;
-      p.hn = (m->reattach_nodes ? 2 : 1) * MTMC_NODE_DIM;
+      p.hn = node_in_width(m);
       p.P = round_P(x, arg); p.Q = round_Q(x, arg);
       p.zero_buf = agg_target(x, arg);
       p.n_nodes = c->n_nodes;
@@ -780,7 +757,7 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
       mtmc::NodeStatParams p;
       p.Q = round_Q(x, arg); p.deg = x.at<int>(x.lo.pub.deg_off); p.seg = x.at<double>(x.lo.pub.seg_off);
       p.un_w = m->upd_node.weight; p.un_b = m->upd_node.bias; p.un_ld = m->upd_node.in_dim;
-      p.un_eoff = (m->reattach_nodes ? 2 : 1) * MTMC_NODE_DIM;
+      p.un_eoff = node_in_width(m);
       p.stats = x.at<double>(x.lo.pub.stat_round_off) + (size_t)arg * mtmc::kRoundBlock;
       p.n_nodes = c->n_nodes;
       p.node_begin = proj_lo(c); p.node_end = proj_hi(c);

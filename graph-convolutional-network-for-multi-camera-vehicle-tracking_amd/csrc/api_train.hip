@@ -26,6 +26,18 @@ int check_grads(const mtmc_mpn_model* m, const mtmc_mpn_model* g) {
   return MTMC_OK;
 }
 
+// the gradient tensors are written: `grads` reuses mtmc_mpn_model, whose parameter pointers are const
+float* wr(const float* p) { return const_cast<float*>(p); }
+
+// every layer in struct order and whether it has a BatchNorm: the order of the pieces of the flat gradient buffer
+template <typename Model, typename F>
+void for_each_layer(Model& m, F f) {
+  for (int l = 0; l < m.n_enc_layers; ++l) f(m.enc_node[l], true);
+  f(m.enc_edge[0], true); f(m.enc_edge[1], true);
+  f(m.upd_edge, true); f(m.upd_node, true);
+  f(m.cls, false);
+}
+
 }  // namespace
 
 static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call, const float* const* d_logits_steps,
@@ -38,7 +50,7 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
   const mtmc_mpn_model* m = model;
   const int L = m->num_enc_steps;
   const int64_t N = call->n_nodes, E = call->n_edges;
-  const int hn = (m->reattach_nodes ? 2 : 1) * MTMC_NODE_DIM;
+  const int hn = node_in_width(m);
   hipStream_t s = x.stream;
   const Layout& lo = x.lo;
   double* bst = x.at<double>(lo.bst);
@@ -77,7 +89,7 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
     char* const end = at + grads_flat_bytes;
     bool ok = ((uintptr_t)at & 15) == 0 && (grads_flat_bytes & 15) == 0;
     for (int l = 0; ok && l < m->n_enc_layers; ++l) {
-      char* w = reinterpret_cast<char*>(const_cast<float*>(grads->enc_node[l].weight));
+      char* w = reinterpret_cast<char*>(wr(grads->enc_node[l].weight));
       const size_t wb = (size_t)m->enc_node[l].in_dim * m->enc_node[l].out_dim * sizeof(float);
       ok = w >= at && w + wb <= end && ((uintptr_t)w & 15) == 0 && (wb & 15) == 0;
       if (ok && w > at) { z.r[z.n].p = reinterpret_cast<uint4*>(at); z.r[z.n].n16 = (size_t)(w - at) / 16; ++z.n; }
@@ -98,15 +110,15 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
     for (int l = 0; l < m->n_enc_layers; ++l) {
       const mtmc_layer& g = grads->enc_node[l];
       const size_t o = m->enc_node[l].out_dim;
-      HIP_OK(zero(const_cast<float*>(g.bias), o));
-      HIP_OK(zero(const_cast<float*>(g.gamma), o)); HIP_OK(zero(const_cast<float*>(g.beta), o));
+      HIP_OK(zero(wr(g.bias), o));
+      HIP_OK(zero(wr(g.gamma), o)); HIP_OK(zero(wr(g.beta), o));
     }
     const mtmc_layer* gs[] = {&grads->enc_edge[0], &grads->enc_edge[1], &grads->upd_edge, &grads->upd_node, &grads->cls};
     const mtmc_layer* ms[] = {&m->enc_edge[0], &m->enc_edge[1], &m->upd_edge, &m->upd_node, &m->cls};
     for (int i = 0; i < 5; ++i) {
       const size_t o = ms[i]->out_dim, in = ms[i]->in_dim;
-      HIP_OK(zero(const_cast<float*>(gs[i]->weight), o * in)); HIP_OK(zero(const_cast<float*>(gs[i]->bias), o));
-      if (i < 4) { HIP_OK(zero(const_cast<float*>(gs[i]->gamma), o)); HIP_OK(zero(const_cast<float*>(gs[i]->beta), o)); }
+      HIP_OK(zero(wr(gs[i]->weight), o * in)); HIP_OK(zero(wr(gs[i]->bias), o));
+      if (i < 4) { HIP_OK(zero(wr(gs[i]->gamma), o)); HIP_OK(zero(wr(gs[i]->beta), o)); }
     }
   }
   // the workspace side: statistics blocks, per-round dP/dQ, dh0, de0, the first de / dh buffers -- one range
@@ -116,11 +128,10 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
   if (d_h) HIP_OK(hipMemcpyAsync(L > 0 ? g_h[cur] : g_h0, d_h, (size_t)N * 32 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (L == 0 && d_logits_steps && d_logits_steps[0] && E > 0)       // no rounds: classifier on the encoded edges
     mtmc::launch_bwd_classify_e0(enc_params(x), call->edge_attr, E, (double)E, m->cls.weight, m->cls.out_dim,
-                                 d_logits_steps[0], g_e0, const_cast<float*>(grads->cls.weight),
-                                 const_cast<float*>(grads->cls.bias), s);
+                                 d_logits_steps[0], g_e0, wr(grads->cls.weight),
+                                 wr(grads->cls.bias), s);
 
-  int first_cls = L - m->num_class_steps + 1;
-  if (first_cls < 1) first_cls = 1;
+  const int first_cls = first_cls_step(m);
 
   for (int r = L - 1; r >= 0; --r) {
     // P, Q of this round are on the tape (Layout::P_tr / Q_tr); what bwd_node_proj needs of the forward's node_proj:
@@ -137,11 +148,11 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
     bp.g_de2 = x.at<float>(lo.g_de2);
     bp.g_Q = x.at<float>(lo.g_Q) + (size_t)r * N * 32; bp.g_P = x.at<float>(lo.g_P) + (size_t)r * mtmc::kGradRep * N * 8;
     bp.g_e = g_e[cur_e]; bp.g_e_prev = g_e[cur_e ^ 1]; bp.g_e0 = g_e0; bp.bst = bst + (size_t)(2 * r) * bst_block;
-    bp.gr_un_w = const_cast<float*>(grads->upd_node.weight); bp.gr_un_b = const_cast<float*>(grads->upd_node.bias);
-    bp.gr_un_g = const_cast<float*>(grads->upd_node.gamma); bp.gr_un_bt = const_cast<float*>(grads->upd_node.beta);
-    bp.gr_ue_w = const_cast<float*>(grads->upd_edge.weight); bp.gr_ue_b = const_cast<float*>(grads->upd_edge.bias);
-    bp.gr_ue_g = const_cast<float*>(grads->upd_edge.gamma); bp.gr_ue_bt = const_cast<float*>(grads->upd_edge.beta);
-    bp.gr_cls_w = const_cast<float*>(grads->cls.weight); bp.gr_cls_b = const_cast<float*>(grads->cls.bias);
+    bp.gr_un_w = wr(grads->upd_node.weight); bp.gr_un_b = wr(grads->upd_node.bias);
+    bp.gr_un_g = wr(grads->upd_node.gamma); bp.gr_un_bt = wr(grads->upd_node.beta);
+    bp.gr_ue_w = wr(grads->upd_edge.weight); bp.gr_ue_b = wr(grads->upd_edge.bias);
+    bp.gr_ue_g = wr(grads->upd_edge.gamma); bp.gr_ue_bt = wr(grads->upd_edge.beta);
+    bp.gr_cls_w = wr(grads->cls.weight); bp.gr_cls_b = wr(grads->cls.bias);
     bp.gacc = x.at<float>(lo.gacc);
 
     if (m->agg == MTMC_AGG_MAX) {
@@ -171,10 +182,10 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
     ep.enc = enc_params(x); ep.attr = call->edge_attr; ep.n_edges = E; ep.e_total = (double)E; ep.g_e0 = g_e0;
     ep.bst = bst + (size_t)(2 * L) * bst_block; ep.d_attr = d_edge_attr;
     ep.gacc = x.at<float>(lo.gacc);
-    ep.gr_w1 = const_cast<float*>(grads->enc_edge[0].weight); ep.gr_b1 = const_cast<float*>(grads->enc_edge[0].bias);
-    ep.gr_g1 = const_cast<float*>(grads->enc_edge[0].gamma); ep.gr_bt1 = const_cast<float*>(grads->enc_edge[0].beta);
-    ep.gr_w2 = const_cast<float*>(grads->enc_edge[1].weight); ep.gr_b2 = const_cast<float*>(grads->enc_edge[1].bias);
-    ep.gr_g2 = const_cast<float*>(grads->enc_edge[1].gamma); ep.gr_bt2 = const_cast<float*>(grads->enc_edge[1].beta);
+    ep.gr_w1 = wr(grads->enc_edge[0].weight); ep.gr_b1 = wr(grads->enc_edge[0].bias);
+    ep.gr_g1 = wr(grads->enc_edge[0].gamma); ep.gr_bt1 = wr(grads->enc_edge[0].beta);
+    ep.gr_w2 = wr(grads->enc_edge[1].weight); ep.gr_b2 = wr(grads->enc_edge[1].bias);
+    ep.gr_g2 = wr(grads->enc_edge[1].gamma); ep.gr_bt2 = wr(grads->enc_edge[1].beta);
     for (int pass = 0; pass < 3; ++pass) mtmc::launch_bwd_edge_enc(ep, pass, s);
   }
 
@@ -185,7 +196,6 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
     float* tA = x.at<float>(lo.tA);
     float* tB = x.at<float>(lo.tB);
     float* zeros = x.at<float>(lo.zeros);
-    const mtmc::Drop nodrop = {0, 0, 1.f, 0};
     for (int l = m->n_enc_layers - 1; l >= 0; --l) {
       const mtmc_layer& Lr = m->enc_node[l];
       const int d = Lr.out_dim, in = Lr.in_dim;
@@ -198,11 +208,10 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
       bb.Y = x.at<float>(lo.Y[l]); bb.dA = dY; bb.rows = N; bb.dim = d;
       bb.stats_fwd = x.at<double>(lo.stat_enc_layer[l]); bb.stats_bwd = sb; bb.count = (double)N;
       bb.gamma = Lr.gamma; bb.beta = Lr.beta; bb.drop = make_drop(x, m->dropout_enc); bb.drop_stream = mtmc::kDropEncNode + l;
-      bb.gr_gamma = const_cast<float*>(grads->enc_node[l].gamma); bb.gr_beta = const_cast<float*>(grads->enc_node[l].beta);
-      bb.gr_bias = const_cast<float*>(grads->enc_node[l].bias);
+      bb.gr_gamma = wr(grads->enc_node[l].gamma); bb.gr_beta = wr(grads->enc_node[l].beta);
+      bb.gr_bias = wr(grads->enc_node[l].bias);
       // |.|max of the three GEMM operands of this layer: dY_l (written by bn_bwd's apply pass), a_{l-1} (x: the forward's
       // value; else from the recomputation below) and W_l (the forward's) -> the fp16 three-product kernel applies
-      unsigned* amax_fwd = x.at<unsigned>(lo.amax);
       unsigned* amax_dy = x.at<unsigned>(lo.amax_bwd) + (size_t)l * mtmc::kAmaxRep;
       unsigned* amax_act = x.at<unsigned>(lo.amax_bwd) + (size_t)(MTMC_MAX_ENC_LAYERS + l) * mtmc::kAmaxRep;
       bb.amax_out = amax_dy;
@@ -227,33 +236,28 @@ static int backward_impl(const mtmc_mpn_model* model, const mtmc_mpn_call* call,
                                   amax_act, tB, npad);
       }
       // dW_l [d][in] = dY^T . a  -> NT GEMM on the transposes (reduction over the node rows, padded to 32)
-      mtmc::GemmParams g;
-      g.A = tA; g.lda = npad; g.W = aT; g.bias = zeros; g.Y = const_cast<float*>(grads->enc_node[l].weight); g.ldy = in;
-      g.stats_in = nullptr; g.gamma_in = nullptr; g.beta_in = nullptr; g.count = 1; g.stats_out = nullptr;
-      g.M = d; g.K = (int)npad; g.Nout = in; g.drop_in = nodrop; g.drop_stream = 0; g.slab = nullptr; g.split_k = 1;
-      g.amax_a = amax_dy; g.amax_w = l > 0 ? amax_act : amax_fwd; g.amax_y = nullptr;
+      mtmc::GemmParams g = mtmc::plain_gemm(tA, npad, aT, zeros, wr(grads->enc_node[l].weight), in, d, (int)npad, in, amax_dy,
+                                            l > 0 ? amax_act : amax_x(x));
       if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "backward: weight-gradient GEMM shape");
       // dA_{l-1} [N][in] = dY . W_l  -> NT GEMM against W^T
       if (l > 0 || d_x) {
-        g.A = dY; g.lda = d; g.W = tWl[l]; g.Y = l > 0 ? gB : d_x; g.ldy = in; g.M = N; g.K = d; g.Nout = in;    // W_l^T [in][d]
-        g.amax_w = x.at<unsigned>(lo.amax_w) + (size_t)l * mtmc::kAmaxRep;
+        g = mtmc::plain_gemm(dY, d, tWl[l], zeros, l > 0 ? gB : d_x, in, N, d, in, amax_dy, amax_w(x, l));    // W_l^T [in][d]
         if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "backward: input-gradient GEMM shape");
         std::swap(gA, gB);
       }
     }
   }
   {  // the replicated small-gradient sums of the edge kernels -> the caller's tensors
-    static_assert(mtmc::kGradRep == 16 && mtmc::kGaccN == 256, "Layout::gacc is sized for 16 x 256 floats");
     mtmc::GradFoldParams fp;
     fp.gacc = x.at<float>(lo.gacc);
-    fp.gr_un_w = const_cast<float*>(grads->upd_node.weight); fp.gr_un_b = const_cast<float*>(grads->upd_node.bias);
+    fp.gr_un_w = wr(grads->upd_node.weight); fp.gr_un_b = wr(grads->upd_node.bias);
     fp.un_ld = m->upd_node.in_dim; fp.un_eoff = hn;
-    fp.gr_ue_w = const_cast<float*>(grads->upd_edge.weight); fp.gr_ue_b = const_cast<float*>(grads->upd_edge.bias);
+    fp.gr_ue_w = wr(grads->upd_edge.weight); fp.gr_ue_b = wr(grads->upd_edge.bias);
     fp.ue_ld = m->upd_edge.in_dim; fp.ue_eoff = 2 * hn; fp.nin = m->reattach_edges ? 8 : 4;
-    fp.gr_cls_w = const_cast<float*>(grads->cls.weight); fp.gr_cls_b = const_cast<float*>(grads->cls.bias);
+    fp.gr_cls_w = wr(grads->cls.weight); fp.gr_cls_b = wr(grads->cls.bias);
     fp.n_classes = m->cls.out_dim;
-    fp.gr_w1 = const_cast<float*>(grads->enc_edge[0].weight); fp.gr_b1 = const_cast<float*>(grads->enc_edge[0].bias);
-    fp.gr_w2 = const_cast<float*>(grads->enc_edge[1].weight); fp.gr_b2 = const_cast<float*>(grads->enc_edge[1].bias);
+    fp.gr_w1 = wr(grads->enc_edge[0].weight); fp.gr_b1 = wr(grads->enc_edge[0].bias);
+    fp.gr_w2 = wr(grads->enc_edge[1].weight); fp.gr_b2 = wr(grads->enc_edge[1].bias);
     fp.fe = m->enc_edge[0].in_dim;
     mtmc::launch_grad_fold(fp, s);
   }
@@ -298,15 +302,11 @@ extern "C" int64_t mtmc_mpn_grad_layout(const mtmc_mpn_model* m, int64_t* offset
     ++n;
     total += (numel + 63) / 64 * 64;
   };
-  auto layer = [&](const mtmc_layer& l, bool bn) {
+  for_each_layer(*m, [&](const mtmc_layer& l, bool bn) {
     piece((int64_t)l.out_dim * l.in_dim);
     piece(l.out_dim);
     if (bn) { piece(l.out_dim); piece(l.out_dim); }
-  };
-  for (int l = 0; l < m->n_enc_layers; ++l) layer(m->enc_node[l], true);
-  layer(m->enc_edge[0], true); layer(m->enc_edge[1], true);
-  layer(m->upd_edge, true); layer(m->upd_node, true);
-  layer(m->cls, false);
+  });
   return total;
 }
 
@@ -320,16 +320,12 @@ extern "C" int32_t mtmc_mpn_backward_flat(const mtmc_mpn_model* model, const mtm
   if (flat_floats < need) return fail(MTMC_E_ARG, "mtmc_mpn_backward_flat: gradient buffer too small");
   mtmc_mpn_model g = *model;
   int n = 0;
-  auto layer = [&](mtmc_layer& l, bool bn) {
+  for_each_layer(g, [&](mtmc_layer& l, bool bn) {
     l.weight = flat + off[n++];
     l.bias = flat + off[n++];
     l.gamma = bn ? flat + off[n++] : nullptr;
     l.beta = bn ? flat + off[n++] : nullptr;
-  };
-  for (int l = 0; l < g.n_enc_layers; ++l) layer(g.enc_node[l], true);
-  layer(g.enc_edge[0], true); layer(g.enc_edge[1], true);
-  layer(g.upd_edge, true); layer(g.upd_node, true);
-  layer(g.cls, false);
+  });
   return backward_impl(model, call, d_logits_steps, d_h, &g, flat, (size_t)need * sizeof(float), d_x, d_edge_attr);
 }
 

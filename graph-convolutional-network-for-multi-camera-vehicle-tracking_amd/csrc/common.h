@@ -259,6 +259,7 @@ static __device__ unsigned long long g_ek[kEkKernels * 2 * kEkPoints];
 // seed_tick_kernel at the start of the forward from the caller's device counter), so that a HIP graph that holds the whole
 // training step draws new masks on every replay; the backward of the same tape reads the same word.
 struct Drop { unsigned long long seed; unsigned thresh; float inv_keep; int on; };
+constexpr Drop kNoDrop = {0, 0, 1.f, 0};   // no Dropout: every element kept, unscaled
 // Every kernel that draws masks calls drop_resolve on its own copy of the parameter ONCE, at its top (read inside drop_keep /
 // drop_apply -- per element -- the indirection cost the hashing kernels 25 us of a 600 us training step,
 // profiles/r05_seed_ab.txt); after it on is 0 or 1 and seed a value.

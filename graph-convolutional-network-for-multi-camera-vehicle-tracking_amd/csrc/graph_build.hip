@@ -447,14 +447,10 @@ int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_
   hipLaunchKernelGGL(mtmc::gb_normalize_kernel, dim3((unsigned)n_nodes), dim3(256), 0, s, feats, feat_row_stride, n_nodes,
                      feat_dim, colsq, l2norm, x_out, row_sq, row_sum);
   if (n_edges > 0) {
-    mtmc::GemmParams g;
-    g.A = x_out; g.lda = feat_dim; g.W = x_out; g.bias = zeros; g.Y = G; g.ldy = n_nodes;
-    g.stats_in = nullptr; g.gamma_in = nullptr; g.beta_in = nullptr; g.count = 1; g.stats_out = nullptr;
-    g.M = n_nodes; g.K = feat_dim; g.Nout = (int)n_nodes; g.drop_in = {0, 0, 1.f, 0}; g.drop_stream = 0;
-    g.slab = l.slab != l.total ? reinterpret_cast<float*>(ws + l.slab) : nullptr; g.split_k = 1;
+    mtmc::GemmParams g = mtmc::plain_gemm(x_out, feat_dim, x_out, zeros, G, n_nodes, n_nodes, feat_dim, (int)n_nodes);
     int sk = 1;
     mtmc::gemm_plan(n_nodes, feat_dim, (int)n_nodes, &sk);
-    if (sk <= 1) g.slab = nullptr;
+    if (sk > 1 && l.slab != l.total) g.slab = reinterpret_cast<float*>(ws + l.slab);
     if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return MTMC_E_ARG;
     mtmc::EdgeBuildParams p;
     p.in_list = in_list; p.in_off = in_off; p.out_list = out_list; p.out_off = out_off; p.block_off = block_off;

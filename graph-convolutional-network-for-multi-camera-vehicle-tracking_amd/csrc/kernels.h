@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/mtmc_mpn.h"
 #include "common.h"
+#include <type_traits>
 
 namespace mtmc {
 
@@ -123,54 +124,76 @@ struct NodeStatParams {
   int64_t node_begin, node_end;   // as in NodeProjParams
 };
 
-struct GemmParams {
-  const float* A; int64_t lda;       // [M][K] activations (raw pre-BN outputs of the previous layer, or x)
-  const float* W;                    // [Nout][K]
-  const float* bias;                 // [Nout]
-  float* Y; int64_t ldy;             // [M][Nout] raw outputs (pre-BN)
-  const double* stats_in;            // f64[2*K] column sum / sumsq of A's producer, or nullptr (layer 0)
-  const float* gamma_in; const float* beta_in;
-  double count;                      // BatchNorm row count (global N)
-  double* stats_out;                 // f64[2*Nout], accumulated atomically
-  int64_t M; int K; int Nout;
-  Drop drop_in; unsigned drop_stream;  // training: dropout applied with the input BatchNorm+ReLU
-  float* slab;                       // [split_k][M][Nout] scratch for split-K partial tiles, or nullptr
-  int split_k;                       // set by launch_gemm_bn
-  // fp16 two-piece path (gemm_bn_f16x3_kernel): |.|max bit patterns, u32[kAmaxRep] each (take the max), device
-  // memory; nullptr = not available
-  const unsigned* amax_a = nullptr;  // of A's source: x itself (no stats_in) or the producing layer's raw Y
-  const unsigned* amax_w = nullptr;  // of W
-  unsigned* amax_y = nullptr;        // out (atomicMax): of this layer's raw Y
-  // Passenger workgroups (few-row graphs): the edge encoder's hidden-layer moments (enc2) ride in this GEMM's launch -- the
-  // encoder chain and the edge branch are independent until the first round, and a few-row GEMM leaves most CUs idle.
-  // launch_gemm_bn runs the job either way: inside the launch where the chosen kernel carries passengers, else behind it.
+// ---- One linear layer of the node encoder, described in parts.  The five parameter blocks below compose them as public bases
+// (like PrepParams : PrepEdge), so a kernel reads p.A, p.Wh, p.pass_blocks, ... and a launch site fills each part once
+// (api_internal.h: fill_in / fill_out / fill_w / fill_x / ride_enc2; plain_gemm below).  Every field has a default: a block
+// that a site only partly fills has null pointers, zero sizes and no Dropout in the rest.
+// The activation input with its producer's BatchNorm and Dropout
+struct ActIn {
+  const float* A = nullptr; int64_t lda = 0;   // [M][K] activations (raw pre-BN outputs of the previous layer, or x)
+  const double* stats_in = nullptr;            // f64[2*K] column sum / sumsq of A's producer, or nullptr (layer 0: A is used as is)
+  const float* gamma_in = nullptr; const float* beta_in = nullptr;
+  double count = 0;                            // BatchNorm row count (global N)
+  Drop drop_in = kNoDrop; unsigned drop_stream = 0;   // training: Dropout applied with the input BatchNorm + ReLU
+};
+// An operand as fp16 planes with one power-of-two inverse scale per row (launch_split_rows / split_body.h); the plane layout
+// is the consuming kernel's: [2][K/32][rows][32] k-tile-major and swizzled (lds_dma.h), or [2][rows][K]
+struct PlanesA { const _Float16* Ah = nullptr; const float* inv_a = nullptr; };   // of A: [M] scales
+struct PlanesW { const _Float16* Wh = nullptr; const float* inv_w = nullptr; };   // of W: [Nout] scales
+// The output side
+struct LayerOut {
+  const float* bias = nullptr;                 // [Nout]
+  float* Y = nullptr; int64_t ldy = 0;         // [M][Nout] raw outputs (pre-BN)
+  double* stats_out = nullptr;                 // f64[2*Nout], accumulated atomically, or nullptr
+  unsigned* amax_y = nullptr;                  // u32[kAmaxRep] |Y|max (atomicMax on the bit patterns), or nullptr; the few-row
+                                               // kernels publish none
+  int64_t M = 0; int K = 0; int Nout = 0;
+};
+// Passenger workgroups (few-row graphs): the edge encoder's hidden-layer moments (enc2) ride in this layer's launch -- the
+// encoder chain and the edge branch are independent until the first round, and a few-row GEMM leaves most CUs idle.
+struct Enc2Ride {
   int pass_blocks = 0; EdgeEncParams pass_enc = {}; const float* pass_attr = nullptr; int64_t pass_edges = 0;
   double pass_e_total = 0; double* pass_stat = nullptr;
 };
 
-// Few-row graphs (gemm_few.hip): layer 0 on pre-split operands, one workgroup per 64 x 32 tile over all of K
-struct FewL0Params {
-  const _Float16* Ah; const float* inv_a;   // planes [2][K/32][M][32] of x (k-tile-major, swizzled: lds_dma.h), [M] inverse row scales
-  const _Float16* Wh; const float* inv_w;   // planes [2][K/32][Nout][32] of W0, [Nout]
-  const float* bias;
-  float* Y; int64_t ldy;
-  double* stats_out;                        // f64[2*Nout], accumulated atomically (or nullptr)
-  int64_t M; int K; int Nout;
+// The in-loop operand split (gemm_bn.hip) and the row-streaming kernel (gemm_rows.hip).
+// launch_gemm_bn runs the passenger job either way: inside the launch where the chosen kernel carries passengers, else behind it.
+struct GemmParams : ActIn, LayerOut, Enc2Ride {
+  const float* W = nullptr;                    // [Nout][K]
+  float* slab = nullptr;                       // [split_k][M][Nout] scratch for split-K partial tiles, or nullptr
+  int split_k = 1;                             // set by launch_gemm_bn
+  // fp16 two-piece path (gemm_bn_f16x3_kernel): |.|max bit patterns, u32[kAmaxRep] each (take the max), device
+  // memory; nullptr = not available
+  const unsigned* amax_a = nullptr;            // of A's source: x itself (no stats_in) or the producing layer's raw Y
+  const unsigned* amax_w = nullptr;            // of W
 };
-// ... layers >= 1: 16 rows x 16 / 32 columns per workgroup, K cut between its waves
-struct FewWaveParams {
-  const float* A; int64_t lda;              // [M][K] raw Y of the previous layer
-  const double* stats_in; const float* gamma_in; const float* beta_in; double count;   // its column statistics / BatchNorm
-  const _Float16* Wh; const float* inv_w;   // planes [2][K/32][Nout][32], [Nout]
-  const float* bias;
-  float* Y; int64_t ldy;
-  double* stats_out;                        // f64[2*Nout], accumulated atomically (or nullptr)
-  int64_t M; int K; int Nout;
-  Drop drop_in = {0, 0, 1.f, 0}; unsigned drop_stream = 0;   // training: Dropout applied with the input BatchNorm + ReLU
-  int tiles = 0;                            // set by launch_few_wave
-  // passenger workgroups as in GemmParams (the edge encoder's enc2 job rides in the last layer's launch)
-  int pass_blocks = 0; EdgeEncParams pass_enc = {}; const float* pass_attr = nullptr; int64_t pass_edges = 0;
-  double pass_e_total = 0; double* pass_stat = nullptr;
+// the two sides of a block from bare arguments (the diagnostics entry points and plain_gemm; the forward: api_internal.h)
+inline void set_in(ActIn* q, const float* A, int64_t lda, const double* stats_in = nullptr, const float* gamma_in = nullptr,
+                   const float* beta_in = nullptr, double count = 0) {
+  q->A = A; q->lda = lda; q->stats_in = stats_in; q->gamma_in = gamma_in; q->beta_in = beta_in; q->count = count;
+}
+inline void set_out(LayerOut* q, const float* bias, float* Y, int64_t ldy, int64_t M, int K, int Nout, double* stats_out = nullptr,
+                    unsigned* amax_y = nullptr) {
+  q->bias = bias; q->Y = Y; q->ldy = ldy; q->M = M; q->K = K; q->Nout = Nout; q->stats_out = stats_out; q->amax_y = amax_y;
+}
+// Y[M][Nout] = A[M][K] . W[Nout][K]^T + bias: no BatchNorm in or out, no Dropout, no slab; the |.|max words are optional
+inline GemmParams plain_gemm(const float* A, int64_t lda, const float* W, const float* bias, float* Y, int64_t ldy, int64_t M,
+                             int K, int Nout, const unsigned* amax_a = nullptr, const unsigned* amax_w = nullptr,
+                             unsigned* amax_y = nullptr) {
+  GemmParams g;
+  g.W = W; g.amax_a = amax_a; g.amax_w = amax_w;
+  set_in(&g, A, lda);
+  set_out(&g, bias, Y, ldy, M, K, Nout, nullptr, amax_y);
+  return g;
+}
+
+// Few-row graphs (gemm_few.hip): layer 0 on pre-split operands (planes [2][K/32][rows][32] of x and W0), one workgroup per
+// 64 x 32 tile over all of K
+struct FewL0Params : PlanesA, PlanesW, LayerOut {};
+// ... layers >= 1: 16 rows x 16 / 32 columns per workgroup, K cut between its waves; A = raw Y of the previous layer.  The
+// enc2 job may ride in the last layer's launch
+struct FewWaveParams : ActIn, PlanesW, LayerOut, Enc2Ride {
+  int tiles = 0;                               // set by launch_few_wave
 };
 bool few_l0_shape(int K, int Nout);
 bool few_wave_shape(int K, int Nout);
@@ -181,31 +204,20 @@ int launch_few_wave(const FewWaveParams& p, hipStream_t s);   // 0 ok, 1 unsuppo
 
 // First encoder layer on pre-split operands (gemm_presplit.hip): fp16 planes [2][rows][K] and one power-of-two
 // inverse scale per row, written by launch_split_rows.
-struct SplitGemmParams {
-  const _Float16* Ah; const float* inv_a;   // [2][M][K], [M]
-  const _Float16* Wh; const float* inv_w;   // [2][Nout][K], [Nout]
-  const float* bias;
-  float* Y; int64_t ldy;
-  double* stats_out;                        // f64[2*Nout], accumulated atomically (or nullptr)
-  unsigned* amax_y;                         // u32[kAmaxRep] (atomicMax) or nullptr
-  int64_t M; int K; int Nout;
+struct SplitGemmParams : PlanesA, PlanesW, LayerOut {   // planes [2][M][K] and [2][Nout][K]
   // a launch over the row PANEL [m_lo, M) of planes that hold M_rows rows (pipelined layer 0: the operand split of the next
   // panel runs beside this panel's GEMM); defaults = the whole matrix.  bm: tile height to use (0 = chosen per launch)
   int64_t m_lo = 0; int64_t M_rows = 0; int bm = 0;
 };
 // Encoder layers >= 1 of many-row graphs (gemm_staged.hip): A = raw outputs of the previous layer (its BatchNorm + ReLU
-// applied by producer waves on the way into LDS), W = the layer's weights pre-split by launch_split_rows.
-struct StagedGemmParams {
-  const float* A; int64_t lda;              // [M][K] raw Y of the previous layer
-  const double* stats_in; const float* gamma_in; const float* beta_in; double count;   // its column statistics / BatchNorm
-  const unsigned* amax_a;                   // u32[kAmaxRep]: its |Y|max
-  const _Float16* Wh; const float* inv_w;   // [2][Nout][K] planes (k-tile-major, swizzled), [Nout] inverse row scales
-  const float* bias;
-  float* Y; int64_t ldy;
-  double* stats_out;                        // f64[2*Nout], accumulated atomically
-  unsigned* amax_y;                         // u32[kAmaxRep] (atomicMax) or nullptr
-  int64_t M; int K; int Nout;
+// applied by producer waves on the way into LDS; eval mode only: drop_in is not read), W = the layer's weights pre-split by
+// launch_split_rows into planes [2][Nout][K] (k-tile-major, swizzled).
+struct StagedGemmParams : ActIn, PlanesW, LayerOut {
+  const unsigned* amax_a = nullptr;            // u32[kAmaxRep]: |A|max
 };
+static_assert(std::is_trivially_copyable<GemmParams>::value && std::is_trivially_copyable<FewL0Params>::value &&
+              std::is_trivially_copyable<FewWaveParams>::value && std::is_trivially_copyable<SplitGemmParams>::value &&
+              std::is_trivially_copyable<StagedGemmParams>::value, "the blocks are passed to kernels by value");
 bool staged_layer(int64_t rows, int K, int Nout);       // many rows, K % 32 == 0, K <= 2048, Nout % 256 == 0 or (Nout == 128, rows >= 49152), not disabled
 int launch_gemm_staged(const StagedGemmParams& p, hipStream_t s);   // 0 ok, 1 unsupported shape, MTMC_E_HIP
 int staged_tile_rows(int64_t M, int tiles_n, int wm);   // (also used by the laboratory's second form, lab/staged2_lab.hip)
@@ -221,6 +233,22 @@ int presplit_tile_rows(int64_t M, int tiles_n);       // tile height the layer-0
 bool allow_big_lds(const void* fn, int bytes);
 bool presplit_layer0(int64_t rows, int K, int Nout);   // many rows, K % 64 == 0, K <= 2048, not disabled (MTMC_GEMM_NO_PRESPLIT)
 int launch_gemm_presplit(const SplitGemmParams& p, hipStream_t s);   // 0 ok, 1 unsupported shape, MTMC_E_HIP
+
+// Shared by the mtmc_linear_*_raw diagnostics (api.hip) and their laboratory twins (lab/).  Their work buffer: the fp16 planes
+// of A (a_planes) and its [M] inverse row scales, then from the next 256-byte boundary the planes of W and its [N] scales
+struct RawWork { _Float16* Ah; float* inv_a; _Float16* Wh; float* inv_w; uint64_t bytes; };
+inline RawWork raw_work(void* work, int64_t M, int K, int N, bool a_planes) {
+  unsigned char* wk = static_cast<unsigned char*>(work);
+  const uint64_t ia_off = a_planes ? (uint64_t)M * K * 4 : 0, wh_off = (ia_off + (uint64_t)M * 4 + 255) / 256 * 256;
+  const uint64_t iw_off = wh_off + (uint64_t)N * K * 4;
+  return {reinterpret_cast<_Float16*>(wk), reinterpret_cast<float*>(wk + ia_off), reinterpret_cast<_Float16*>(wk + wh_off),
+          reinterpret_cast<float*>(wk + iw_off), iw_off + (uint64_t)N * 4};
+}
+// scratch (u32[3][kAmaxRep]: the |A|max, |W|max, |Y|max words) and stats (f64[2*N]) cleared; either may be NULL
+inline bool clear_raw(uint32_t* scratch, double* stats, int N, hipStream_t s) {
+  return (!scratch || hipMemsetAsync(scratch, 0, 3 * kAmaxRep * sizeof(uint32_t), s) == hipSuccess) &&
+         (!stats || hipMemsetAsync(stats, 0, 2 * (size_t)N * sizeof(double), s) == hipSuccess);
+}
 
 void launch_prep(const PrepParams& p, hipStream_t s);
 void launch_enc2(const EdgeEncParams& enc, const float* attr, int64_t n_edges, double e_total, double* stat_enc2,

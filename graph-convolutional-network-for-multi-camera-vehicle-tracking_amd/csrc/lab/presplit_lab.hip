@@ -672,24 +672,19 @@ extern "C" int32_t mtmc_lab_linear_presplit_raw(const float* A, int64_t lda, con
                                                 int32_t K, int32_t N, void* work, uint64_t work_bytes, uint32_t* scratch,
                                                 double* stats, int32_t variant, void* stream) {
   if (!A || !W || !bias || !Y || !work || !scratch || M < 1 || K < 64 || K % 64 || K > 2048 || N < 1) return MTMC_E_ARG;
-  const uint64_t a_bytes = (uint64_t)M * K * 4, w_bytes = (uint64_t)N * K * 4;
-  const uint64_t ia_off = a_bytes, wh_off = (ia_off + (uint64_t)M * 4 + 255) / 256 * 256, iw_off = wh_off + w_bytes;
-  if (work_bytes < iw_off + (uint64_t)N * 4) return MTMC_E_ARG;
+  const mtmc::RawWork wk = mtmc::raw_work(work, M, K, N, true);
+  if (work_bytes < wk.bytes) return MTMC_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, 3 * mtmc::kAmaxRep * sizeof(uint32_t), s) != hipSuccess) return MTMC_E_HIP;
-  if (stats && hipMemsetAsync(stats, 0, 2 * (size_t)N * sizeof(double), s) != hipSuccess) return MTMC_E_HIP;
-  unsigned char* wk = static_cast<unsigned char*>(work);
+  if (!mtmc::clear_raw(scratch, stats, N, s)) return MTMC_E_HIP;
   if (variant >= 0) {
-    mtmc::launch_split_rows(A, lda, M, K, wk, reinterpret_cast<float*>(wk + ia_off), s);
-    mtmc::launch_split_rows(W, K, N, K, wk + wh_off, reinterpret_cast<float*>(wk + iw_off), s);
+    mtmc::launch_split_rows(A, lda, M, K, wk.Ah, wk.inv_a, s);
+    mtmc::launch_split_rows(W, K, N, K, wk.Wh, wk.inv_w, s);
   } else {
     variant = -variant - 1;          // negative: the planes in `work` are reused (times the GEMM alone)
   }
   mtmc::SplitGemmParams g;
-  g.Ah = reinterpret_cast<const _Float16*>(wk); g.inv_a = reinterpret_cast<const float*>(wk + ia_off);
-  g.Wh = reinterpret_cast<const _Float16*>(wk + wh_off); g.inv_w = reinterpret_cast<const float*>(wk + iw_off);
-  g.bias = bias; g.Y = Y; g.ldy = N; g.stats_out = stats; g.amax_y = scratch + 2 * mtmc::kAmaxRep;
-  g.M = M; g.K = K; g.Nout = N;
+  g.Ah = wk.Ah; g.inv_a = wk.inv_a; g.Wh = wk.Wh; g.inv_w = wk.inv_w;
+  mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
   const int rc = mtmc::launch_lab(g, s, variant);
   if (rc != 0) return rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG;
   return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;

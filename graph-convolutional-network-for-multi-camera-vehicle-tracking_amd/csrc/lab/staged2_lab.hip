@@ -386,19 +386,18 @@ extern "C" int32_t mtmc_lab_linear_staged2_raw(const float* A, int64_t lda, cons
   const uint64_t iw_off = ((uint64_t)N * K * 4 + 255) / 256 * 256;
   if (work_bytes < iw_off + (uint64_t)N * 4) return MTMC_E_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, 3 * mtmc::kAmaxRep * sizeof(uint32_t), s) != hipSuccess) return MTMC_E_HIP;
-  if (stats && hipMemsetAsync(stats, 0, 2 * (size_t)N * sizeof(double), s) != hipSuccess) return MTMC_E_HIP;
+  if (!mtmc::clear_raw(scratch, stats, N, s)) return MTMC_E_HIP;
   mtmc::PrepParams pp = {};
   pp.n_edges = 0; pp.n_jobs = 1;
   pp.jobs[0] = {A, M, K, lda, scratch, 0, 0};
   mtmc::launch_prep(pp, s);
-  unsigned char* wk = static_cast<unsigned char*>(work);
-  mtmc::launch_split_rows(W, K, N, K, wk, reinterpret_cast<float*>(wk + iw_off), s);
+  float* inv_w = reinterpret_cast<float*>(static_cast<char*>(work) + iw_off);
+  mtmc::launch_split_rows(W, K, N, K, work, inv_w, s);
   mtmc::StagedGemmParams g;
-  g.A = A; g.lda = lda; g.stats_in = stats_in; g.gamma_in = gamma_in; g.beta_in = beta_in; g.count = count;
-  g.amax_a = scratch; g.Wh = reinterpret_cast<const _Float16*>(wk); g.inv_w = reinterpret_cast<const float*>(wk + iw_off);
-  g.bias = bias; g.Y = Y; g.ldy = N; g.stats_out = stats; g.amax_y = scratch + 2 * mtmc::kAmaxRep;
-  g.M = M; g.K = K; g.Nout = N;
+  mtmc::set_in(&g, A, lda, stats_in, gamma_in, beta_in, count);
+  g.amax_a = scratch;
+  g.Wh = static_cast<_Float16*>(work); g.inv_w = inv_w;
+  mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
   const int rc = mtmc::launch_gemm_staged2(g, s);
   if (rc != 0) return rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG;
   return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
