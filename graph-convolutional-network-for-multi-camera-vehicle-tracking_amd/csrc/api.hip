@@ -156,7 +156,7 @@ int32_t mtmc_mpn_plan_call(const mtmc_mpn_model* model, const mtmc_mpn_call* cal
   out->lazy_edges = p.lazy_edges ? 1 : 0;
   out->avg_degree = p.avg_degree;
   out->pass_a_col_blocks = p.col_blocks;
-  out->pass_c = p.pass_c_pub;
+  out->pass_c = p.pass_c_pub();
   out->node_stat_folded = p.fold_node_stat ? 1 : 0;
   out->layer0_panels = p.l0_panels;
   out->enc2_passenger = (p.enc2_may_ride && !(c->flags & MTMC_F_FORK)) ? 1 : 0;     // what mtmc_mpn_forward makes of it

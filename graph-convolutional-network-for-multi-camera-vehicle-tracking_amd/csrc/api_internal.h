@@ -264,7 +264,15 @@ struct CallPlan {
   bool fold_node_stat;                           // few-edge list: node-update statistics out of node_proj + pass B
   double avg_degree;                             // edges per source row of this call's edges
   int col_blocks;                                // column blocks of pass A (0: edge order)
-  int pass_c, pass_c_pub;                        // plan_pass_c (RoundParams::mfma_c) and the MTMC_PASS_C_* it amounts to
+  mtmc::PassC pass_c;                            // plan_pass_c (RoundParams::pass_c)
+  // the public value names the matrix-core kernel the call launches, with or without the walk behind it
+  int pass_c_pub() const {
+    switch (pass_c) {
+      case mtmc::kPassCSortedWalk: case mtmc::kPassCSortedDet: return MTMC_PASS_C_MFMA_SORTED;
+      case mtmc::kPassCAnyWalk: case mtmc::kPassCAny: return MTMC_PASS_C_MFMA_ANY;
+      default: return MTMC_PASS_C_WALK;
+    }
+  }
 };
 
 inline bool in_loop_kernel(int k) { return k == MTMC_GEMM_GENERIC || k == MTMC_GEMM_INLOOP_64 || k == MTMC_GEMM_INLOOP_128; }
@@ -322,9 +330,6 @@ inline void make_plan(const mtmc_mpn_model* m, const mtmc_mpn_call* c, const Lay
                    mtmc::plan_col_blocks(N, E, p->avg_degree, lo.training) == lo.col_blocks) ? lo.col_blocks : 0;
   const bool drop_n = lo.training && m->dropout_upd_node > 0.f;
   p->pass_c = mtmc::plan_pass_c(m->agg, (c->flags & MTMC_F_DETERMINISTIC) != 0, drop_n, E, N, p->avg_degree);
-  // the public value names what launch_pass_c launches: the sorted kernel is MFMA_SORTED, the any-order kernel MFMA_ANY
-  // (on a many-edge list it still has the walk launched behind it for unsorted rows)
-  p->pass_c_pub = p->pass_c == 1 ? (mtmc::pass_c_sorted_taken(N) ? MTMC_PASS_C_MFMA_SORTED : MTMC_PASS_C_MFMA_ANY) : p->pass_c;
 }
 
 struct Ctx {
@@ -468,7 +473,7 @@ inline mtmc::RoundParams round_params(const Ctx& x, int r) {
   p.deg = x.at<int>(x.lo.pub.deg_off); p.row_start = x.at<int>(x.lo.row_start); p.carry = x.at<float>(x.lo.carry);
   p.n_nodes = x.c->n_nodes;
   p.avg_degree = x.plan.avg_degree;
-  p.mfma_c = x.plan.pass_c;
+  p.pass_c = x.plan.pass_c;
   p.col_blocks = x.plan.col_blocks;
   p.col_sub = x.at<int>(x.lo.col_sub); p.cb_row_lo = proj_lo(x.c); p.cb_row_hi = proj_hi(x.c);
   p.enc = enc_params(x);

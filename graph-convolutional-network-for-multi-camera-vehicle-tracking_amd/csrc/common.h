@@ -401,7 +401,7 @@ __device__ __forceinline__ void edge_enc_out(const EdgeEncParams& p, const EdgeE
 __device__ __forceinline__ void load_attr(const float* attr, int fe, int64_t e, float& a0, float& a1);
 
 // Moments of the edge encoder's hidden activations (enc2): workgroup `block` of `n_blocks`, 256 threads.  The body of
-// enc2_kernel (edge_kernels.hip) and of the passenger workgroups the few-row encoder GEMM carries (gemm_bn.hip).
+// enc2_kernel (edge_prep.hip) and of the passenger workgroups the few-row encoder GEMM carries (gemm_bn.hip).
 __device__ __forceinline__ void enc2_body(const EdgeEncParams& enc_in, const float* attr, int64_t n_edges, double e_total,
                                           double* stat_enc2, int block, int n_blocks) {
   EdgeEncParams enc = enc_in;

@@ -57,6 +57,16 @@ struct PrepParams : PrepEdge {
   AmaxJob jobs[2 * MTMC_MAX_ENC_LAYERS + 2];
 };
 
+// The kernels pass C launches (plan_pass_c, once per call: api_internal.h make_plan).  Sortedness of the rows is only known on
+// the device (prep_kernel's flags), so the forms with a second kernel launch both and one of the two returns at once.
+enum PassC : int {
+  kPassCWalk = 0,         // the half-wave walk (pass_c_kernel)
+  kPassCAnyWalk = 1,      // many-edge list: the any-order matrix-core kernel; unsorted rows: it returns, the walk behind it does the round
+  kPassCAny = 2,          // few-edge list: the any-order matrix-core kernel alone, whatever the order
+  kPassCSortedWalk = 3,   // many-edge list: pass_c_sorted_kernel, the walk takes the < 64 edges behind the last whole chunk (unsorted: all)
+  kPassCSortedDet = 4,    // fixed-order sums: pass_c_sorted_kernel<., true> takes that tail itself (unsorted rows: the walk does the round)
+};
+
 // Everything one message-passing round needs (passes A, B, C).
 struct RoundParams {
   const int* row32; const int* col32; const float* attr;
@@ -79,7 +89,7 @@ struct RoundParams {
   // eval mode: e' = relu(bn(z1)) is never written -- pass C and the next round's pass A recompute it from z1 (4 FMAs)
   // with the round's z1 statistics; pass B only reduces it.  16 B/edge/round less traffic.  prev_stats: round r-1's block
   int lazy_e; const double* prev_stats;
-  int mfma_c;                // the call's plan_pass_c (round_params); launch_pass_c turns 1 into 3 / 4 for the sorted kernel
+  PassC pass_c;              // the call's plan_pass_c (round_params)
   int stream_z1;             // set by launch_pass_a: z1 is stored non-temporally (lists whose z1 outgrows the Infinity Cache)
   int det_len;               // set by launch_pass_c: edges per carry chunk of the deterministic sums (32, or a span of the sorted kernel)
   int det; const int* flags; const int* deg; const int* row_start; float* carry; int64_t n_nodes;   // deterministic sums
@@ -258,12 +268,9 @@ int plan_col_blocks(int64_t n_nodes, int64_t n_edges, double avg_degree, bool tr
 void launch_colblock_index(const RoundParams& p, int* sub, int B, int64_t row_lo, int64_t row_hi, hipStream_t s);
 void launch_pass_b(const RoundParams& p, hipStream_t s);
 void launch_pass_c(const RoundParams& p, hipStream_t s);
-// Which pass-C kernel a call takes (host-only, once per call: api_internal.h make_plan): 0 = the half-wave walk; 1 = the
-// matrix-core kernel with the walk launched behind it for unsorted rows (many-edge lists); 2 = the matrix-core kernel
-// alone (few-edge lists).  avg_degree: edges per source row of THIS call's edges (RoundParams::avg_degree).
-int plan_pass_c(int agg, bool deterministic, bool dropout, int64_t n_edges, int64_t n_nodes, double avg_degree);
-bool pass_c_sorted_taken(int64_t n_nodes);
-// Few-edge / many-edge regime of the edge passes (edge_kernels.hip: pick_ept).  Up to this many edges: one edge per thread in
+// avg_degree: edges per source row of THIS call's edges (RoundParams::avg_degree)
+PassC plan_pass_c(int agg, bool deterministic, bool dropout, int64_t n_edges, int64_t n_nodes, double avg_degree);
+// Few-edge / many-edge regime of the edge passes (edge_common.h: pick_ept).  Up to this many edges: one edge per thread in
 // passes A / B, e' stored, the node-update statistics folded into node_proj + pass B, ONE any-order matrix-core pass C, the
 // operand-split jobs and enc2 as passengers; above: four edges per thread, lazy e', node_stat, pass_c_sorted + the walk behind
 // it.  Rounds 1-4: 2048 * 256 (one 2048-block grid of one edge per thread); round 5, after the few-edge forms lost three
@@ -278,6 +285,11 @@ void launch_seed_tick(unsigned long long* counter, unsigned long long* word, hip
 int plan_edges_per_thread(int64_t n_edges);      // passes A / B: 1 on few-edge lists, 4 otherwise
 void launch_classify_e0(const EdgeEncParams& enc, const float* attr, int64_t n_edges, double e_total,
                         const float* cls_w, const float* cls_b, int n_classes, float* logits, hipStream_t s);
+
+#if EK_STAMP
+int ek_stamps_pass_a(unsigned long long* out);   // a unit's copy of the in-kernel stamps (common.h) -> host buffer; hipError_t
+int ek_stamps_pass_b(unsigned long long* out);
+#endif
 
 void launch_node_proj(const NodeProjParams& p, hipStream_t s);
 void launch_node_stat(const NodeStatParams& p, hipStream_t s);

@@ -1,4 +1,4 @@
-// The edge part of prep_kernel as a device function: shared by prep_kernel (edge_kernels.hip) and by the passenger workgroups of
+// The edge part of prep_kernel as a device function: shared by prep_kernel (edge_prep.hip) and by the passenger workgroups of
 // few_l0_kernel (gemm_few.hip: on few-row forwards nothing of this is needed before the first round, so it rides in the first
 // encoder layer's launch instead of standing in front of it).  NW = waves per workgroup of the hosting kernel.
 #pragma once

@@ -1,6 +1,6 @@
 // The operand split of the pre-split GEMM kernels as a device function: 8 rows per 256-thread workgroup, half a wave per
 // row.  Three users: split_rows_kernel (gemm_presplit.hip: x and weights of many-row graphs), and two kinds of passenger
-// workgroups of prep_kernel (edge_kernels.hip): the x planes of few-row graphs, and the CONTENT-VERIFIED weight-plane cache.
+// workgroups of prep_kernel (edge_prep.hip): the x planes of few-row graphs, and the CONTENT-VERIFIED weight-plane cache.
 //
 // Weight-plane cache (round 5; replaces the host-side (data_ptr, _version) key of round 4, which writes through
 // `param.data` and recycled allocations could fool): the fp16 planes + row scales of the node-encoder weights live in a

@@ -123,7 +123,7 @@ def _skewed_graph(N, E, seed):
     (dict(num_enc_steps=2, num_class_steps=1), "boundary_dups"),   # many equal columns exactly on the column-block boundaries
 ])
 def test_column_blocked_pass_a_regime(over, unsort_cols):
-    """Pass A by column blocks (csrc/edge_kernels.hip pass_a_blocked_kernel: graphs whose Pc table, 16 B per node, outgrows
+    """Pass A by column blocks (csrc/edge_pass_a.hip pass_a_blocked_kernel: graphs whose Pc table, 16 B per node, outgrows
     an XCD's L2): 230 000 nodes / 9.2 M edges is the smallest size that takes it (8 blocks of 28 750 nodes, sub-runs of 5
     edges -- ragged: many are empty) -- against the oracle's code run by torch on the device in fp64, every edge."""
     from mtmc_mpn import _lib, engine

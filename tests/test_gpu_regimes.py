@@ -348,6 +348,67 @@ def test_sorted_many_edge_list_with_low_degree_stretches(tail):
     assert int((deg == 0).sum()) > 0 and int(((deg > 0) & (deg < 8)).sum()) > 1000     # the stretches the test is about
 
 
+# ---- classifiers that are not two-class -----------------------------------------------------------------------------------
+# The library accepts 1..4 classifier outputs (MTMC_MAX_CLASSES); everything above runs the reference's 2.  The general class
+# count is one device function (csrc/edge_common.h classify_edge) that every kernel with a classifier in it calls: one case per
+# kernel, each on the smallest list of this file that reaches it.  Logits and h only: _check's label flips need two classes.
+
+def _model_with_classes(L, C):
+    cls = dict(mtmc_mpn.default_params()["classifier_feats_dict"], edge_out_dim=C)
+    return _model(L, 1, classifier_feats_dict=cls)
+
+
+def _check_logits_and_h(got, h, want64, h64, C, tag):
+    assert len(got) == len(want64) == 1 and got[0].shape == want64[0].shape and got[0].shape[1] == C, tag
+    err = (got[0].double() - want64[0]).abs().max().item()
+    print(f"{tag}: max |dlogit| {err:.3e}")
+    assert err <= LOGIT_TOL, f"{tag}: max |dlogit| {err:.3e}"
+    assert (h.double() - h64).abs().max().item() <= 1e-4 * max(1.0, h64.abs().max().item()), tag
+
+
+@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("form", ["classify_e0", "walk", "mfma_any"])
+def test_classifier_widths_on_short_lists(form, C):
+    """classify_e0_kernel (L = 0, the S02 ground-truth graph), the walk (22 edges per source row) and the any-order
+    matrix-core kernel (36 000 edges at 72 per row) with 1 and 3 classifier outputs."""
+    if form == "classify_e0":
+        L, d, want_plan = 0, graphs.camera_graph(), None
+    elif form == "walk":
+        L, d, want_plan = 2, _random_sorted_graph(2000, 22_000, seed=40), _lib.PASS_C_WALK
+    else:
+        L, d, want_plan = 2, _random_sorted_graph(500, 18_000, seed=41), _lib.PASS_C_MFMA_ANY
+    m, sd, params = _model_with_classes(L, C)
+    if want_plan is not None:
+        assert engine.ForwardEngine(m).plan(d.x.shape[0], d.edge_index.shape[1]).pass_c == want_plan
+    got, h = _gpu(m.cuda(), d, transposed_view=False)
+    want64, h64 = _oracle(sd, params, d)
+    _check_logits_and_h(got, h, want64, h64, C, f"{form} C={C}")
+
+
+@pytest.fixture(scope="module")
+def many_edge_oracle():
+    """The fp64 answer on the many_edge graph per class count: shared by the plain and the deterministic case."""
+    return {}
+
+
+@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("det", [False, True], ids=["plain", "deterministic"])
+def test_classifier_widths_on_the_sorted_kernel(many_edge, many_edge_oracle, det, C):
+    """pass_c_sorted_kernel with 1 and 3 classifier outputs.  1 642 800 % 64 = 48: the 48 edges behind the last whole chunk get
+    their logits from the walk launched behind it (plain) or from the kernel's own partial last chunk (deterministic)."""
+    m, sd, params = _model_with_classes(1, C)
+    flags = _lib.F_DETERMINISTIC if det else 0
+    plan = engine.ForwardEngine(m).plan(1480, 1_642_800, flags=flags)
+    assert plan.pass_c == _lib.PASS_C_MFMA_SORTED and plan.lazy_edges
+    m = m.cuda()
+    m.deterministic = det
+    got, h = _gpu(m, many_edge)
+    if C not in many_edge_oracle:
+        many_edge_oracle[C] = _oracle(sd, params, many_edge)
+    want64, h64 = many_edge_oracle[C]
+    _check_logits_and_h(got, h, want64, h64, C, f"sorted det={det} C={C}")
+
+
 def test_two_host_threads_run_many_row_forwards_on_their_own_streams():
     """the pipelined layer 0 had ONE side stream + event set per device; two host threads recorded and waited
     on the same event objects and a panel GEMM of one could start before its own operand split had finished.  Now one set

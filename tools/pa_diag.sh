@@ -9,7 +9,7 @@ CS=$ROOT/graph-convolutional-network-for-multi-camera-vehicle-tracking_amd/csrc
 cd $ROOT && patch -p1 < tools/pa_diag.patch > /dev/null
 export MTMC_NO_COL_BLOCKS=1 MTMC_SKIP_ISA_LINT=1
 for d in 0 1 2 3 4; do
-  (cd $CS && rm -f edge_kernels.o && make -s EXTRA="-DPA_DIAG=$d" libmtmc_mpn.so > /dev/null 2>&1)
+  (cd $CS && rm -f edge_pass_a.o && make -s EXTRA="-DPA_DIAG=$d" libmtmc_mpn.so > /dev/null 2>&1)
   python3 $ROOT/bench.py --full --workload cfg5 --steps 4 --warmup 2 --no-cpu 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
@@ -17,5 +17,5 @@ print('PA_DIAG=$d: forward %.3f ms  pass_a (3 launches) %.3f ms  pass_b %.3f  pa
 "
 done
 cd $ROOT && patch -R -p1 < tools/pa_diag.patch > /dev/null
-(cd $CS && rm -f edge_kernels.o && make -s libmtmc_mpn.so > /dev/null 2>&1)
+(cd $CS && rm -f edge_pass_a.o && make -s libmtmc_mpn.so > /dev/null 2>&1)
 echo restored
