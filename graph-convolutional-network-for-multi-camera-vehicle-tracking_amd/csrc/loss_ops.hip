@@ -116,6 +116,149 @@ static inline int ce_grid_fwd(int64_t n) {
   return g > 512 ? 512 : g;
 }
 
+
+// ---- mtmc_edge_loss_*: loss and metrics of every classified step in one pass (include/mtmc_mpn.h) -------------------
+// Both class counts reduce to one scalar per row, the margin z of the true class (x[y] - x[1-y]; one logit: +-x): the row
+// loss is softplus(-z), the true-class probability sigmoid(z), and d loss / d z = -sigmoid(-z).  e = exp(-|z|) <= 1 serves
+// all three, so |x| = 80 (e = 0 or tiny) stays finite.
+__device__ __forceinline__ void el_row(float z, float& l, float& p, float& q) {   // l = softplus(-z), p = sigmoid(z), q = 1 - p
+  const float e = expf(-fabsf(z));
+  const float inv = 1.f / (1.f + e);
+  l = fmaxf(-z, 0.f) + log1pf(e);
+  p = z >= 0.f ? inv : e * inv;
+  q = z >= 0.f ? e * inv : inv;
+}
+template <int C>
+__device__ __forceinline__ float el_margin(const float* x, int64_t i, bool y, bool& pred) {
+  if (C == 2) {
+    const float2 v = reinterpret_cast<const float2*>(x)[i];
+    pred = v.y > v.x;                                        // argmax == 1; a tie is class 0 (first maximum)
+    return y ? v.y - v.x : v.x - v.y;
+  }
+  const float v = x[i];
+  pred = v >= 0.f;
+  return y ? v : -v;
+}
+
+// scratch: per step kStatRep replicas of kElStride 64-bit words (128 bytes): L0 L1 P0 P1 (f64) | TP FP TN FN (u64) | padding
+constexpr int kElStride = 16;
+
+// grid (x: row blocks, y: steps); both dimensions are strided over, so any n and any n_steps run
+template <int C>
+__global__ __launch_bounds__(256) void el_forward_kernel(const float* logits, const int64_t* labels, int64_t n, int n_steps,
+                                                         double* scratch) {
+  __shared__ double red[4 * 4];
+  __shared__ unsigned int cnt[4];
+  const int64_t nthreads = (int64_t)gridDim.x * 256;
+  for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
+    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const float* x = logits + (int64_t)s * n * C;
+    double acc[4] = {0, 0, 0, 0};
+    unsigned int c[4] = {0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
+      const int64_t lab = labels[i];
+      if (lab != 0 && lab != 1) continue;
+      const bool y = lab == 1;
+      bool pred;
+      const float z = el_margin<C>(x, i, y, pred);
+      float l, p, q;
+      el_row(z, l, p, q);
+      if (y) { acc[1] += l; acc[3] += p; } else { acc[0] += l; acc[2] += p; }
+      c[0] += y && pred; c[1] += !y && pred; c[2] += !y && !pred; c[3] += y && !pred;
+    }
+    double* rep = scratch + (int64_t)s * kStatRep * kElStride;
+    block_atomic_add<4>(acc, rep, kElStride, red);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned int v = c[j];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if ((threadIdx.x & 63) == 0 && v) atomicAdd(&cnt[j], v);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && cnt[threadIdx.x])
+      atomicAdd(reinterpret_cast<unsigned long long*>(rep + (blockIdx.x % kStatRep) * kElStride + 4) + threadIdx.x,
+                (unsigned long long)cnt[threadIdx.x]);
+    __syncthreads();
+  }
+}
+
+// one wave: the class weights from the counts, then lane l takes steps l, l + 64, ...; the loss is their wave sum
+__global__ __launch_bounds__(64) void el_finalize_kernel(const double* scratch, int n_steps, int C, int weight_mode,
+                                                         const float* weight, float fpr_alpha, double* record, float* out,
+                                                         long long* confusion) {
+  const unsigned long long* words = reinterpret_cast<const unsigned long long*>(scratch);
+  unsigned long long k0[4] = {0, 0, 0, 0};                        // the label counts are those of any step: step 0
+  for (int r = 0; r < kStatRep; ++r)
+    for (int j = 0; j < 4; ++j) k0[j] += words[r * kElStride + 4 + j];
+  const double n0 = (double)(k0[1] + k0[2]), n1 = (double)(k0[0] + k0[3]);
+  double w0 = 1.0, w1 = 1.0;
+  if (weight_mode == MTMC_EDGE_W_GIVEN) {
+    if (C == 2) { w0 = weight[0]; w1 = weight[1]; } else w1 = weight[0];
+  } else if (weight_mode == MTMC_EDGE_W_BALANCED && n0 > 0 && n1 > 0) {
+    w1 = n0 / n1;
+  }
+  const double D = C == 2 ? w0 * n0 + w1 * n1 : n0 + n1;
+  float* class_loss = out + 3;
+  float* class_prob = class_loss + 2 * (int64_t)n_steps;
+  float* fpr_out = class_prob + 2 * (int64_t)n_steps;
+  double part = 0;
+  for (int s = threadIdx.x; s < n_steps; s += 64) {
+    const int64_t base = (int64_t)s * kStatRep * kElStride;
+    double f[4] = {0, 0, 0, 0};
+    unsigned long long k[4] = {0, 0, 0, 0};
+    for (int r = 0; r < kStatRep; ++r)
+      for (int j = 0; j < 4; ++j) { f[j] += scratch[base + r * kElStride + j]; k[j] += words[base + r * kElStride + 4 + j]; }
+    const double m0 = (double)(k[1] + k[2]), m1 = (double)(k[0] + k[3]);
+    const double fpr = m0 > 0 ? (double)k[1] / m0 : 0.0;
+    part += (w0 * f[0] + w1 * f[1]) / D + (double)fpr_alpha * fpr;
+    class_loss[2 * s] = (float)(m0 > 0 ? f[0] / m0 : 0.0);
+    class_loss[2 * s + 1] = (float)(m1 > 0 ? f[1] / m1 : 0.0);
+    class_prob[2 * s] = (float)(m0 > 0 ? f[2] / m0 : 0.5);
+    class_prob[2 * s + 1] = (float)(m1 > 0 ? f[3] / m1 : 0.5);
+    fpr_out[s] = (float)fpr;
+    for (int j = 0; j < 4; ++j) confusion[4 * (int64_t)s + j] = (long long)k[j];
+  }
+  part = wave_sum(part);
+  if (threadIdx.x == kWaveSumLane) {
+    out[0] = (float)part; out[1] = (float)w0; out[2] = (float)w1;
+    record[0] = w0; record[1] = w1; record[2] = D; record[3] = n0 + n1;
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void el_backward_kernel(const float* logits, const int64_t* labels, int64_t n, int n_steps,
+                                                          const float* grad, const double* record, float* d_logits) {
+  const double gd = (double)grad[0] / record[2];
+  const float g0 = (float)(gd * record[0]), g1 = (float)(gd * record[1]);
+  const int64_t nthreads = (int64_t)gridDim.x * 256;
+  for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
+    const float* x = logits + (int64_t)s * n * C;
+    float* d = d_logits + (int64_t)s * n * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
+      const int64_t lab = labels[i];
+      float dz = 0.f;                                        // d loss / d z; skipped rows: 0
+      const bool y = lab == 1;
+      if (lab == 0 || lab == 1) {
+        bool pred;
+        float l, p, q;
+        el_row(el_margin<C>(x, i, y, pred), l, p, q);
+        dz = -(y ? g1 : g0) * q;
+      }
+      if (C == 2) reinterpret_cast<float2*>(d)[i] = y ? make_float2(-dz, dz) : make_float2(dz, -dz);
+      else d[i] = y ? dz : -dz;
+    }
+  }
+}
+
+// x: row blocks up to `cap` workgroups in all (the forward ends in eight 64-bit atomics per workgroup: 512, as ce_grid_fwd)
+static inline dim3 el_grid(int64_t n, int n_steps, int cap) {
+  const int gy = n_steps < 1024 ? n_steps : 1024;
+  const int64_t b = (n + 255) / 256, bx = cap / gy < 1 ? 1 : cap / gy;
+  return dim3((unsigned)(b < 1 ? 1 : (b > bx ? bx : b)), (unsigned)gy);
+}
+
 }  // namespace mtmc
 
 extern "C" {
@@ -186,6 +329,51 @@ int32_t mtmc_edge_confusion(const float* logits, const int64_t* labels, int64_t 
   if (n > 0)
     hipLaunchKernelGGL(mtmc::confusion_kernel, dim3(mtmc::ce_grid(n) > 256 ? 256 : mtmc::ce_grid(n)), dim3(256), 0, s, logits,
                        labels, n, n_classes, reinterpret_cast<unsigned long long*>(counts));
+  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+}
+
+size_t mtmc_edge_loss_scratch_bytes(int32_t n_steps) {
+  return n_steps < 1 ? 0 : (size_t)n_steps * mtmc::kStatRep * mtmc::kElStride * sizeof(double);
+}
+
+int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                               int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
+                               size_t scratch_bytes, double* record, float* out, int64_t* confusion, void* stream) {
+  if (!logits || !labels || !scratch || !record || !out || !confusion || n < 0 || n_steps < 1) return MTMC_E_ARG;
+  if (n_classes != 1 && n_classes != 2) return MTMC_E_ARG;
+  if (weight_mode < MTMC_EDGE_W_ONE || weight_mode > MTMC_EDGE_W_BALANCED || (weight_mode == MTMC_EDGE_W_GIVEN && !weight))
+    return MTMC_E_ARG;
+  if ((n_classes == 2 && ((uintptr_t)logits & 7)) || ((uintptr_t)scratch & 7)) return MTMC_E_ARG;
+  const size_t need = mtmc_edge_loss_scratch_bytes(n_steps);
+  if (scratch_bytes < need) return MTMC_E_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(scratch, 0, need, s) != hipSuccess) return MTMC_E_HIP;
+  double* acc = static_cast<double*>(scratch);
+  if (n > 0) {
+    const dim3 grid = mtmc::el_grid(n, n_steps, 512);
+    if (n_classes == 2)
+      hipLaunchKernelGGL(mtmc::el_forward_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, acc);
+    else
+      hipLaunchKernelGGL(mtmc::el_forward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, acc);
+  }
+  hipLaunchKernelGGL(mtmc::el_finalize_kernel, dim3(1), dim3(64), 0, s, acc, n_steps, n_classes, weight_mode, weight,
+                     fpr_alpha, record, out, reinterpret_cast<long long*>(confusion));
+  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+}
+
+int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                                const float* grad, const double* record, float* d_logits, void* stream) {
+  if (!logits || !labels || !grad || !record || !d_logits || n < 0 || n_steps < 1) return MTMC_E_ARG;
+  if (n_classes != 1 && n_classes != 2) return MTMC_E_ARG;
+  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7))) return MTMC_E_ARG;
+  if (n > 0) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
+    if (n_classes == 2)
+      hipLaunchKernelGGL(mtmc::el_backward_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, record, d_logits);
+    else
+      hipLaunchKernelGGL(mtmc::el_backward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, record, d_logits);
+  }
   return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
 }
 

@@ -488,6 +488,11 @@ __global__ __launch_bounds__(256) void bwd_edge_enc_kernel(BwdEncParams p) {
 #pragma unroll
   for (int i = 0; i < NV; ++i) acc[i] = 0;
   const int fe = p.enc.fe;
+  // dW1 = sum_e dza (x) a is summed against the CENTRED attributes: sum_e dza = 0 in exact arithmetic (BatchNorm backward),
+  // so the mean's share is 0 -- but in fp32 that sum leaves a residual (the layer-1 bias gradient, ~1e-6), and raw
+  // attributes carry it into dW1 times their mean (distances: mean 11.5, deviation 0.18 on a three-camera graph, where the
+  // gradient itself is what remains after the batch terms cancel: 8e-6 on a |grad|max of 2e-3)
+  const double ma0 = sc[0] / p.e_total, ma1 = sc[1] / p.e_total;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < p.n_edges; e += nthreads) {
     float a0, a1, za[4], u[4], zb[4], e0[4], zha[4], zhb[4];
@@ -546,8 +551,8 @@ __global__ __launch_bounds__(256) void bwd_edge_enc_kernel(BwdEncParams p) {
     for (int k = 0; k < 4; ++k) {
       dza[k] = wl.g1[k] * sh.ia[k] * (ga[k] - sh.mga[k] - zha[k] * sh.mgza[k]);
       acc[8 + k] += dza[k];
-      acc[k * 2] += (double)dza[k] * a0;
-      acc[k * 2 + 1] += (double)dza[k] * a1;
+      acc[k * 2] += (double)dza[k] * ((double)a0 - ma0);
+      acc[k * 2 + 1] += (double)dza[k] * ((double)a1 - ma1);
     }
     if (p.d_attr) {
       float s0 = 0.f, s1 = 0.f;

@@ -7,11 +7,15 @@
       edge logits, forward and backward fused (the training callers' loss, reference train.py:88-93, :109-142)
   edge_confusion                             TP / FP / TN / FN of argmax(logits) against the edge labels in one pass,
       without the device synchronisations of boolean-mask indexing (reference train.py:98-107, inference.py:20-67)
+  edge_loss                                  everything the training / validation loops' `compute_loss_acc` returns
+      (reference train.py:36-245: balanced CE or one-logit BCE, FPR term, per-class losses and probabilities, confusion
+      counts) for every classified step in one pass, with a fused backward and no host read
 
 All of them run HIP kernels through the C ABI; CPU tensors are refused.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -211,3 +215,89 @@ def edge_confusion(logits, labels):
         _lib.check(_lib.load().mtmc_edge_confusion(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(),
                                                    _stream(x.device)))
     return out
+
+
+EdgeLoss = collections.namedtuple("EdgeLoss", ["loss", "class_loss", "class_prob", "confusion", "fpr", "class_weight"])
+
+
+class _EdgeLoss(torch.autograd.Function):
+    """Consecutive [E, C] slices of one logits block, C in {1, 2}: 3 launches forward (memset, pass, finalize), 1 backward."""
+
+    @staticmethod
+    def forward(ctx, target, weight, mode, fpr_alpha, *steps):
+        n, c = steps[0].shape
+        s = len(steps)
+        dev = steps[0].device
+        lib = _lib.load()
+        nbytes = lib.mtmc_edge_loss_scratch_bytes(s)
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        record = torch.empty(_lib.EDGE_LOSS_RECORD, dtype=torch.float64, device=dev)
+        out = torch.empty(3 + 5 * s, dtype=torch.float32, device=dev)
+        confusion = torch.empty((s, 4), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mtmc_edge_loss_forward(
+                steps[0].data_ptr(), target.data_ptr(), n, c, s, mode, weight.data_ptr() if weight is not None else None,
+                fpr_alpha, scratch.data_ptr(), nbytes, record.data_ptr(), out.data_ptr(), confusion.data_ptr(), _stream(dev)))
+        ctx.save_for_backward(target, record, *steps)
+        r = (out[0], out[3:3 + 2 * s].view(s, 2), out[3 + 2 * s:3 + 4 * s].view(s, 2), confusion, out[3 + 4 * s:], out[1:3])
+        ctx.mark_non_differentiable(*r[1:])
+        return r
+
+    @staticmethod
+    def backward(ctx, grad, *_unused):
+        target, record, *steps = ctx.saved_tensors
+        n, c = steps[0].shape
+        dev = steps[0].device
+        d = torch.empty((len(steps), n, c), dtype=torch.float32, device=dev)
+        g = grad.contiguous().float()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().mtmc_edge_loss_backward(
+                steps[0].data_ptr(), target.data_ptr(), n, c, len(steps), g.data_ptr(), record.data_ptr(), d.data_ptr(),
+                _stream(dev)))
+        return (None, None, None, None) + tuple(d[i] for i in range(len(steps)))
+
+
+def edge_loss(steps, labels, weight=None, pos_weight=None, fpr_alpha: float = 0.0):
+    """The training / validation loops' `compute_loss_acc` (reference train.py:36-245) over `outputs['classified_edges']`
+    in one pass over the logits block, without a host read (it can sit inside `capture_training_step`):
+
+      C = 2 (CE / CE_weighted):  loss = sum_s F.cross_entropy(step_s, labels, weight) + fpr_alpha * sum_s FPR_s
+          `weight`: None, a [2] tensor, or "balanced" = (1, n0/n1) from the label counts of this call (train.py:124-130)
+      C = 1 (BCE / BCE_weighted): loss = sum_s F.binary_cross_entropy_with_logits(step_s[:, 0], labels, pos_weight=pw)
+          + fpr_alpha * sum_s FPR_s;  `pos_weight`: None, a number, a one-element tensor, or "balanced" = n0/n1
+
+    "balanced" with an empty class falls back to (1, 1) (the reference divides by zero there).  `labels` [E]: int64 or the
+    float 0/1 tensor the reference keeps; rows labelled neither 0 nor 1 count for nothing.  Returns the named tuple
+    EdgeLoss(loss, class_loss [S,2], class_prob [S,2], confusion [S,4] = TP FP TN FN, fpr [S], class_weight [2]); only
+    `loss` is differentiable (the FPR term has no gradient, as in the reference).  Steps that are the consecutive slices
+    of one block (what a forward of this package returns) are used in place; any other list is stacked first."""
+    steps = list(steps)
+    if not steps:
+        raise ValueError("edge_loss: no classified steps")
+    s0 = steps[0]
+    if s0.dim() != 2 or s0.dtype != torch.float32 or s0.shape[1] not in (1, 2) or labels.shape != s0.shape[:1] \
+            or any(t.shape != s0.shape or t.dtype != s0.dtype or t.device != s0.device for t in steps):
+        raise NotImplementedError("mtmc_mpn.edge_loss: steps must be float32 [E, 1] or [E, 2] tensors of one shape, labels [E]")
+    c = s0.shape[1]
+    given, other, name = (weight, pos_weight, "weight") if c == 2 else (pos_weight, weight, "pos_weight")
+    if other is not None:
+        raise ValueError(f"mtmc_mpn.edge_loss: [E, {c}] logits take `{name}`, not `{'pos_weight' if c == 2 else 'weight'}`")
+    if isinstance(given, str) and given != "balanced":
+        raise ValueError(f"mtmc_mpn.edge_loss: {name} must be None, a tensor or 'balanced', got {given!r}")
+    if not (s0.is_cuda and labels.is_cuda):
+        raise RuntimeError("mtmc_mpn.edge_loss: tensors must be on a ROCm GPU (no CPU path)")
+    if given is None:
+        mode = _lib.EDGE_W_ONE
+    elif isinstance(given, str):
+        mode, given = _lib.EDGE_W_BALANCED, None
+    else:
+        mode = _lib.EDGE_W_GIVEN
+        if not isinstance(given, torch.Tensor):
+            given = torch.full((1,), float(given), dtype=torch.float32, device=s0.device)    # (a fill: capture-safe)
+        given = given.detach().to(device=s0.device, dtype=torch.float32).contiguous().view(-1)
+        if given.numel() != (2 if c == 2 else 1):
+            raise ValueError(f"mtmc_mpn.edge_loss: {name} must have {2 if c == 2 else 1} element(s)")
+    block = all(t.is_contiguous() and t.data_ptr() == s0.data_ptr() + i * s0.numel() * 4 for i, t in enumerate(steps))
+    if not block:
+        steps = list(torch.stack(steps).unbind(0))           # autograd reaches the pieces through the stack
+    return EdgeLoss(*_EdgeLoss.apply(labels.contiguous().long(), given, mode, float(fpr_alpha), *steps))

@@ -376,6 +376,41 @@ int32_t mtmc_cross_entropy_steps_backward(const float* logits, const int64_t* la
 int32_t mtmc_edge_confusion(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int64_t* counts,
                             void* stream);
 
+/* ---- loss and metrics of the training / validation loops in one pass: everything compute_loss_acc returns (reference
+ * train.py:36-245) for every classified step, without a host read.  logits = the contiguous [n_steps][n][n_classes] block
+ * of one forward, n_classes 1 (one logit x, the BCE / BCE_weighted losses) or 2 (CE / CE_weighted); labels [n] shared by
+ * the steps; rows whose label is neither 0 nor 1 count for nothing anywhere.  n0 / n1 = the numbers of label-0 / label-1
+ * rows.  With z = the margin of the true class (x[y] - x[1-y]; for one logit x if y = 1, -x if y = 0):
+ *   row loss l = softplus(-z) (= logsumexp(x) - x[y], resp. the BCE-with-logits term), true-class probability = sigmoid(z);
+ *   prediction = (argmax == 1), first maximum on ties, resp. x >= 0.
+ * forward: one memset of `scratch`, ONE launch over all steps (fp64 sums L0 L1 P0 P1 and the integer counts TP FP TN FN
+ * per step, in MTMC_STAT_REPLICAS replicas), one single-workgroup finalize that writes
+ *   record [MTMC_EDGE_LOSS_RECORD] f64 : w0, w1, the denominator D, n0 + n1   (what the backward reads)
+ *   out    [3 + 5*n_steps] f32         : loss | w0 w1 | class_loss [n_steps][2] | class_prob [n_steps][2] | fpr [n_steps]
+ *   confusion [n_steps][4] int64       : TP, FP, TN, FN
+ * weight_mode MTMC_EDGE_W_ONE: (w0, w1) = (1, 1); _GIVEN: weight[0..1] (n_classes 2) resp. (1, weight[0]) (one logit: the
+ * pos_weight); _BALANCED: (1, n0/n1), the reference's w_0b/w_0b, w_1b/w_0b (train.py:127-130) -- (1, 1) if either class is
+ * empty, where the reference divides by zero.
+ *   loss = sum_s (w0 L0_s + w1 L1_s) / D + fpr_alpha * sum_s fpr_s,  D = w0 n0 + w1 n1 (n_classes 2: torch's weighted-mean
+ *   cross entropy per step) resp. n0 + n1 (one logit: BCEWithLogitsLoss with pos_weight w1, reduction 'mean');
+ *   fpr_s = FP_s / (FP_s + TN_s), 0 without label-0 rows (the reference's FPR term, train.py:194-195);
+ *   class_loss = L_c / n_c (0 where the class is empty), class_prob = P_c / n_c (0.5 where empty: the reference's filler,
+ *   train.py:378-385).  Without any counted row the loss is 0/0 = NaN, as in torch.
+ * backward: one launch, d_logits [n_steps][n][n_classes] = grad[0] * w[y] / D * d l / d x (softmax(x) - onehot(y), resp.
+ * (1-y) sigmoid(x) - y (1 - sigmoid(x))), 0 on skipped rows; w and D are read from `record` on the device.  The FPR term
+ * has no gradient (none in the reference either).
+ * All pointers are device pointers; nothing is allocated or synchronised.  MTMC_E_ARG: n_classes outside {1, 2},
+ * n_steps < 1, n < 0, an unknown weight_mode, a NULL pointer (weight only with _GIVEN), a two-class block (logits,
+ * d_logits) that is not 8-byte aligned, scratch_bytes short of the query's answer. */
+enum { MTMC_EDGE_W_ONE = 0, MTMC_EDGE_W_GIVEN = 1, MTMC_EDGE_W_BALANCED = 2 };
+#define MTMC_EDGE_LOSS_RECORD 4
+size_t mtmc_edge_loss_scratch_bytes(int32_t n_steps);
+int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                               int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
+                               size_t scratch_bytes, double* record, float* out, int64_t* confusion, void* stream);
+int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                                const float* grad, const double* record, float* d_logits, void* stream);
+
 /* ---- post-processing of the last logits (replaces reference inference.py:475-489, post_processing
  * inference.py:70-169 and utils.py compute_SCC_and_Clusters :30-52, splitting :54-123, remove_edges_single_direction
  * :125-142, pruning :144-339) ----
