@@ -79,6 +79,8 @@ ROUND_BLOCK = STAT_REPLICAS * (Z1_STRIDE + M_STRIDE + Z2_STRIDE)
 F_DETERMINISTIC, F_GLOBAL_DEG, F_FORK, F_SEED_ON_DEVICE = 1, 4, 2, 16
 EDGE_W_ONE, EDGE_W_GIVEN, EDGE_W_BALANCED = range(3)      # mtmc_edge_loss_forward: weight_mode
 EDGE_LOSS_RECORD = 4
+CLUSTER_SCORES, CLUSTER_COUNTS, EDGE_PRF = 9, 7, 5        # mtmc_cluster_scores: scores / counts; mtmc_edge_prf: out
+CLUSTER_SCORES_MAX_N = 1048576
 
 # MTMC_MPN_LIB: another build of the same ABI (same-box A/B of two library versions, tools/lib_ab.sh); default: the in-tree build
 LIB_PATH = os.environ.get("MTMC_MPN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmtmc_mpn.so")
@@ -90,7 +92,8 @@ EXPORTS = ["mtmc_mpn_abi_version", "mtmc_mpn_last_error", "mtmc_mpn_workspace_by
            "mtmc_cross_entropy_steps_forward", "mtmc_cross_entropy_steps_backward", "mtmc_mpn_backward_steps", "mtmc_mpn_backward_flat", "mtmc_mpn_grad_layout", "mtmc_linear_raw", "mtmc_edge_confusion",
            "mtmc_linear_presplit_raw", "mtmc_linear_staged_raw", "mtmc_linear_few_raw", "mtmc_mpn_weight_cache_bytes",
            "mtmc_graph_backward_workspace_bytes", "mtmc_build_graph_backward",
-           "mtmc_edge_loss_scratch_bytes", "mtmc_edge_loss_forward", "mtmc_edge_loss_backward"]
+           "mtmc_edge_loss_scratch_bytes", "mtmc_edge_loss_forward", "mtmc_edge_loss_backward",
+           "mtmc_cluster_scores_workspace_bytes", "mtmc_cluster_scores", "mtmc_edge_prf"]
 
 _lib = None
 
@@ -174,6 +177,13 @@ def load() -> C.CDLL:
     lib.mtmc_edge_loss_backward.restype = C.c_int32
     lib.mtmc_edge_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+    lib.mtmc_cluster_scores_workspace_bytes.restype = C.c_size_t
+    lib.mtmc_cluster_scores_workspace_bytes.argtypes = [C.c_int64]
+    lib.mtmc_cluster_scores.restype = C.c_int32
+    lib.mtmc_cluster_scores.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mtmc_edge_prf.restype = C.c_int32
+    lib.mtmc_edge_prf.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mtmc_postprocess_workspace_bytes.restype = C.c_size_t
     lib.mtmc_postprocess_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     lib.mtmc_postprocess.restype = C.c_int32

@@ -431,6 +431,43 @@ int32_t mtmc_postprocess(const float* logits, const int64_t* row, const int64_t*
                          float* prob1, int64_t* predictions, int64_t* id_pred, int32_t* info,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- how good a tracking result is (the input_test == 'gt' branch of reference inference.py:501-526) ----
+ * mtmc_cluster_scores replaces the five scikit-learn calls on (ID_GT, ID_pred) at inference.py:509 and :516-519
+ * (adjusted_rand_score, adjusted_mutual_info_score, homogeneity_score, completeness_score, v_measure_score), with
+ * scikit-learn's definitions and special cases, natural logarithms, fp64 throughout.  labels_true / labels_pred: n int64
+ * labels each, element strides stride_true / stride_pred >= 0; the values are arbitrary (negative, not compact, INT64_MIN
+ * and INT64_MAX included) and are not modified.  With a_i / b_j the cluster sizes of either side and n_ij the cell counts:
+ *   scores [MTMC_CLUSTER_SCORES] f64 : ARI, AMI, homogeneity, completeness, V-measure, H_true, H_pred, MI, EMI
+ *   counts [MTMC_CLUSTER_COUNTS] i64 : R, C (clusters of either side), non-empty cells, then the pair confusion
+ *       tp = sum n_ij^2 - n, fp = sum b_j^2 - sum n_ij^2, fn = sum a_i^2 - sum n_ij^2, tn = n (n - 1) - tp - fp - fn
+ *       (ordered pairs of distinct nodes, scikit-learn's pair_confusion_matrix)
+ *   ARI = 1 if fn == fp == 0, else 2 (tp tn - fn fp) / ((tp + fn)(fn + tn) + (tp + fp)(fp + tn)), products in 128 bits;
+ *   MI is clamped at 0; homogeneity = 1 if H_true == 0 else MI / H_true, completeness likewise with H_pred, V their
+ *   harmonic mean (0 if both are 0); AMI = 1 if R == C == 1, else (MI - EMI) / den, den = (H_true + H_pred) / 2 - EMI
+ *   kept at least DBL_EPSILON away from 0 with its sign.  Identical partitions give exactly 1.0 everywhere.
+ * Labels and cells are kept in open-addressing tables of O(n) slots (no R x C table), EMI is summed over pairs of distinct
+ * cluster sizes; the sums are integer (fixed point), so the result does not depend on the order of the insertions.
+ * The workspace (8-byte aligned) is the caller's: at most 256 n + 64 KiB bytes; the size query is host-only and returns 0
+ * for n < 1 or n > 1 048 576, sizes the entry point refuses with MTMC_E_ARG, as it does a NULL pointer, a negative
+ * stride and a workspace short of the query's answer.  One memset and five launches; nothing is allocated or synchronised.
+ *
+ * mtmc_edge_prf replaces compute_P_R_F (inference.py:23-68, called at :511) on the post-processed int64 predictions
+ * (mtmc_edge_confusion takes logits): one pass over predictions [n_edges] and labels [n_edges] (element strides >= 0).
+ *   counts [4] i64 : TP, FP, TN, FN; rows whose label or prediction is neither 0 nor 1 count for nothing
+ *   out    [MTMC_EDGE_PRF] f64 : P = TP / (TP + FP), R = TP / (TP + FN), F = 2 P R / (P + R), each 0 on a zero denominator;
+ *       then the reference's precision_class0 = 100 TN / (TN + FP) and precision_class1 = 100 TP / (TP + FN) (0 without
+ *       a success of that class)
+ * n_edges == 0 is legal (all zeros; the row pointers may be NULL then). */
+#define MTMC_CLUSTER_SCORES 9
+#define MTMC_CLUSTER_COUNTS 7
+#define MTMC_EDGE_PRF 5
+size_t mtmc_cluster_scores_workspace_bytes(int64_t n);
+int32_t mtmc_cluster_scores(const int64_t* labels_true, int64_t stride_true, const int64_t* labels_pred, int64_t stride_pred,
+                            int64_t n, double* scores, int64_t* counts, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int32_t mtmc_edge_prf(const int64_t* predictions, int64_t stride_pred, const int64_t* labels, int64_t stride_labels,
+                      int64_t n_edges, int64_t* counts, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
