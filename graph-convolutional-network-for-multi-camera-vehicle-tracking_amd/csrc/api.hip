@@ -249,8 +249,8 @@ int32_t mtmc_mlp_layer_forward(const mtmc_layer* layer, const float* x, int64_t 
   if (bn) g.stats_out = stats_scratch;
   if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "unsupported layer shape");
   if (bn)
-    mtmc::launch_bn_relu_rows(y, layer->out_dim, rows, layer->out_dim, stats_scratch, layer->gamma, layer->beta, (double)rows, y,
-                              mtmc::kNoDrop, 0, 0, s);
+    mtmc::launch_bn_relu_rows({y, layer->out_dim, rows, layer->out_dim, stats_scratch, layer->gamma, layer->beta, (double)rows, y,
+                               mtmc::kNoDrop, 0}, s);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "mlp layer launch failed: %s", hipGetErrorString(e));
 }

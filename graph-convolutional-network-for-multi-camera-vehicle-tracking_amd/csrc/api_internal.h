@@ -46,14 +46,13 @@ struct Layout {
   // (gemm_presplit.hip), layers >= 1 on the role-split kernel (gemm_staged.hip).  (A call with a weight-plane cache reads that.)
   size_t wh[MTMC_MAX_ENC_LAYERS], inv_w[MTMC_MAX_ENC_LAYERS]; bool w_ws[MTMC_MAX_ENC_LAYERS];
   size_t g_e[2], g_e0, g_h[2], g_h0, g_P, g_Q, g_de2, g_arg;   // gradients wrt e_r, e0, h_r, h0, P, Q; A^T dz2 [E][4]
-  size_t bst;                                  // f64[2L+1][kStatRep][kBwdStride] backward statistics blocks
+  size_t bst;                                  // f64[2L+1][kStatRep][kBwdStride] backward statistics blocks (train_kernels.h)
   size_t bwd_zero, bwd_zero_end;               // the range the backward clears with one memset
   size_t gacc;                                 // f32[kGradRep][kGaccN] (train_kernels.h)
   size_t amax_bwd;                             // u32[2][MTMC_MAX_ENC_LAYERS][kAmaxRep] (zeroed with the backward scratch)
   size_t seed_word = 0;
   size_t gA, gB, tA, tB, tW, tX, zeros, bst_n; // node-encoder backward: gradient ping-pong, transposes, 0-bias, column stats
 };
-constexpr int kBwdStride = 256;                // doubles per replica of the backward statistics scratch
 
 // The weight-plane cache (mtmc_mpn_call::weight_cache; split_body.h): per node-encoder layer the fp16 planes [2][K/32][out][32],
 // the inverse row scales [out] and one 64-bit fingerprint per 8-row chunk.  Depends on the model's dimensions only.
@@ -191,7 +190,7 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
       bn_stats += 2 * (size_t)m->enc_node[l].out_dim;
     }
     lo->bwd_zero = off;
-    lo->bst = take((size_t)(2 * L + 1) * mtmc::kStatRep * kBwdStride * sizeof(double));   // per round: node, edge; + encoder
+    lo->bst = take((size_t)(2 * L + 1) * mtmc::kStatRep * mtmc::kBwdStride * sizeof(double));   // per round: node, edge; + encoder
     lo->bst_n = take(bn_stats * sizeof(double));
     lo->gacc = take((size_t)mtmc::kGradRep * mtmc::kGaccN * sizeof(float));   // small-gradient replicas
     lo->amax_bwd = take((size_t)2 * MTMC_MAX_ENC_LAYERS * mtmc::kAmaxRep * sizeof(uint32_t));   // |dY_l|max, |a_{l-1}|max
@@ -714,10 +713,10 @@ inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
       const int last = m->n_enc_layers - 1;
       const int64_t rows = c->node_hi - c->node_lo;
       if (rows > 0)
-        mtmc::launch_bn_relu_rows(x.at<float>(x.lo.Y[last]), MTMC_NODE_DIM, rows, MTMC_NODE_DIM,
-                                  x.at<double>(x.lo.stat_enc_layer[last]), m->enc_node[last].gamma, m->enc_node[last].beta,
-                                  (double)c->n_nodes, x.at<float>(x.lo.pub.h0_off) + (size_t)c->node_lo * MTMC_NODE_DIM,
-                                  make_drop(x, m->dropout_enc), mtmc::kDropEncNode + last, c->node_lo, s);
+        mtmc::launch_bn_relu_rows({x.at<float>(x.lo.Y[last]), MTMC_NODE_DIM, rows, MTMC_NODE_DIM,
+                                   x.at<double>(x.lo.stat_enc_layer[last]), m->enc_node[last].gamma, m->enc_node[last].beta,
+                                   (double)c->n_nodes, x.at<float>(x.lo.pub.h0_off) + (size_t)c->node_lo * MTMC_NODE_DIM,
+                                   make_drop(x, m->dropout_enc), mtmc::kDropEncNode + last, c->node_lo}, s);
       break;
     }
     case MTMC_PH_ROUND_PROJ: {

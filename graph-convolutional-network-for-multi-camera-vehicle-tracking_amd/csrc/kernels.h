@@ -296,11 +296,18 @@ void launch_node_stat(const NodeStatParams& p, hipStream_t s);
 // few-edge lists (one edge per thread in passes A / B): the node-update statistics come out of node_proj + pass B, no
 // node_stat_kernel launch and no seg[] (RoundParams::fold_z2, NodeProjParams::z2_stats); many-edge lists: seg[] + node_stat
 bool fold_node_stat(int64_t n_edges);
-// h_dst[i][k] = relu(s_k * Y[i][k] + t_k) for local rows; stats over `count` rows
-void launch_bn_relu_rows(const float* Y, int64_t ldy, int64_t rows, int dim, const double* stats, const float* gamma,
-                         const float* beta, double count, float* dst, Drop drop, unsigned drop_stream, int64_t row0,
-                         hipStream_t s, unsigned* amax_out = nullptr,    // amax_out: u32[kAmaxRep] |dst|max (atomicMax) or nullptr
-                         float* dstT = nullptr, int64_t ldt = 0);         // dstT: dst^T [dim][ldt] as well, rows..ldt zero-filled
+// dst[i][k] = relu(s_k * Y[i][k] + t_k) (+ Dropout) for local rows; stats over `count` rows
+struct RowsTJob {
+  const float* Y; int64_t ldy; int64_t rows; int dim;
+  const double* stats; const float* gamma; const float* beta; double count;
+  float* dst; Drop drop; unsigned drop_stream;
+  int64_t row0 = 0;                    // the first row's number in the whole matrix (Dropout's element index)
+  unsigned* amax_out = nullptr;        // u32[kAmaxRep] |dst|max (atomicMax on the bit patterns), or nullptr
+  float* dstT = nullptr; int64_t ldt = 0;   // dst^T [dim][ldt] as well, rows..ldt zero-filled
+};
+// the shapes bn_relu_rows_t_body takes: launch_bn_relu_rows runs it on them, and on them the job can ride in bn_bwd_kernel<1>
+inline bool rows_t_form_takes(const RowsTJob& j) { return j.dstT && j.ldt % 4 == 0 && j.rows > 0 && (j.rows + 15) / 16 <= 65535; }
+void launch_bn_relu_rows(const RowsTJob& j, hipStream_t s);
 // dst = src (sum/max) or src / max(deg,1) (mean)
 void launch_h_final(const float* src, const int* deg, int mean, int64_t n_nodes, float* dst, hipStream_t s);
 

@@ -392,18 +392,16 @@ void launch_node_proj(const NodeProjParams& p, hipStream_t s) {
 void launch_node_stat(const NodeStatParams& p, hipStream_t s) {
   hipLaunchKernelGGL(node_stat_kernel, dim3(cap_grid((p.node_end - p.node_begin + 7) / 8)), dim3(256), 0, s, p);
 }
-void launch_bn_relu_rows(const float* Y, int64_t ldy, int64_t rows, int dim, const double* stats, const float* gamma,
-                         const float* beta, double count, float* dst, Drop drop, unsigned drop_stream, int64_t row0,
-                         hipStream_t s, unsigned* amax_out, float* dstT, int64_t ldt) {
-  if (dstT && ldt % 4 == 0 && rows > 0 && (rows + 15) / 16 <= 65535) {
-    const RowsTJob j = {Y, ldy, rows, dim, stats, gamma, beta, count, dst, drop, drop_stream, row0, amax_out, dstT, ldt};
-    hipLaunchKernelGGL(bn_relu_rows_t_kernel, dim3((dim + 63) / 64, (unsigned)((rows + 15) / 16)), dim3(256), 0, s, j);
+void launch_bn_relu_rows(const RowsTJob& j, hipStream_t s) {
+  if (rows_t_form_takes(j)) {
+    hipLaunchKernelGGL(bn_relu_rows_t_kernel, dim3((j.dim + 63) / 64, (unsigned)((j.rows + 15) / 16)), dim3(256), 0, s, j);
     return;
   }
   // with the |.|max bookkeeping: one workgroup per CU, so that at most 16 of them meet on a word
-  const int64_t blocks = (rows * dim + 255) / 256;
-  hipLaunchKernelGGL(bn_relu_rows_kernel, dim3(amax_out && blocks > 256 ? 256 : cap_grid(blocks)), dim3(256), 0, s, Y, ldy,
-                     rows, dim, stats, gamma, beta, count, dst, drop, drop_stream, row0, amax_out, dstT, ldt);
+  const int64_t blocks = (j.rows * j.dim + 255) / 256;
+  hipLaunchKernelGGL(bn_relu_rows_kernel, dim3(j.amax_out && blocks > 256 ? 256 : cap_grid(blocks)), dim3(256), 0, s, j.Y, j.ldy,
+                     j.rows, j.dim, j.stats, j.gamma, j.beta, j.count, j.dst, j.drop, j.drop_stream, j.row0, j.amax_out, j.dstT,
+                     j.ldt);
 }
 void launch_h_final(const float* src, const int* deg, int mean, int64_t n_nodes, float* dst, hipStream_t s) {
   hipLaunchKernelGGL(h_final_kernel, dim3(cap_grid((n_nodes * kH + 255) / 256)), dim3(256), 0, s, src, deg, mean,

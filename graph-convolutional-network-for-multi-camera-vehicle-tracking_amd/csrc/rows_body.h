@@ -4,15 +4,9 @@
 // are independent).  A thread keeps ONE column: its BatchNorm affine is derived once; the transposed tile leaves through LDS
 // as one 16-byte store per thread.  bx / by / ny: the workgroup's tile and the number of row tiles.
 #pragma once
-#include "common.h"
+#include "kernels.h"
 
 namespace mtmc {
-
-struct RowsTJob {
-  const float* Y; int64_t ldy; int64_t rows; int dim;
-  const double* stats; const float* gamma; const float* beta; double count;
-  float* dst; Drop drop; unsigned drop_stream; int64_t row0; unsigned* amax_out; float* dstT; int64_t ldt;
-};
 
 __device__ __forceinline__ void bn_relu_rows_t_body(const RowsTJob& j, int bx, int by, int ny) {
   __shared__ float tile[16][65];

@@ -17,7 +17,11 @@ constexpr int kGaUnB = 0, kGaUnW = 32, kGaClsW = 160, kGaClsB = kGaClsW + 4 * MT
               kGaW1 = kGaB2 + 4, kGaB1 = kGaW1 + 8, kGaccN = 256;
 static_assert(kGaB1 + 4 <= kGaccN, "gradient scratch row too short");
 
-constexpr int kBwdStrideD = 256;   // doubles per replica of the backward statistics scratch (api_internal.h: kBwdStride)
+constexpr int kBwdStride = 256;    // doubles per replica of the backward statistics scratch (api_internal.h: Layout::bst)
+
+// Where one layer's parameter gradients go: the caller's tensors (weight, bias, BatchNorm gamma, beta; the last two null
+// where the layer has no BatchNorm).  The parameter blocks below carry one per layer they write to.
+struct LayerGrad { float* w; float* b; float* g; float* bt; };
 
 struct BwdRoundParams {
   RoundParams f;             // the forward parameters of this round (tape pointers, weights, statistics, dropout)
@@ -32,18 +36,16 @@ struct BwdRoundParams {
   float* g_e_prev;           // [E][4] out: gradient wrt e_{r-1}
   float* g_e0;               // [E][4] accumulated gradient wrt the encoded edges
   double* bst;               // backward statistics scratch (zeroed by the host before each statistics pass)
-  float* gr_un_w; float* gr_un_b; float* gr_un_g; float* gr_un_bt;
-  float* gr_ue_w; float* gr_ue_b; float* gr_ue_g; float* gr_ue_bt;
-  float* gr_cls_w; float* gr_cls_b;
+  LayerGrad un, ue, cls;     // node update, edge update, classifier
   float* gacc;               // [kGradRep][kGaccN] replicated small-gradient sums (see above)
 };
 
 struct GradFoldParams {
   const float* gacc;
-  float* gr_un_w; float* gr_un_b; int un_ld, un_eoff;
-  float* gr_ue_w; float* gr_ue_b; int ue_ld, ue_eoff, nin;
-  float* gr_cls_w; float* gr_cls_b; int n_classes;
-  float* gr_w1; float* gr_b1; float* gr_w2; float* gr_b2; int fe;
+  LayerGrad un; int un_ld, un_eoff;      // node update
+  LayerGrad ue; int ue_ld, ue_eoff, nin; // edge update
+  LayerGrad cls; int n_classes;
+  LayerGrad l1, l2; int fe;              // the edge encoder's two layers
 };
 
 struct BwdProjParams {
@@ -59,19 +61,19 @@ struct BwdEncParams {
   EdgeEncParams enc; const float* attr; int64_t n_edges; double e_total;
   const float* g_e0; double* bst; float* d_attr;
   float* gacc;               // [kGradRep][kGaccN]: w1, b1, w2, b2 sums
-  float* gr_w1; float* gr_b1; float* gr_g1; float* gr_bt1;
-  float* gr_w2; float* gr_b2; float* gr_g2; float* gr_bt2;
+  LayerGrad l1, l2;
 };
 
 struct BnBwdParams {
   const float* Y; float* dA; int64_t rows; int dim;
   const double* stats_fwd; double* stats_bwd; double count;
   const float* gamma; const float* beta; Drop drop; unsigned drop_stream;
-  float* gr_gamma; float* gr_beta; float* gr_bias;
+  LayerGrad gr;              // (gr.w is the weight-gradient GEMM's output, not this kernel's)
   unsigned* amax_out;        // u32[kAmaxRep] |dY|max (mode 1; atomicMax on the bit patterns), or nullptr
   float* dT; int64_t ldt;    // mode 1: dY^T [dim][ldt] as well (rows..ldt zero-filled): the weight-gradient GEMM's operand
   RowsTJob rc; int rc_on = 0;  // mode 1: the recomputation of the layer's INPUT activation (+ its transpose) rides as the z = 1
-                               // workgroups of the launch (independent of this layer's dY); same rows, 16 per workgroup
+                               // workgroups of the launch (independent of this layer's dY); same rows, 16 per workgroup.
+                               // Only a job that rows_t_form_takes (kernels.h)
 };
 
 void launch_bwd_node_upd(const BwdRoundParams& p, int mode, hipStream_t s);
@@ -83,13 +85,9 @@ void launch_bwd_classify_e0(const EdgeEncParams& enc, const float* attr, int64_t
                             int n_classes, const float* d_logits, float* g_e0, float* gr_cls_w, float* gr_cls_b,
                             hipStream_t s);
 void launch_bn_bwd(const BnBwdParams& p, int mode, hipStream_t s);
-bool bn_bwd_carries_rows_job(int64_t rows, int64_t ldt);      // the shapes bn_relu_rows_t_body takes
-void launch_transpose_pad(const float* src, int64_t rows, int cols, int64_t ld_src, float* dst, int64_t rows_pad,
-                          hipStream_t s);
 // what the backward accumulates into, cleared by ONE launch: the gaps between the node encoder's weight gradients in the caller's
 // flat gradient buffer (those are plain GEMM outputs) and the workspace's zero range (two memsets, 10.8 MB of them needless, before)
 struct ZeroRanges { int n = 0; struct { uint4* p; size_t n16; } r[MTMC_MAX_ENC_LAYERS + 3]; };
-void launch_zero_ranges(const ZeroRanges& z, hipStream_t s);
 // several padded transposes in one launch (x^T and every W_l^T of the node encoder's backward)
 struct TransposeJob { const float* src; float* dst; int64_t rows, ld_src, rows_pad; int cols; unsigned blocks_r, first_block; };
 struct TransposeJobs { int n = 0; unsigned n_blocks = 0; TransposeJob job[MTMC_MAX_ENC_LAYERS + 1]; };

@@ -62,6 +62,15 @@ __device__ __forceinline__ void mean_istd(double sum, double sumsq, double count
   istd = (float)r;
 }
 
+// Block sum of NV per-thread fp64 values (256 threads): thread i < NV gets the sum of value i, the others 0.  red: 256 doubles.
+template <int NV>
+__device__ __forceinline__ double block_sums_f64(const double (&acc)[NV], double* red) {
+  wave_sums_f64<NV>(acc, red + (threadIdx.x >> 6) * 64);      // (5 instructions per value instead of 18: common.h)
+  __syncthreads();
+  const int i = threadIdx.x;
+  return i < NV ? red[i] + red[64 + i] + red[128 + i] + red[192 + i] : 0.0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // node-update MLP: statistics (mode 0) and apply (mode 1); lanes = channels as in pass_c_kernel.
 // Max aggregation routes a node's gradient to ONE edge per channel, the arg max (torch_scatter.scatter_max
@@ -80,7 +89,7 @@ __global__ __launch_bounds__(256) void bwd_node_upd_kernel(BwdRoundParams p) {
   __shared__ float4 a_all[32];
   const int k = threadIdx.x & 31, hw = threadIdx.x >> 5;
   stat_gather2(p.f.stats + kRoundMOff + 4, 10, kMStride, p.f.stats + kRoundZ2Off, 64, kZ2Stride, st);
-  if (MODE == 1) stat_gather(p.bst, 64, kBwdStrideD, st + 74);
+  if (MODE == 1) stat_gather(p.bst, 64, kBwdStride, st + 74);
   __syncthreads();
   const float* aw = p.f.un_w + k * p.f.un_ld + p.f.un_eoff;
   float a4[4];
@@ -183,7 +192,7 @@ __global__ __launch_bounds__(256) void bwd_node_upd_kernel(BwdRoundParams p) {
       double s = 0;
       for (int h = 0; h < 8; ++h) s += red[(i * 8 + h) * 32 + k];
       if (MODE == 0) {
-        unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStrideD + i * 32 + k, s);
+        unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStride + i * 32 + k, s);
       } else if (i == 0) {
         gacc_add(p.gacc, kGaUnB + k, (float)s);
       } else {
@@ -191,8 +200,8 @@ __global__ __launch_bounds__(256) void bwd_node_upd_kernel(BwdRoundParams p) {
       }
     }
     if (MODE == 1 && blockIdx.x == 0) {      // dgamma = sum g*zh, dbeta = sum g (the statistics of mode 0)
-      p.gr_un_g[k] += (float)st[74 + 32 + k];     // += : the update MLPs are shared by all rounds
-      p.gr_un_bt[k] += (float)st[74 + k];
+      p.un.g[k] += (float)st[74 + 32 + k];        // += : the update MLPs are shared by all rounds
+      p.un.bt[k] += (float)st[74 + k];
     }
   }
 }
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(256) void bwd_edge_upd_kernel(BwdRoundParams p) {
   __shared__ double red[64 * 4];
   __shared__ EdgeWeightsLds wl;
   stat_gather(p.f.stats + kRoundZ1Off, 8, kZ1Stride, red);
-  if (MODE == 1) stat_gather(p.bst, 8, kBwdStrideD, red + 8);
+  if (MODE == 1) stat_gather(p.bst, 8, kBwdStride, red + 8);
   edge_weights_to_lds(p.f.enc, &p.f, &wl);
   const EdgeEncParams enc = enc_from_lds(p.f.enc, &wl);
   const bool need_e0 = MODE == 1 && (p.f.first_round || p.f.reattach_edges);
@@ -344,14 +353,11 @@ __global__ __launch_bounds__(256) void bwd_edge_upd_kernel(BwdRoundParams p) {
       }
     }
   }
-  // block reduction of NV doubles
-  wave_sums_f64<NV>(acc, red + (threadIdx.x >> 6) * 64);      // (5 instructions per value instead of 18: common.h)
-  __syncthreads();
+  const double s = block_sums_f64<NV>(acc, red);
   if (threadIdx.x < NV) {
     const int i = threadIdx.x;
-    const double s = red[i] + red[64 + i] + red[128 + i] + red[192 + i];
     if (MODE == 0) {
-      if (i < 8) unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStrideD + i, s);
+      if (i < 8) unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStride + i, s);
       else if (i < 24) { if ((i - 8) / 4 < C) gacc_add(p.gacc, kGaClsW + (i - 8), (float)s); }
       else if (i - 24 < C) gacc_add(p.gacc, kGaClsB + (i - 24), (float)s);
     } else {
@@ -363,8 +369,8 @@ __global__ __launch_bounds__(256) void bwd_edge_upd_kernel(BwdRoundParams p) {
     }
   }
   if (MODE == 1 && blockIdx.x == 0 && threadIdx.x < 4) {
-    p.gr_ue_g[threadIdx.x] += (float)sh.sum_gz[threadIdx.x];   // += : shared by all rounds
-    p.gr_ue_bt[threadIdx.x] += (float)sh.sum_g[threadIdx.x];
+    p.ue.g[threadIdx.x] += (float)sh.sum_gz[threadIdx.x];      // += : shared by all rounds
+    p.ue.bt[threadIdx.x] += (float)sh.sum_g[threadIdx.x];
   }
 }
 
@@ -467,8 +473,8 @@ __global__ __launch_bounds__(256) void bwd_edge_enc_kernel(BwdEncParams p) {
   __shared__ EdgeWeightsLds wl;
   edge_weights_to_lds(p.enc, nullptr, &wl);                       // (the first barrier below publishes it)
   edge_enc_affine_to_smem(p.enc, p.e_total, 2, &af, sc);          // also leaves the summed moments in sc
-  if (PASS >= 1) stat_gather(p.bst, 8, kBwdStrideD, sc + kStatAttr + kStatEnc2);
-  if (PASS >= 2) stat_gather(p.bst + 8, 8, kBwdStrideD, sc + kStatAttr + kStatEnc2 + 8);
+  if (PASS >= 1) stat_gather(p.bst, 8, kBwdStride, sc + kStatAttr + kStatEnc2);
+  if (PASS >= 2) stat_gather(p.bst + 8, 8, kBwdStride, sc + kStatAttr + kStatEnc2 + 8);
   __syncthreads();
   if (threadIdx.x < 4) {
     const int k = threadIdx.x;
@@ -563,14 +569,12 @@ __global__ __launch_bounds__(256) void bwd_edge_enc_kernel(BwdEncParams p) {
     }
     (void)za; (void)zb;
   }
-  wave_sums_f64<NV>(acc, red + (threadIdx.x >> 6) * 64);      // (5 instructions per value instead of 18: common.h)
-  __syncthreads();
+  const double s = block_sums_f64<NV>(acc, red);
   if (threadIdx.x < NV) {
     const int i = threadIdx.x;
-    const double s = red[i] + red[64 + i] + red[128 + i] + red[192 + i];
-    if (PASS == 0) unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStrideD + i, s);
+    if (PASS == 0) unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStride + i, s);
     else if (PASS == 1) {
-      if (i < 8) unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStrideD + 8 + i, s);
+      if (i < 8) unsafeAtomicAdd(p.bst + (blockIdx.x % kStatRep) * kBwdStride + 8 + i, s);
       else if (i < 24) gacc_add(p.gacc, kGaW2 + (i - 8), (float)s);
       else gacc_add(p.gacc, kGaB2 + (i - 24), (float)s);
     } else {
@@ -580,8 +584,8 @@ __global__ __launch_bounds__(256) void bwd_edge_enc_kernel(BwdEncParams p) {
   }
   if (blockIdx.x == 0 && threadIdx.x < 4) {
     const int k = threadIdx.x;
-    if (PASS == 1) { p.gr_g2[k] = (float)sh.sums[4 + k]; p.gr_bt2[k] = (float)sh.sums[k]; }
-    if (PASS == 2) { p.gr_g1[k] = (float)sh.sums[12 + k]; p.gr_bt1[k] = (float)sh.sums[8 + k]; }
+    if (PASS == 1) { p.l2.g[k] = (float)sh.sums[4 + k]; p.l2.bt[k] = (float)sh.sums[k]; }
+    if (PASS == 2) { p.l1.g[k] = (float)sh.sums[12 + k]; p.l1.bt[k] = (float)sh.sums[8 + k]; }
   }
 }
 
@@ -655,7 +659,7 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(BnBwdParams p) {
       const double* q = red + which * 256 + (threadIdx.x & 63);
       const double s = q[0] + q[64] + q[128] + q[192];
       if (MODE == 0) unsafeAtomicAdd(p.stats_bwd + which * p.dim + c, s);
-      else if (which == 0) unsafeAtomicAdd(p.gr_bias + c, (float)s);
+      else if (which == 0) unsafeAtomicAdd(p.gr.b + c, (float)s);
     }
   }
   if (MODE == 1 && p.amax_out) {                   // operand scale of the weight- / input-gradient GEMMs
@@ -668,33 +672,14 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(BnBwdParams p) {
       amax_publish(p.amax_out + (blockIdx.x + blockIdx.y) % kAmaxRep, fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])));
   }
   if (MODE == 1 && blockIdx.y == 0 && threadIdx.x < 64 && col < p.dim) {
-    p.gr_gamma[col] = (float)p.stats_bwd[p.dim + col];
-    p.gr_beta[col] = (float)p.stats_bwd[col];
+    p.gr.g[col] = (float)p.stats_bwd[p.dim + col];
+    p.gr.bt[col] = (float)p.stats_bwd[col];
   }
 }
 
-// dst[c][r] = src[r][c] for r < rows, 0 for rows <= r < rows_pad   (dst leading dimension rows_pad)
-__global__ __launch_bounds__(256) void transpose_pad_kernel(const float* src, int64_t rows, int cols, int64_t ld_src,
-                                                            float* dst, int64_t rows_pad) {
-  __shared__ float tile[32][33];
-  const int64_t r0 = (int64_t)blockIdx.x * 32;
-  const int c0 = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8) {
-    const int64_t r = r0 + i;
-    const int c = c0 + tx;
-    tile[i][tx] = (r < rows && c < cols) ? src[r * ld_src + c] : 0.f;
-  }
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8) {
-    const int c = c0 + i;
-    const int64_t r = r0 + tx;
-    if (c < cols && r < rows_pad) dst[(int64_t)c * rows_pad + r] = tile[tx][i];
-  }
-}
-
-// The same for several matrices in ONE launch (the node encoder's backward needs x^T and every W_l^T, all of them known before
-// its first kernel: four 5 us launches on the chain become one).  1-D grid; a block finds its matrix by the block prefix.
+// dst[c][r] = src[r][c] for r < rows, 0 for rows <= r < rows_pad (dst leading dimension rows_pad), for several matrices in ONE
+// launch (the node encoder's backward needs x^T and every W_l^T, all of them known before its first kernel: four 5 us launches
+// on the chain become one).  1-D grid; a block finds its matrix by the block prefix.
 __device__ __forceinline__ void transpose_job_body(const TransposeJobs& p, unsigned block) {
   __shared__ float tile[32][33];
   int j = 0;
@@ -729,16 +714,16 @@ __global__ __launch_bounds__(256) void grad_fold_kernel(GradFoldParams p) {
 #pragma unroll
   for (int r = 0; r < kGradRep; ++r) s += p.gacc[r * kGaccN + i];
   float* dst = nullptr;
-  if (i < kGaUnW) dst = p.gr_un_b + i;
-  else if (i < kGaClsW) dst = p.gr_un_w + ((i - kGaUnW) >> 2) * p.un_ld + p.un_eoff + ((i - kGaUnW) & 3);
-  else if (i < kGaClsB) { if ((i - kGaClsW) / 4 < p.n_classes) dst = p.gr_cls_w + (i - kGaClsW); }
-  else if (i < kGaUeB) { if (i - kGaClsB < p.n_classes) dst = p.gr_cls_b + (i - kGaClsB); }
-  else if (i < kGaUeW) dst = p.gr_ue_b + (i - kGaUeB);
-  else if (i < kGaW2) { const int kk = (i - kGaUeW) >> 3, j = (i - kGaUeW) & 7; if (j < p.nin) dst = p.gr_ue_w + kk * p.ue_ld + p.ue_eoff + j; }
-  else if (i < kGaB2) dst = p.gr_w2 + (i - kGaW2);
-  else if (i < kGaW1) dst = p.gr_b2 + (i - kGaB2);
-  else if (i < kGaB1) { const int q = i - kGaW1; if ((q & 1) < p.fe) dst = p.gr_w1 + (q >> 1) * p.fe + (q & 1); }
-  else if (i < kGaB1 + 4) dst = p.gr_b1 + (i - kGaB1);
+  if (i < kGaUnW) dst = p.un.b + i;
+  else if (i < kGaClsW) dst = p.un.w + ((i - kGaUnW) >> 2) * p.un_ld + p.un_eoff + ((i - kGaUnW) & 3);
+  else if (i < kGaClsB) { if ((i - kGaClsW) / 4 < p.n_classes) dst = p.cls.w + (i - kGaClsW); }
+  else if (i < kGaUeB) { if (i - kGaClsB < p.n_classes) dst = p.cls.b + (i - kGaClsB); }
+  else if (i < kGaUeW) dst = p.ue.b + (i - kGaUeB);
+  else if (i < kGaW2) { const int kk = (i - kGaUeW) >> 3, j = (i - kGaUeW) & 7; if (j < p.nin) dst = p.ue.w + kk * p.ue_ld + p.ue_eoff + j; }
+  else if (i < kGaB2) dst = p.l2.w + (i - kGaW2);
+  else if (i < kGaW1) dst = p.l2.b + (i - kGaB2);
+  else if (i < kGaB1) { const int q = i - kGaW1; if ((q & 1) < p.fe) dst = p.l1.w + (q >> 1) * p.fe + (q & 1); }
+  else if (i < kGaB1 + 4) dst = p.l1.b + (i - kGaB1);
   if (dst) *dst += s;
 }
 void launch_grad_fold(const GradFoldParams& p, hipStream_t s) {
@@ -796,11 +781,9 @@ __global__ __launch_bounds__(256) void bwd_classify_e0_kernel(EdgeEncParams enc,
     }
     reinterpret_cast<float4*>(g_e0)[e] = make_float4(de[0], de[1], de[2], de[3]);
   }
-  wave_sums_f64<NV>(acc, red + (threadIdx.x >> 6) * 64);      // (5 instructions per value instead of 18: common.h)
-  __syncthreads();
+  const double s = block_sums_f64<NV>(acc, red);
   if (threadIdx.x < NV) {
     const int i = threadIdx.x;
-    const double s = red[i] + red[64 + i] + red[128 + i] + red[192 + i];
     if (i < 4 * MTMC_MAX_CLASSES) { if (i / 4 < n_classes) unsafeAtomicAdd(gr_cls_w + i, (float)s); }
     else if (i - 4 * MTMC_MAX_CLASSES < n_classes) unsafeAtomicAdd(gr_cls_b + (i - 4 * MTMC_MAX_CLASSES), (float)s);
   }
@@ -829,18 +812,7 @@ void launch_bn_bwd(const BnBwdParams& p, int mode, hipStream_t s) {
   }
   hipLaunchKernelGGL(bn_bwd_kernel<1>, grid, dim3(256), 0, s, p);
 }
-bool bn_bwd_carries_rows_job(int64_t rows, int64_t ldt) { return ldt % 4 == 0 && rows > 0 && (rows + 15) / 16 <= 65535; }
-void launch_transpose_pad(const float* src, int64_t rows, int cols, int64_t ld_src, float* dst, int64_t rows_pad,
-                          hipStream_t s) {
-  hipLaunchKernelGGL(transpose_pad_kernel, dim3((unsigned)((rows_pad + 31) / 32), (cols + 31) / 32), dim3(256), 0, s,
-                     src, rows, cols, ld_src, dst, rows_pad);
-}
 
-__global__ __launch_bounds__(256) void zero_ranges_kernel(ZeroRanges z) {
-  const size_t nthreads = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int j = 0; j < z.n; ++j)
-    for (size_t i = t0; i < z.r[j].n16; i += nthreads) z.r[j].p[i] = make_uint4(0u, 0u, 0u, 0u);
-}
 // The backward's first launch: what it accumulates into is cleared by the first n_zero workgroups, x^T and every W_l^T (which
 // depend on nothing the backward computes) are made by the rest.
 __global__ __launch_bounds__(256) void bwd_begin_kernel(ZeroRanges z, TransposeJobs t, unsigned n_zero) {
@@ -859,13 +831,6 @@ void launch_bwd_begin(const ZeroRanges& z, const TransposeJobs& t, hipStream_t s
   const unsigned nz = (unsigned)(blocks > 2048 ? 2048 : blocks);
   if (nz + t.n_blocks == 0) return;
   hipLaunchKernelGGL(bwd_begin_kernel, dim3(nz + t.n_blocks), dim3(256), 0, s, z, t, nz);
-}
-void launch_zero_ranges(const ZeroRanges& z, hipStream_t s) {
-  size_t total = 0;
-  for (int j = 0; j < z.n; ++j) total += z.r[j].n16;
-  if (total == 0) return;
-  const size_t blocks = (total + 1023) / 1024;                     // four 16-byte stores per thread
-  hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, z);
 }
 
 void transpose_jobs_add(TransposeJobs& p, const float* src, int64_t rows, int cols, int64_t ld_src, float* dst, int64_t rows_pad) {
