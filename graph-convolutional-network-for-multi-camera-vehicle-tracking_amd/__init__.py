@@ -10,6 +10,8 @@ Public surface = the reference's interface for the hot path (reference models/mp
 from .config import DEFAULT_ARCH, DEFAULT_GRAPH_NET_PARAMS, default_params  # noqa: F401
 from .graph_build import build_graph  # noqa: F401
 from .postprocess import postprocess  # noqa: F401
+from . import pool  # noqa: F401
+from .pool import pool_tracklets  # noqa: F401
 from . import ops  # noqa: F401
 from .ops import cross_entropy, cross_entropy_steps, edge_loss  # noqa: F401
 from . import metrics  # noqa: F401
@@ -20,4 +22,4 @@ from .modules import (MLP, EdgeModel, MetaLayer, MLPGraphIndependent, MOTMPNet, 
 
 __all__ = ["MOTMPNet", "MetaLayer", "EdgeModel", "NodeModel", "MLPGraphIndependent", "MLP",
            "DEFAULT_GRAPH_NET_PARAMS", "DEFAULT_ARCH", "default_params", "build_graph", "postprocess", "FeatureStore", "cross_entropy", "cross_entropy_steps", "edge_loss", "ops",
-           "metrics", "cluster_scores", "edge_prf", "evaluate", "ClusterScores", "EdgePRF"]
+           "metrics", "cluster_scores", "edge_prf", "evaluate", "ClusterScores", "EdgePRF", "pool", "pool_tracklets"]

@@ -81,6 +81,7 @@ EDGE_W_ONE, EDGE_W_GIVEN, EDGE_W_BALANCED = range(3)      # mtmc_edge_loss_forwa
 EDGE_LOSS_RECORD = 4
 CLUSTER_SCORES, CLUSTER_COUNTS, EDGE_PRF = 9, 7, 5        # mtmc_cluster_scores: scores / counts; mtmc_edge_prf: out
 CLUSTER_SCORES_MAX_N = 1048576
+POOL_INFO = 4                                             # mtmc_pool_tracklets: info words
 
 # MTMC_MPN_LIB: another build of the same ABI (same-box A/B of two library versions, tools/lib_ab.sh); default: the in-tree build
 LIB_PATH = os.environ.get("MTMC_MPN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmtmc_mpn.so")
@@ -93,7 +94,8 @@ EXPORTS = ["mtmc_mpn_abi_version", "mtmc_mpn_last_error", "mtmc_mpn_workspace_by
            "mtmc_linear_presplit_raw", "mtmc_linear_staged_raw", "mtmc_linear_few_raw", "mtmc_mpn_weight_cache_bytes",
            "mtmc_graph_backward_workspace_bytes", "mtmc_build_graph_backward",
            "mtmc_edge_loss_scratch_bytes", "mtmc_edge_loss_forward", "mtmc_edge_loss_backward",
-           "mtmc_cluster_scores_workspace_bytes", "mtmc_cluster_scores", "mtmc_edge_prf"]
+           "mtmc_cluster_scores_workspace_bytes", "mtmc_cluster_scores", "mtmc_edge_prf",
+           "mtmc_pool_chunk_rows", "mtmc_pool_tracklets_workspace_bytes", "mtmc_pool_tracklets", "mtmc_pool_tracklets_backward"]
 
 _lib = None
 
@@ -184,6 +186,16 @@ def load() -> C.CDLL:
                                         C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mtmc_edge_prf.restype = C.c_int32
     lib.mtmc_edge_prf.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mtmc_pool_chunk_rows.restype = C.c_int32
+    lib.mtmc_pool_chunk_rows.argtypes = []
+    lib.mtmc_pool_tracklets_workspace_bytes.restype = C.c_size_t
+    lib.mtmc_pool_tracklets_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.mtmc_pool_tracklets.restype = C.c_int32
+    lib.mtmc_pool_tracklets.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mtmc_pool_tracklets_backward.restype = C.c_int32
+    lib.mtmc_pool_tracklets_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_int64, C.c_void_p]
     lib.mtmc_postprocess_workspace_bytes.restype = C.c_size_t
     lib.mtmc_postprocess_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     lib.mtmc_postprocess.restype = C.c_int32

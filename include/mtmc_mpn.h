@@ -24,6 +24,8 @@
  *   mtmc_mlp_forward           <- MLP.forward as a stand-alone op  models/mlp.py:32-33
  *   mtmc_build_graph           <- graph construction around the call  inference.py:402-456, train.py:316-342
  *   mtmc_postprocess           <- softmax/argmax + post_processing    inference.py:475-489, :70-169; utils.py:30-339
+ *   mtmc_pool_tracklets        <- per-tracklet mean of the detections' embeddings  train.py:305-316,
+ *                                 libs/reid_feature_extraction.py:177-178
  *
  * All floating tensors are fp32, row-major, contiguous unless a stride argument says otherwise;
  * BatchNorm statistics are accumulated in fp64.  All work is enqueued on `stream` (a hipStream_t
@@ -467,6 +469,39 @@ int32_t mtmc_cluster_scores(const int64_t* labels_true, int64_t stride_true, con
                             void* stream);
 int32_t mtmc_edge_prf(const int64_t* predictions, int64_t stride_pred, const int64_t* labels, int64_t stride_labels,
                       int64_t n_edges, int64_t* counts, double* out, void* stream);
+
+/* ---- from detections to node features: the mean of each tracklet's ReID embeddings ----
+ * mtmc_pool_tracklets replaces the reference's Python loop with one torch.mean(bboxes_embeds, 0) per tracklet and the
+ * torch.stack behind it (train.py:305-316), and the same mean taken once per tracklet at feature extraction
+ * (libs/reid_feature_extraction.py:177-178); mtmc_pool_tracklets_backward is what autograd runs through that loop when the
+ * CNN is fine-tuned (train.py:305-316 again, under loss.backward()).
+ *   embeds  [n_rows][feat_dim] fp32, element stride row_stride between rows (a multiple of 4, >= feat_dim), 16-byte aligned
+ *   offsets [n_tracklets + 1] int64 IN DEVICE MEMORY: tracklet s owns rows [offsets[s], offsets[s+1]); offsets[0] = 0,
+ *           offsets[n_tracklets] = n_rows, strictly increasing
+ *   out     [n_tracklets][feat_dim] fp32, contiguous, 16-byte aligned: out[s] = mean of the rows of s
+ *   info    [MTMC_POOL_INFO] int32 in device memory (may be NULL): status, tracklets with a bad range, 0, 0.
+ *           status 0 = ok; 1 = offsets not strictly increasing, or outside [0, n_rows]; 2 = offsets[0] != 0 or
+ *           offsets[n_tracklets] != n_rows (the larger one if both).  The host never reads the offsets: every value is
+ *           clamped into [0, n_rows] before it is used, an empty or inverted range gives a zero row, and with a nonzero
+ *           status the other rows of out hold sums over the clamped ranges (unspecified where ranges overlap).
+ * The rows are cut into chunks of mtmc_pool_chunk_rows() rows, one wave per chunk and 256 columns, so no wave's work grows
+ * with the longest tracklet; a tracklet that crosses chunk boundaries is summed from per-chunk partial sums in chunk order.
+ * No atomics on floats: the same bits on every run.  The partial sums live in the caller's workspace (16-byte aligned):
+ * 2 * ceil(n_rows / chunk_rows) * feat_dim * 4 bytes, rounded up; the size query is host-only and returns 0 for sizes the
+ * entry points refuse: feat_dim not a multiple of 4 or outside [4, 16384], n_rows < 0 or >= 2^31.
+ * mtmc_pool_tracklets_backward: grad_out [n_tracklets][feat_dim] contiguous -> grad_embeds [n_rows][feat_dim] with element
+ * stride grad_row_stride: grad_embeds[r] = grad_out[s] / (offsets[s+1] - offsets[s]) for every row r of s, each row written
+ * exactly once (rows that no tracklet owns -- bad offsets only -- get zeros); needs no workspace.
+ * n_tracklets == 0 or n_rows == 0: success, nothing is enqueued.  Everything else is enqueued on `stream`; nothing is
+ * allocated or synchronised.  MTMC_E_ARG (with text) on bad sizes, NULL or misaligned pointers, a short workspace. */
+#define MTMC_POOL_INFO 4
+int32_t mtmc_pool_chunk_rows(void);
+size_t mtmc_pool_tracklets_workspace_bytes(int64_t n_rows, int32_t feat_dim);
+int32_t mtmc_pool_tracklets(const float* embeds, int64_t row_stride, int64_t n_rows, int32_t feat_dim,
+                            const int64_t* offsets, int64_t n_tracklets, float* out, int32_t* info,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int32_t mtmc_pool_tracklets_backward(const float* grad_out, int64_t n_rows, int32_t feat_dim, const int64_t* offsets,
+                                     int64_t n_tracklets, float* grad_embeds, int64_t grad_row_stride, void* stream);
 
 #ifdef __cplusplus
 }
