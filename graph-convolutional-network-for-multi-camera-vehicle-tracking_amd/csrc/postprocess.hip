@@ -14,7 +14,7 @@
 //   pp_graph_kernel      ONE workgroup of 1024 lanes, resident for the whole cut / prune / cut / split sequence:
 //                        set-parallel steps run on all lanes with block barriers in between; the cluster *numbering*
 //                        is defined by networkx's depth-first traversal order (utils.py:31), which is inherently
-//                        sequential, so that walk runs on lane 0 -- out of LDS whenever N <= 2048 and A <= 16384.
+//                        sequential, so that walk runs on lane 0 -- out of LDS whenever N <= 2048 and A <= 8192.
 // No host round trip, no dynamic allocation: a caller can enqueue it right behind the forward.
 #include "kernels.h"
 #include "../../include/mtmc_mpn.h"
@@ -24,7 +24,7 @@
 namespace mtmc {
 
 constexpr int kPpChunk = 1024;            // edges per block in the wide kernels (256 lanes x 4)
-constexpr int kPpThreads = 1024;          // the graph kernel's workgroup
+constexpr int kPpThreads = 1024;          // the graph kernel's workgroup and its loops' stride (blockDim.x is a load)
 constexpr int kPpLdsNodes = 2048;         // LDS-resident graph state up to this many nodes ...
 constexpr int kPpLdsEdges = 8192;         // ... and this many active edges
 constexpr int kPpNodeArrays = 13;         // rowptr, label, t0..t6, component records (size, tree key, sequence, free ids)
@@ -155,15 +155,29 @@ __global__ __launch_bounds__(256) void pp_compact_kernel(PpParams p) {
 // ------------------------------------------------------------------------------------------------
 // the resident workgroup
 // ------------------------------------------------------------------------------------------------
-struct PpGraph {
-  // N-sized
-  int* rowptr;     // [N+1] CSR over ALL compacted active edges, rows in ascending active id (= edge order)
-  int* label;      // [N]   cluster number of the node's component (output numbering)
-  int* t0; int* t1; int* t2; int* t3; int* t4; int* t5; int* t6;   // [N] each, phase-dependent (see uses)
-  int* csize; int* ctree; int* cseq; int* freel;                  // [N] each: component records of the splitting loop
-  unsigned* csr;   // [A]   target node | kDead
+typedef __attribute__((address_space(3))) int* LdsIntPtr;
+typedef __attribute__((address_space(3))) unsigned* LdsUintPtr;
+
+// Templated on the pointer types so that lane 0's walk over an LDS-resident graph compiles to ds_read/ds_write
+// instead of flat accesses (pp_run_walk); everything else uses generic pointers.
+template <typename IP, typename UP>
+struct PpGraphT {
+  // N-sized, npad apart from rowptr on
+  IP rowptr;       // [N+1] CSR over ALL compacted active edges, rows in ascending active id (= edge order)
+  IP label;        // [N]   cluster number of the node's component (output numbering)
+  IP t0, t1, t2, t3, t4, t5, t6;                                   // [N] each, phase-dependent (see uses)
+  IP csize, ctree, cseq, freel;                                    // [N] each: component records of the splitting loop
+  UP csr;          // [A]   target node | kDead
   int n, a, cams;
+  size_t npad;
+  bool lds_nodes, lds_walk;   // node arrays in LDS; node arrays AND csr in LDS
+  __device__ void place_nodes(IP base) {
+    rowptr = base; label = base + npad; t0 = base + 2 * npad; t1 = base + 3 * npad; t2 = base + 4 * npad;
+    t3 = base + 5 * npad; t4 = base + 6 * npad; t5 = base + 7 * npad; t6 = base + 8 * npad;
+    csize = base + 9 * npad; ctree = base + 10 * npad; cseq = base + 11 * npad; freel = base + 12 * npad;
+  }
 };
+typedef PpGraphT<int*, unsigned*> PpGraph;
 
 __device__ __forceinline__ void pp_kill(const PpParams& p, const PpGraph& g, int i) {
   p.alive[i] = 0;
@@ -174,21 +188,21 @@ __device__ __forceinline__ void pp_kill(const PpParams& p, const PpGraph& g, int
 // successors when the reference builds nx.DiGraph(list of active edges).
 __device__ void pp_build_csr(const PpParams& p, const PpGraph& g, int* sh) {
   int* deg = g.rowptr;
-  for (int i = threadIdx.x; i <= g.n; i += blockDim.x) deg[i] = 0;
+  for (int i = threadIdx.x; i <= g.n; i += kPpThreads) deg[i] = 0;
   __syncthreads();
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) atomicAdd(&deg[p.a_u[i]], 1);
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) atomicAdd(&deg[p.a_u[i]], 1);
   __syncthreads();
   block_exclusive_scan(deg, (int64_t)g.n + 1, sh);      // rowptr[n] = A
   int* fill = g.t0;
-  for (int i = threadIdx.x; i < g.n; i += blockDim.x) fill[i] = g.rowptr[i];
+  for (int i = threadIdx.x; i < g.n; i += kPpThreads) fill[i] = g.rowptr[i];
   __syncthreads();
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) p.a_slot[i] = atomicAdd(&fill[p.a_u[i]], 1);   // any order ...
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) p.a_slot[i] = atomicAdd(&fill[p.a_u[i]], 1);   // any order ...
   __syncthreads();
   // ... then each row's slots re-dealt in ascending active id (rows are short: insertion sort per row)
   int* ids = reinterpret_cast<int*>(g.csr);
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) ids[p.a_slot[i]] = i;
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) ids[p.a_slot[i]] = i;
   __syncthreads();
-  for (int r = threadIdx.x; r < g.n; r += blockDim.x) {
+  for (int r = threadIdx.x; r < g.n; r += kPpThreads) {
     const int lo = g.rowptr[r], hi = g.rowptr[r + 1];
     for (int x = lo + 1; x < hi; ++x) {
       const int key = ids[x];
@@ -198,19 +212,19 @@ __device__ void pp_build_csr(const PpParams& p, const PpGraph& g, int* sh) {
     }
   }
   __syncthreads();
-  for (int s = threadIdx.x; s < g.a; s += blockDim.x) {
+  for (int s = threadIdx.x; s < g.a; s += kPpThreads) {
     const int i = ids[s];
     p.a_slot[i] = s;
     p.mark[s] = 0;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) g.csr[p.a_slot[i]] = (unsigned)p.a_v[i];
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) g.csr[p.a_slot[i]] = (unsigned)p.a_v[i];
   __syncthreads();
 }
 
 // utils.py:125-142: an active edge survives only if its reverse is active too -- decided on a snapshot
 __device__ void pp_cut(const PpParams& p, const PpGraph& g) {
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) {
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) {
     int drop = 0;
     if (p.alive[i]) {
       const unsigned u = (unsigned)p.a_u[i];
@@ -222,7 +236,7 @@ __device__ void pp_cut(const PpParams& p, const PpGraph& g) {
     p.mark[i] = (unsigned char)drop;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x)
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads)
     if (p.mark[i]) pp_kill(p, g, i);
   __syncthreads();
 }
@@ -235,11 +249,11 @@ __device__ int pp_prune(const PpParams& p, const PpGraph& g) {
   unsigned long long* key_in = reinterpret_cast<unsigned long long*>(g.t4);    // t4|t5
   int rounds = 0;
   for (;;) {
-    for (int n = threadIdx.x; n < g.n; n += blockDim.x) {
+    for (int n = threadIdx.x; n < g.n; n += kPpThreads) {
       flow_out[n] = 0; flow_in[n] = 0; key_out[n] = ~0ull; key_in[n] = ~0ull;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < g.a; i += blockDim.x) {
+    for (int i = threadIdx.x; i < g.a; i += kPpThreads) {
       if (!p.alive[i]) continue;
       const int u = p.a_u[i], v = p.a_v[i];
       const unsigned long long key = ((unsigned long long)__float_as_uint(p.a_p[i]) << 32) | (unsigned)i;
@@ -250,7 +264,7 @@ __device__ int pp_prune(const PpParams& p, const PpGraph& g) {
     }
     __syncthreads();
     int any = 0;
-    for (int n = threadIdx.x; n < g.n; n += blockDim.x) {
+    for (int n = threadIdx.x; n < g.n; n += kPpThreads) {
       if (flow_out[n] > g.cams - 1) { any = 1; pp_kill(p, g, (int)(key_out[n] & 0xffffffffu)); }
       if (flow_in[n] > g.cams - 1) { any = 1; pp_kill(p, g, (int)(key_in[n] & 0xffffffffu)); }
     }
@@ -262,14 +276,25 @@ __device__ int pp_prune(const PpParams& p, const PpGraph& g) {
 // Lane 0's part of utils.py:30-52: nx.strongly_connected_components' traversal (sources in node insertion order,
 // successors in insertion order, a component is emitted when its root finishes -- Tarjan's algorithm; networkx
 // evaluates the lowlinks at finish time, here they are folded into the single pass over the successors, which finds
-// the same roots in the same order) and the stable placement of the emitted components by size.  Templated on the pointer types
-// so that the LDS-resident case compiles to ds_read/ds_write instead of flat accesses.
-template <typename IP, typename UP>
-__device__ int pp_walk(IP rowptr, IP pre, IP low, IP comp, IP cursor, IP dstack, IP sstack, UP csr, IP src, int n_src) {
-  int counter = 0, n_comp = 0, stop = 0;
+// the same roots in the same order).  The two things a pass decides are its policy's (by value: state in registers):
+//   pol.enter_tree(first)   a tree starts at an unvisited source, whose t1 still holds `first` (pp_sources)
+//   pol.finish(g, v, stop)  the component rooted at v is complete: pop it off the component stack (pp_pop)
+template <typename G>
+__device__ __forceinline__ int pp_pop(const G& g, int v, int& stop, int id) {   // comp = id down to v; returns how many
+  int w, cnt = 0;
+  do { w = g.t5[--stop]; g.t2[w] = id; ++cnt; } while (w != v);
+  return cnt;
+}
+
+template <typename IP, typename UP, typename Policy>
+__device__ __forceinline__ Policy pp_walk(const PpGraphT<IP, UP>& g, int n_src, Policy pol) {
+  const IP rowptr = g.rowptr, pre = g.t0, low = g.t1, comp = g.t2, cursor = g.t3, dstack = g.t4, sstack = g.t5, src = g.t6;
+  const UP csr = g.csr;
+  int counter = 0, stop = 0;
   for (int i = 0; i < n_src; ++i) {
     const int source = src[i];
     if (pre[source] != 0) continue;
+    pol.enter_tree(low[source]);
     int dtop = 0;
     dstack[dtop++] = source;
     pre[source] = low[source] = ++counter;
@@ -299,14 +324,76 @@ __device__ int pp_walk(IP rowptr, IP pre, IP low, IP comp, IP cursor, IP dstack,
         const int par = dstack[dtop - 1];
         if (lv < low[par]) low[par] = lv;
       }
-      if (lv == pre[v]) {
-        int w;
-        do { w = sstack[--stop]; comp[w] = n_comp; } while (w != v);
-        ++n_comp;
-      }
+      if (lv == pre[v]) pol.finish(g, v, stop);
     }
   }
-  return n_comp;
+  return pol;
+}
+
+// the final pass: components numbered in the order networkx emits them
+struct PpNumberAll {
+  int n_comp;
+  __device__ __forceinline__ void enter_tree(int) {}
+  template <typename G>
+  __device__ __forceinline__ void finish(const G& g, int v, int& stop) { pp_pop(g, v, stop, n_comp++); }
+};
+
+// the splitting loop's re-walk: ids from the free list (else a new one), and the key (size, first position of the
+// tree's source, sequence within this walk) recorded per component
+struct PpRecord {
+  int n_free, n_ids, seq, tree_key;
+  __device__ __forceinline__ void enter_tree(int first) { tree_key = first; }
+  template <typename G>
+  __device__ __forceinline__ void finish(const G& g, int v, int& stop) {
+    const int id = n_free > 0 ? g.freel[--n_free] : n_ids++;
+    g.csize[id] = pp_pop(g, v, stop, id); g.ctree[id] = tree_key; g.cseq[id] = seq++;
+  }
+};
+
+// Lane 0 only.  The one place that picks the pointer types: LDS address-space pointers only when node arrays and CSR
+// are both LDS-resident, generic ones otherwise.
+template <typename Policy>
+__device__ Policy pp_run_walk(const PpParams& p, const PpGraph& g, int n_src, Policy pol) {
+  const long long t_begin = wall_clock64();
+  if (g.lds_walk) {
+    PpGraphT<LdsIntPtr, LdsUintPtr> l;
+    l.npad = g.npad; l.place_nodes((LdsIntPtr)g.rowptr); l.csr = (LdsUintPtr)g.csr;
+    pol = pp_walk(l, n_src, pol);
+  } else {
+    pol = pp_walk(g, n_src, pol);
+  }
+  p.hdr[2] += (int)(wall_clock64() - t_begin);           // 100 MHz ticks spent walking (diagnostic, info[7])
+  return pol;
+}
+
+// The ordered source list of a walk over the nodes that `want`: node insertion order of nx.DiGraph(active edge list),
+// i.e. first appearance, u before v within an edge.  Resets the walk state (t0 pre, t2 comp, t3 cursor) of those nodes
+// -- recycle(n) sees each just before -- and leaves their first positions in t1 (the walk's low, until it visits
+// them), the list in t6; returns its length.  `want` holds for both ends of an edge or for neither.
+template <typename Want, typename Recycle>
+__device__ int pp_sources(const PpParams& p, const PpGraph& g, int* sh, Want want, Recycle recycle) {
+  int* pre = g.t0; int* first_pos = g.t1; int* comp = g.t2; int* cursor = g.t3; int* src = g.t6;
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) {
+    if (!want(n)) continue;
+    recycle(n);
+    pre[n] = 0; comp[n] = -1; cursor[n] = g.rowptr[n]; first_pos[n] = 0x7fffffff;
+  }
+  for (int i = threadIdx.x; i < 2 * g.a; i += kPpThreads) p.g_flags[i] = 0;
+  __syncthreads();
+  for (int k = threadIdx.x; k < g.a; k += kPpThreads) {
+    if (!p.alive[k] || !want(p.a_u[k])) continue;
+    atomicMin(&first_pos[p.a_u[k]], 2 * k);
+    atomicMin(&first_pos[p.a_v[k]], 2 * k + 1);
+  }
+  __syncthreads();
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads)
+    if (want(n) && first_pos[n] != 0x7fffffff) p.g_flags[first_pos[n]] = 1;
+  __syncthreads();
+  const int n_src = block_exclusive_scan(p.g_flags, 2 * (int64_t)g.a, sh);
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads)
+    if (want(n) && first_pos[n] != 0x7fffffff) src[p.g_flags[first_pos[n]]] = n;
+  __syncthreads();
+  return n_src;
 }
 
 template <typename IP>
@@ -314,71 +401,39 @@ __device__ void pp_place(IP clabel, IP hist, IP csize, int n_comp) {
   for (int k = 0; k < n_comp; ++k) clabel[k] = hist[csize[k] - 1]++;
 }
 
-typedef __attribute__((address_space(3))) int* LdsIntPtr;
-typedef __attribute__((address_space(3))) unsigned* LdsUintPtr;
-
 // utils.py:30-52.  Strongly connected components in the order networkx emits them, stably sorted by size; nodes
 // without an active edge follow as singletons in index order.  label[v] = position of v's set; returns the number
 // of sets; sizes by label in t5.  All lanes prepare the ordered source list and the numbering; the walk is lane 0's.
-__device__ int pp_scc(const PpParams& p, const PpGraph& g, bool nodes_in_lds, bool csr_in_lds, int* sh) {
-  int* pre = g.t0; int* low = g.t1; int* comp = g.t2; int* cursor = g.t3; int* dstack = g.t4; int* sstack = g.t5;
-  int* src = g.t6;
-  int* first_pos = low;                                  // until the walk starts
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x) {
-    pre[n] = 0; comp[n] = -1; cursor[n] = g.rowptr[n]; first_pos[n] = 0x7fffffff;
-  }
-  for (int i = threadIdx.x; i < 2 * g.a; i += blockDim.x) p.g_flags[i] = 0;
-  __syncthreads();
-  // node insertion order of nx.DiGraph(active edge list): first appearance, u before v within an edge
-  for (int k = threadIdx.x; k < g.a; k += blockDim.x) {
-    if (!p.alive[k]) continue;
-    atomicMin(&first_pos[p.a_u[k]], 2 * k);
-    atomicMin(&first_pos[p.a_v[k]], 2 * k + 1);
-  }
-  __syncthreads();
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x)
-    if (first_pos[n] != 0x7fffffff) p.g_flags[first_pos[n]] = 1;
-  __syncthreads();
-  const int n_src = block_exclusive_scan(p.g_flags, 2 * (int64_t)g.a, sh);
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x)
-    if (first_pos[n] != 0x7fffffff) src[p.g_flags[first_pos[n]]] = n;
-  __syncthreads();
+__device__ int pp_scc(const PpParams& p, const PpGraph& g, int* sh) {
+  int* comp = g.t2;
+  const int n_src = pp_sources(p, g, sh, [](int) { return true; }, [](int) {});
   __shared__ int s_ncomp;
-  if (threadIdx.x == 0) {
-    const long long t_begin = wall_clock64();
-    if (nodes_in_lds && csr_in_lds)
-      s_ncomp = pp_walk((LdsIntPtr)g.rowptr, (LdsIntPtr)pre, (LdsIntPtr)low, (LdsIntPtr)comp, (LdsIntPtr)cursor,
-                        (LdsIntPtr)dstack, (LdsIntPtr)sstack, (LdsUintPtr)g.csr, (LdsIntPtr)src, n_src);
-    else
-      s_ncomp = pp_walk(g.rowptr, pre, low, comp, cursor, dstack, sstack, g.csr, src, n_src);
-    p.hdr[2] += (int)(wall_clock64() - t_begin);         // 100 MHz ticks spent walking (diagnostic, info[7])
-  }
+  if (threadIdx.x == 0) s_ncomp = pp_run_walk(p, g, n_src, PpNumberAll{0}).n_comp;
   __syncthreads();
   const int n_comp = s_ncomp;
   // sizes per emitted component (t3), histogram of sizes (t4, sizes 1..N), stable placement by size (lane 0),
   // isolated nodes numbered after them in index order (scan over t1)
   int* csize = g.t3; int* hist = g.t4; int* clabel = g.t0; int* lsize = g.t5; int* iso = g.t1;
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x) { csize[n] = 0; hist[n] = 0; iso[n] = comp[n] < 0 ? 1 : 0; }
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) { csize[n] = 0; hist[n] = 0; iso[n] = comp[n] < 0 ? 1 : 0; }
   __syncthreads();
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x)
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads)
     if (comp[n] >= 0) atomicAdd(&csize[comp[n]], 1);
   __syncthreads();
-  for (int k = threadIdx.x; k < n_comp; k += blockDim.x) atomicAdd(&hist[csize[k] - 1], 1);
+  for (int k = threadIdx.x; k < n_comp; k += kPpThreads) atomicAdd(&hist[csize[k] - 1], 1);
   __syncthreads();
   block_exclusive_scan(hist, g.n, sh);
   const int n_iso = block_exclusive_scan(iso, g.n, sh);
   if (threadIdx.x == 0) {
-    if (nodes_in_lds) pp_place((LdsIntPtr)clabel, (LdsIntPtr)hist, (LdsIntPtr)csize, n_comp);
+    if (g.lds_nodes) pp_place((LdsIntPtr)clabel, (LdsIntPtr)hist, (LdsIntPtr)csize, n_comp);
     else pp_place(clabel, hist, csize, n_comp);
   }
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x) lsize[n] = 1;
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) lsize[n] = 1;
   __syncthreads();
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x) g.label[n] = comp[n] >= 0 ? clabel[comp[n]] : n_comp + iso[n];
-  for (int k = threadIdx.x; k < n_comp; k += blockDim.x) lsize[clabel[k]] = csize[k];
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) g.label[n] = comp[n] >= 0 ? clabel[comp[n]] : n_comp + iso[n];
+  for (int k = threadIdx.x; k < n_comp; k += kPpThreads) lsize[clabel[k]] = csize[k];
   __syncthreads();
   return n_comp + n_iso;
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // Splitting loop without a full renumbering per iteration.  The loop only needs (a) the first over-sized set in the
@@ -387,62 +442,14 @@ __device__ int pp_scc(const PpParams& p, const PpGraph& g, bool nodes_in_lds, bo
 // appearance in the active edge list, components within a tree in finish order".  Dropping an edge changes trees
 // only inside the weakly connected component (WCC) it belonged to, and positions in the edge list never move, so
 // every component keeps the key (size, first position of its tree's source, sequence within its walk); lane 0
-// re-walks the dirty WCCs alone and the numbers asked for are found by counting smaller keys.
+// re-walks the dirty WCCs alone (PpRecord) and the numbers asked for are found by counting smaller keys.
 // ------------------------------------------------------------------------------------------------
-template <typename IP, typename UP>
-__device__ void pp_walk_inc(IP rowptr, IP pre, IP low, IP comp, IP cursor, IP dstack, IP sstack, UP csr, IP src, int n_src,
-                            IP csize, IP ctree, IP cseq, IP freel, int* n_free, int* n_ids) {
-  int counter = 0, seq = 0, stop = 0, nf = *n_free, ni = *n_ids;
-  for (int i = 0; i < n_src; ++i) {
-    const int source = src[i];
-    if (pre[source] != 0) continue;
-    const int tree_key = low[source];                    // unvisited: still the node's first position in the edge list
-    int dtop = 0;
-    dstack[dtop++] = source;
-    pre[source] = low[source] = ++counter;
-    sstack[stop++] = source;
-    while (dtop) {
-      const int v = dstack[dtop - 1];
-      const int end = rowptr[v + 1];
-      int c = cursor[v], lv = low[v];
-      int child = -1;
-      while (c < end) {
-        const unsigned t = csr[c++];
-        if (t & kDead) continue;
-        const int pt = pre[t];
-        if (pt == 0) { child = (int)t; break; }
-        if (comp[t] < 0) lv = min(lv, pt);
-      }
-      cursor[v] = c;
-      low[v] = lv;
-      if (child >= 0) {
-        dstack[dtop++] = child;
-        pre[child] = low[child] = ++counter;
-        sstack[stop++] = child;
-        continue;
-      }
-      --dtop;
-      if (dtop) {
-        const int par = dstack[dtop - 1];
-        if (lv < low[par]) low[par] = lv;
-      }
-      if (lv == pre[v]) {
-        const int id = nf > 0 ? freel[--nf] : ni++;
-        int w, cnt = 0;
-        do { w = sstack[--stop]; comp[w] = id; ++cnt; } while (w != v);
-        csize[id] = cnt; ctree[id] = tree_key; cseq[id] = seq++;
-      }
-    }
-  }
-  *n_free = nf; *n_ids = ni;
-}
-
 __device__ void pp_wcc(const PpParams& p, const PpGraph& g) {
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x) p.g_wcc[n] = n;
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) p.g_wcc[n] = n;
   __syncthreads();
   for (;;) {
     int changed = 0;
-    for (int k = threadIdx.x; k < g.a; k += blockDim.x) {
+    for (int k = threadIdx.x; k < g.a; k += kPpThreads) {
       if (!p.alive[k]) continue;
       const int u = p.a_u[k], v = p.a_v[k];
       const int a = p.g_wcc[u], b = p.g_wcc[v];
@@ -454,7 +461,7 @@ __device__ void pp_wcc(const PpParams& p, const PpGraph& g) {
   // pointer jumping to the component minimum (labels only ever decrease towards it)
   for (;;) {
     int changed = 0;
-    for (int n = threadIdx.x; n < g.n; n += blockDim.x) {
+    for (int n = threadIdx.x; n < g.n; n += kPpThreads) {
       const int w = p.g_wcc[n], ww = p.g_wcc[w];
       if (ww != w) { p.g_wcc[n] = ww; changed = 1; }
     }
@@ -462,43 +469,33 @@ __device__ void pp_wcc(const PpParams& p, const PpGraph& g) {
   }
 }
 
-// Re-walk the dirty WCCs.  s_cnt: {free ids, ids in use (high-water mark)} in shared memory.
-__device__ void pp_inc_walk(const PpParams& p, const PpGraph& g, bool nodes_in_lds, bool csr_in_lds, int* s_cnt, int* sh) {
-  int* pre = g.t0; int* low = g.t1; int* comp = g.t2; int* cursor = g.t3; int* dstack = g.t4; int* sstack = g.t5;
-  int* src = g.t6;
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x) {
-    if (!p.g_dirty[p.g_wcc[n]]) continue;
-    const int id = comp[n];
-    if (id >= 0 && atomicExch(&g.csize[id], 0) > 0) g.freel[atomicAdd(&s_cnt[0], 1)] = id;
-    pre[n] = 0; comp[n] = -1; cursor[n] = g.rowptr[n]; low[n] = 0x7fffffff;
-  }
-  for (int i = threadIdx.x; i < 2 * g.a; i += blockDim.x) p.g_flags[i] = 0;
-  __syncthreads();
-  for (int k = threadIdx.x; k < g.a; k += blockDim.x) {
-    if (!p.alive[k] || !p.g_dirty[p.g_wcc[p.a_u[k]]]) continue;
-    atomicMin(&low[p.a_u[k]], 2 * k);
-    atomicMin(&low[p.a_v[k]], 2 * k + 1);
-  }
-  __syncthreads();
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x)
-    if (p.g_dirty[p.g_wcc[n]] && low[n] != 0x7fffffff) p.g_flags[low[n]] = 1;
-  __syncthreads();
-  const int n_src = block_exclusive_scan(p.g_flags, 2 * (int64_t)g.a, sh);
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x)
-    if (p.g_dirty[p.g_wcc[n]] && low[n] != 0x7fffffff) src[p.g_flags[low[n]]] = n;
-  __syncthreads();
+// The splitting loop's shared words
+struct PpSplitWords {
+  int n_free, n_ids;            // component ids on the free list (g.freel); ids in use (high-water mark)
+  int pick;                     // the component a search settled on, -1 for none
+  int min_size;                 // pp_first_oversized: size of the smallest over-sized component
+  int count, n_over;            // pp_number_of: smaller keys counted; pp_carrier_of: over-sized components listed
+  unsigned min_prob;            // pp_split_step: minimum probability (its bits) over the edges touching the component
+  unsigned long long min_key;   // pp_first_oversized: smallest pp_tree_key at min_size
+};
+
+// Re-walk the dirty WCCs: the ids of their components go back to the free list, their nodes are walked again.
+__device__ void pp_inc_walk(const PpParams& p, const PpGraph& g, PpSplitWords& s, int* sh) {
+  const int n_src = pp_sources(p, g, sh, [&](int n) { return p.g_dirty[p.g_wcc[n]] != 0; },
+                               [&](int n) {
+                                 const int id = g.t2[n];
+                                 if (id >= 0 && atomicExch(&g.csize[id], 0) > 0) g.freel[atomicAdd(&s.n_free, 1)] = id;
+                               });
   if (threadIdx.x == 0) {
-    const long long t_begin = wall_clock64();
-    if (nodes_in_lds && csr_in_lds)
-      pp_walk_inc((LdsIntPtr)g.rowptr, (LdsIntPtr)pre, (LdsIntPtr)low, (LdsIntPtr)comp, (LdsIntPtr)cursor,
-                  (LdsIntPtr)dstack, (LdsIntPtr)sstack, (LdsUintPtr)g.csr, (LdsIntPtr)src, n_src,
-                  (LdsIntPtr)g.csize, (LdsIntPtr)g.ctree, (LdsIntPtr)g.cseq, (LdsIntPtr)g.freel, &s_cnt[0], &s_cnt[1]);
-    else
-      pp_walk_inc(g.rowptr, pre, low, comp, cursor, dstack, sstack, g.csr, src, n_src, g.csize, g.ctree, g.cseq,
-                  g.freel, &s_cnt[0], &s_cnt[1]);
-    p.hdr[2] += (int)(wall_clock64() - t_begin);
+    const PpRecord r = pp_run_walk(p, g, n_src, PpRecord{s.n_free, s.n_ids, 0, 0});
+    s.n_free = r.n_free; s.n_ids = r.n_ids;
   }
   __syncthreads();
+}
+
+// (tree source position, sequence within the walk) of component c: what orders components of one size
+__device__ __forceinline__ unsigned long long pp_tree_key(const PpGraph& g, int c) {
+  return ((unsigned long long)(unsigned)g.ctree[c] << 32) | (unsigned)g.cseq[c];
 }
 
 // key(a) < key(b) in the reference's numbering: size, then tree source position, then sequence within the walk
@@ -508,14 +505,116 @@ __device__ __forceinline__ bool pp_key_less(const PpGraph& g, int a, int b) {
   return g.cseq[a] < g.cseq[b];
 }
 
+// First over-sized set of the numbering: the smallest key among components of more than num_cameras nodes; -1: none
+__device__ int pp_first_oversized(const PpGraph& g, PpSplitWords& s) {
+  if (threadIdx.x == 0) { s.min_size = 0x7fffffff; s.min_key = ~0ull; s.pick = -1; }
+  __syncthreads();
+  const int n_ids = s.n_ids;
+  for (int c = threadIdx.x; c < n_ids; c += kPpThreads)
+    if (g.csize[c] > g.cams) atomicMin(&s.min_size, g.csize[c]);
+  __syncthreads();
+  const int min_size = s.min_size;
+  if (min_size == 0x7fffffff) return -1;
+  for (int c = threadIdx.x; c < n_ids; c += kPpThreads)
+    if (g.csize[c] == min_size) atomicMin(&s.min_key, pp_tree_key(g, c));
+  __syncthreads();
+  for (int c = threadIdx.x; c < n_ids; c += kPpThreads)
+    if (g.csize[c] == min_size && pp_tree_key(g, c) == s.min_key) s.pick = c;
+  __syncthreads();
+  return s.pick;
+}
+
+// The number of component `id` = how many components precede it
+__device__ int pp_number_of(const PpGraph& g, PpSplitWords& s, int id) {
+  if (threadIdx.x == 0) s.count = 0;
+  __syncthreads();
+  const int n_ids = s.n_ids;
+  for (int c = threadIdx.x; c < n_ids; c += kPpThreads)
+    if (g.csize[c] > 0 && pp_key_less(g, c, id)) atomicAdd(&s.count, 1);
+  __syncthreads();
+  return s.count;
+}
+
+// Which over-sized component carries number `lab` now (-1: none)?  One wave per candidate counts the smaller keys.
+__device__ int pp_carrier_of(const PpGraph& g, PpSplitWords& s, int lab) {
+  int* over = g.t4;                                      // list of over-sized components (free outside the walks)
+  if (threadIdx.x == 0) { s.n_over = 0; s.pick = -1; }
+  __syncthreads();
+  const int n_ids = s.n_ids;
+  for (int c = threadIdx.x; c < n_ids; c += kPpThreads)
+    if (g.csize[c] > g.cams) over[atomicAdd(&s.n_over, 1)] = c;
+  __syncthreads();
+  const int n_over = s.n_over, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = kPpThreads >> 6;
+  for (int o = wave; o < n_over; o += n_waves) {
+    const int id = over[o];
+    int cnt = 0;
+    for (int c = lane; c < n_ids; c += 64)
+      if (g.csize[c] > 0 && pp_key_less(g, c, id)) ++cnt;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if (lane == 0 && cnt == lab) s.pick = id;
+  }
+  __syncthreads();
+  const int cur = s.pick;
+  __syncthreads();                                       // everyone has it before the next search resets it
+  return cur;
+}
+
+// One splitting step on component `cur`: drop every edge whose probability equals the minimum over the active edges
+// touching cur, and mark the WCCs that lost one dirty (and only those).  false: no active edge touches cur.
+__device__ bool pp_split_step(const PpParams& p, const PpGraph& g, PpSplitWords& s, int cur) {
+  const int* comp = g.t2;
+  if (threadIdx.x == 0) s.min_prob = 0xffffffffu;
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) p.g_dirty[n] = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads)
+    if (p.alive[i] && (comp[p.a_u[i]] == cur || comp[p.a_v[i]] == cur))
+      atomicMin(&s.min_prob, __float_as_uint(p.a_p[i]));
+  __syncthreads();
+  const unsigned mn = s.min_prob;
+  if (mn == 0xffffffffu) return false;
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads)
+    if (p.alive[i] && __float_as_uint(p.a_p[i]) == mn) {
+      pp_kill(p, g, i);
+      p.g_dirty[p.g_wcc[p.a_u[i]]] = 1;
+    }
+  __syncthreads();
+  return true;
+}
+
+// utils.py:54-123, tail recursion unrolled: pick the first over-sized set of the numbering; drop every edge whose
+// probability equals the minimum over the active edges touching it; stay on the SAME NUMBER while the set that
+// carries it after the renumbering is over-sized (reference quirk), else pick again.  Returns the status (0, 2, 3).
+__device__ int pp_split(const PpParams& p, const PpGraph& g, int* sh, int& split_iters, int& walks) {
+  __shared__ PpSplitWords s;
+  if (threadIdx.x == 0) { s.n_free = 0; s.n_ids = 0; }
+  pp_wcc(p, g);
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) { p.g_dirty[n] = 1; g.t2[n] = -1; g.csize[n] = 0; }
+  __syncthreads();
+  pp_inc_walk(p, g, s, sh);
+  ++walks;
+  for (;;) {
+    int cur = pp_first_oversized(g, s);
+    if (cur < 0) return 0;
+    const int lab = pp_number_of(g, s, cur);
+    while (cur >= 0) {
+      if (!pp_split_step(p, g, s, cur)) return 2;        // cannot happen for a real component; never spin on it
+      pp_inc_walk(p, g, s, sh);
+      ++walks; ++split_iters;
+      if (split_iters >= kPpMaxSplitIters) return 3;     // a resident workgroup must not run unbounded
+      cur = pp_carrier_of(g, s, lab);
+    }
+  }
+}
+
 // Drop the dead edges from the active arrays (stable) once the cut / prune stages are over: the walks of the
 // splitting loop then step over ~A_alive instead of A_in slots.  Dead edges get their prediction cleared here.
 __device__ int pp_compact_alive(const PpParams& p, const PpGraph& g, int* sh) {
   int* pos = p.g_flags;
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) pos[i] = p.alive[i] ? 1 : 0;
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) pos[i] = p.alive[i] ? 1 : 0;
   __syncthreads();
   const int kept = block_exclusive_scan(pos, g.a, sh);
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) {
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) {
     if (p.alive[i]) {
       const int k = pos[i];
       p.b_idx[k] = p.a_idx[i]; p.b_u[k] = p.a_u[i]; p.b_v[k] = p.a_v[i]; p.b_p[k] = p.a_p[i];
@@ -524,7 +623,7 @@ __device__ int pp_compact_alive(const PpParams& p, const PpGraph& g, int* sh) {
     }
   }
   __syncthreads();
-  for (int k = threadIdx.x; k < kept; k += blockDim.x) {
+  for (int k = threadIdx.x; k < kept; k += kPpThreads) {
     p.a_idx[k] = p.b_idx[k]; p.a_u[k] = p.b_u[k]; p.a_v[k] = p.b_v[k]; p.a_p[k] = p.b_p[k];
     p.alive[k] = 1;
   }
@@ -535,24 +634,21 @@ __device__ int pp_compact_alive(const PpParams& p, const PpGraph& g, int* sh) {
 __global__ __launch_bounds__(kPpThreads) void pp_graph_kernel(PpParams p, int lds_nodes) {
   extern __shared__ __attribute__((aligned(16))) int lds[];
   __shared__ int sh[kPpThreads / 64 + 1];
-  __shared__ unsigned s_min;
   if (p.hdr[1]) {                                        // capacity exceeded: report, leave predictions = argmax
     if (threadIdx.x == 0) p.info[3] = 1;
     return;
   }
   PpGraph g;
-  g.n = (int)p.n_nodes; g.a = p.hdr[0]; g.cams = p.num_cameras;
-  const size_t npad = ((size_t)g.n + 4) & ~(size_t)3;
-  int* node_base = lds_nodes ? lds : p.g_node;
-  g.rowptr = node_base; g.label = node_base + npad;
-  g.t0 = node_base + 2 * npad; g.t1 = node_base + 3 * npad; g.t2 = node_base + 4 * npad; g.t3 = node_base + 5 * npad;
-  g.t4 = node_base + 6 * npad; g.t5 = node_base + 7 * npad; g.t6 = node_base + 8 * npad;
-  g.csize = node_base + 9 * npad; g.ctree = node_base + 10 * npad; g.cseq = node_base + 11 * npad;
-  g.freel = node_base + 12 * npad;
-  unsigned* lds_csr = reinterpret_cast<unsigned*>(lds + (lds_nodes ? kPpNodeArrays * npad : 0));
-  bool csr_in_lds = g.a <= kPpLdsEdges;
-  g.csr = csr_in_lds ? lds_csr : p.g_csr;
-
+  g.n = (int)p.n_nodes; g.a = p.hdr[0]; g.cams = p.num_cameras; g.lds_nodes = lds_nodes != 0;
+  g.npad = ((size_t)g.n + 4) & ~(size_t)3;
+  g.place_nodes(lds_nodes ? lds : p.g_node);
+  unsigned* lds_csr = reinterpret_cast<unsigned*>(lds + (lds_nodes ? kPpNodeArrays * g.npad : 0));
+  auto place_csr = [&]() {                               // by the current number of active edges
+    const bool csr_in_lds = g.a <= kPpLdsEdges;
+    g.csr = csr_in_lds ? lds_csr : p.g_csr;
+    g.lds_walk = g.lds_nodes && csr_in_lds;
+  };
+  place_csr();
   pp_build_csr(p, g, sh);
   const bool cutting = p.flags & 1, pruning = p.flags & 2, splitting = p.flags & 4;
   int prune_rounds = 0, split_iters = 0, walks = 0, status = 0;
@@ -561,98 +657,18 @@ __global__ __launch_bounds__(kPpThreads) void pp_graph_kernel(PpParams p, int ld
   if (cutting) pp_cut(p, g);
   if (cutting || pruning) {
     g.a = pp_compact_alive(p, g, sh);
-    csr_in_lds = g.a <= kPpLdsEdges;
-    g.csr = csr_in_lds ? lds_csr : p.g_csr;
+    place_csr();
     pp_build_csr(p, g, sh);
   }
-  if (splitting) {
-    // utils.py:54-123, tail recursion unrolled: pick the first over-sized set of the numbering; drop every edge whose
-    // probability equals the minimum over the active edges touching it; stay on the SAME NUMBER while the set that
-    // carries it after the renumbering is over-sized (reference quirk), else pick again
-    __shared__ int s_cnt[2], s_i[4];
-    __shared__ unsigned long long s_key;
-    int* over = g.t4;                                    // list of over-sized components (free outside the walks)
-    if (threadIdx.x == 0) { s_cnt[0] = 0; s_cnt[1] = 0; }
-    pp_wcc(p, g);
-    for (int n = threadIdx.x; n < g.n; n += blockDim.x) { p.g_dirty[n] = 1; g.t2[n] = -1; g.csize[n] = 0; }
-    __syncthreads();
-    pp_inc_walk(p, g, lds_nodes != 0, csr_in_lds, s_cnt, sh);
-    ++walks;
-    for (;;) {
-      // first over-sized set = smallest key among the components with more than num_cameras nodes
-      if (threadIdx.x == 0) { s_i[0] = 0x7fffffff; s_key = ~0ull; s_i[1] = -1; s_i[2] = 0; }
-      __syncthreads();
-      const int n_ids = s_cnt[1];
-      for (int c = threadIdx.x; c < n_ids; c += blockDim.x)
-        if (g.csize[c] > g.cams) atomicMin(&s_i[0], g.csize[c]);
-      __syncthreads();
-      const int min_size = s_i[0];
-      if (min_size == 0x7fffffff) break;
-      for (int c = threadIdx.x; c < n_ids; c += blockDim.x)
-        if (g.csize[c] == min_size)
-          atomicMin(&s_key, ((unsigned long long)(unsigned)g.ctree[c] << 32) | (unsigned)g.cseq[c]);
-      __syncthreads();
-      for (int c = threadIdx.x; c < n_ids; c += blockDim.x)
-        if (g.csize[c] == min_size && (((unsigned long long)(unsigned)g.ctree[c] << 32) | (unsigned)g.cseq[c]) == s_key)
-          s_i[1] = c;
-      __syncthreads();
-      int cur = s_i[1];
-      for (int c = threadIdx.x; c < n_ids; c += blockDim.x)      // its number = how many components precede it
-        if (g.csize[c] > 0 && pp_key_less(g, c, cur)) atomicAdd(&s_i[2], 1);
-      __syncthreads();
-      const int lab = s_i[2];
-      for (;;) {
-        if (threadIdx.x == 0) s_min = 0xffffffffu;
-        for (int n = threadIdx.x; n < g.n; n += blockDim.x) p.g_dirty[n] = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < g.a; i += blockDim.x)
-          if (p.alive[i] && (g.t2[p.a_u[i]] == cur || g.t2[p.a_v[i]] == cur))
-            atomicMin(&s_min, __float_as_uint(p.a_p[i]));
-        __syncthreads();
-        const unsigned mn = s_min;
-        if (mn == 0xffffffffu) { status = 2; break; }    // cannot happen for a real component; never spin on it
-        for (int i = threadIdx.x; i < g.a; i += blockDim.x)
-          if (p.alive[i] && __float_as_uint(p.a_p[i]) == mn) {
-            pp_kill(p, g, i);
-            p.g_dirty[p.g_wcc[p.a_u[i]]] = 1;
-          }
-        __syncthreads();
-        pp_inc_walk(p, g, lds_nodes != 0, csr_in_lds, s_cnt, sh);
-        ++walks; ++split_iters;
-        if (split_iters >= kPpMaxSplitIters) { status = 3; break; }   // a resident workgroup must not run unbounded
-        // which over-sized component carries number `lab` now?  (one wave per candidate counts the smaller keys)
-        if (threadIdx.x == 0) { s_i[3] = 0; s_i[1] = -1; }
-        __syncthreads();
-        const int ids_now = s_cnt[1];
-        for (int c = threadIdx.x; c < ids_now; c += blockDim.x)
-          if (g.csize[c] > g.cams) over[atomicAdd(&s_i[3], 1)] = c;
-        __syncthreads();
-        const int n_over = s_i[3], lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-        for (int o = wave; o < n_over; o += n_waves) {
-          const int id = over[o];
-          int cnt = 0;
-          for (int c = lane; c < ids_now; c += 64)
-            if (g.csize[c] > 0 && pp_key_less(g, c, id)) ++cnt;
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-          if (lane == 0 && cnt == lab) s_i[1] = id;
-        }
-        __syncthreads();
-        cur = s_i[1];
-        __syncthreads();
-        if (cur < 0) break;
-      }
-      if (status) break;
-    }
-  }
-  const int n_sets = pp_scc(p, g, lds_nodes != 0, csr_in_lds, sh);     // the reference's final numbering
+  if (splitting) status = pp_split(p, g, sh, split_iters, walks);
+  const int n_sets = pp_scc(p, g, sh);                   // the reference's final numbering
   ++walks;
   // outputs
   int alive_cnt = 0;
-  for (int i = threadIdx.x; i < g.a; i += blockDim.x) {
+  for (int i = threadIdx.x; i < g.a; i += kPpThreads) {
     if (p.alive[i]) ++alive_cnt; else p.pred[p.a_idx[i]] = 0;
   }
-  for (int n = threadIdx.x; n < g.n; n += blockDim.x) p.id_pred[n] = g.label[n];
+  for (int n = threadIdx.x; n < g.n; n += kPpThreads) p.id_pred[n] = g.label[n];
   __shared__ int s_alive;
   if (threadIdx.x == 0) s_alive = 0;
   __syncthreads();
@@ -665,53 +681,41 @@ __global__ __launch_bounds__(kPpThreads) void pp_graph_kernel(PpParams p, int ld
 }
 
 // ------------------------------------------------------------------------------------------------
-struct PpLayout { size_t hdr, block_count, a_idx, a_u, a_v, a_p, a_slot, alive, mark, g_node, g_csr, g_flags, b_idx, b_u, b_v, b_p, g_wcc, g_dirty, total; };
-
-static PpLayout pp_layout(int64_t n_nodes, int64_t n_edges, int64_t cap) {
-  PpLayout lo;
+// The workspace, buffer by buffer, each on a 256-byte boundary; from p.n_nodes, p.n_edges and max_active.  Sets p.cap
+// and returns the total; given a base pointer it also fills p's workspace fields.
+static size_t pp_carve(PpParams& p, int64_t max_active, char* ws) {
+  p.cap = (max_active > 0 && max_active < p.n_edges) ? max_active : p.n_edges;
+  if (p.cap < 1) p.cap = 1;
+  const size_t cap = (size_t)p.cap, nodes = (size_t)p.n_nodes + 4;
+  const int64_t nb = (p.n_edges + kPpChunk - 1) / kPpChunk;
   size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; };
-  const int64_t nb = (n_edges + kPpChunk - 1) / kPpChunk;
-  lo.hdr = take(16 * sizeof(int));
-  lo.block_count = take((size_t)(nb > 0 ? nb : 1) * sizeof(int));
-  lo.a_idx = take((size_t)cap * 4); lo.a_u = take((size_t)cap * 4); lo.a_v = take((size_t)cap * 4);
-  lo.a_p = take((size_t)cap * 4); lo.a_slot = take((size_t)cap * 4);
-  lo.alive = take((size_t)cap); lo.mark = take((size_t)cap);
-  lo.g_node = take((size_t)kPpNodeArrays * (n_nodes + 4) * 4);
-  lo.g_csr = take((size_t)cap * 4);
-  lo.g_flags = take((size_t)cap * 8);
-  lo.b_idx = take((size_t)cap * 4); lo.b_u = take((size_t)cap * 4); lo.b_v = take((size_t)cap * 4); lo.b_p = take((size_t)cap * 4);
-  lo.g_wcc = take((size_t)(n_nodes + 4) * 4); lo.g_dirty = take((size_t)(n_nodes + 4) * 4);
-  lo.total = off;
-  return lo;
+  auto take = [&](auto*& field, size_t count) {
+    if (ws) field = reinterpret_cast<decltype(field + 0)>(ws + off);
+    off = (off + count * sizeof(*field) + 255) / 256 * 256;
+  };
+  take(p.hdr, 16); take(p.block_count, (size_t)(nb > 0 ? nb : 1));
+  take(p.a_idx, cap); take(p.a_u, cap); take(p.a_v, cap); take(p.a_p, cap); take(p.a_slot, cap);
+  take(p.alive, cap); take(p.mark, cap);
+  take(p.g_node, kPpNodeArrays * nodes); take(p.g_csr, cap); take(p.g_flags, 2 * cap);
+  take(p.b_idx, cap); take(p.b_u, cap); take(p.b_v, cap); take(p.b_p, cap);
+  take(p.g_wcc, nodes); take(p.g_dirty, nodes);
+  return off;
 }
 
 size_t pp_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t max_active) {
-  const int64_t cap = (max_active > 0 && max_active < n_edges) ? max_active : n_edges;
-  return pp_layout(n_nodes, n_edges, cap > 0 ? cap : 1).total;
+  PpParams p;
+  p.n_nodes = n_nodes; p.n_edges = n_edges;
+  return pp_carve(p, max_active, nullptr);
 }
 
 int launch_postprocess(const float* logits, const int64_t* row, const int64_t* col, int64_t idx_stride, int64_t n_nodes,
                        int64_t n_edges, int num_cameras, int flags, int64_t max_active, float* prob1, int64_t* pred,
                        int64_t* id_pred, int32_t* info, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  int64_t cap = (max_active > 0 && max_active < n_edges) ? max_active : n_edges;
-  if (cap < 1) cap = 1;
-  const PpLayout lo = pp_layout(n_nodes, n_edges, cap);
-  if (workspace_bytes < lo.total) return MTMC_E_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
   PpParams p;
   p.logits = logits; p.row = row; p.col = col; p.idx_stride = idx_stride; p.n_nodes = n_nodes; p.n_edges = n_edges;
   p.num_cameras = num_cameras; p.flags = flags; p.prob1 = prob1; p.pred = pred; p.id_pred = id_pred; p.info = info;
-  p.hdr = reinterpret_cast<int*>(ws + lo.hdr); p.block_count = reinterpret_cast<int*>(ws + lo.block_count);
-  p.a_idx = reinterpret_cast<int*>(ws + lo.a_idx); p.a_u = reinterpret_cast<int*>(ws + lo.a_u);
-  p.a_v = reinterpret_cast<int*>(ws + lo.a_v); p.a_p = reinterpret_cast<float*>(ws + lo.a_p);
-  p.a_slot = reinterpret_cast<int*>(ws + lo.a_slot); p.alive = reinterpret_cast<unsigned char*>(ws + lo.alive);
-  p.mark = reinterpret_cast<unsigned char*>(ws + lo.mark); p.g_node = reinterpret_cast<int*>(ws + lo.g_node);
-  p.g_csr = reinterpret_cast<unsigned*>(ws + lo.g_csr); p.cap = cap;
-  p.g_flags = reinterpret_cast<int*>(ws + lo.g_flags); p.b_idx = reinterpret_cast<int*>(ws + lo.b_idx);
-  p.b_u = reinterpret_cast<int*>(ws + lo.b_u); p.b_v = reinterpret_cast<int*>(ws + lo.b_v);
-  p.b_p = reinterpret_cast<float*>(ws + lo.b_p);
-  p.g_wcc = reinterpret_cast<int*>(ws + lo.g_wcc); p.g_dirty = reinterpret_cast<int*>(ws + lo.g_dirty);
+  if (workspace_bytes < pp_carve(p, max_active, nullptr)) return MTMC_E_WORKSPACE;
+  pp_carve(p, max_active, static_cast<char*>(workspace));
   const int nb = (int)((n_edges + kPpChunk - 1) / kPpChunk);
   if (nb > 0) hipLaunchKernelGGL(pp_classify_kernel, dim3(nb), dim3(256), 0, s, p);
   hipLaunchKernelGGL(pp_scan_kernel, dim3(1), dim3(1024), 0, s, p, nb);
@@ -719,13 +723,8 @@ int launch_postprocess(const float* logits, const int64_t* row, const int64_t* c
   const int lds_nodes = n_nodes <= kPpLdsNodes ? 1 : 0;
   const size_t npad = ((size_t)n_nodes + 4) & ~(size_t)3;
   const size_t lds = (lds_nodes ? kPpNodeArrays * npad * sizeof(int) : 0) + (size_t)kPpLdsEdges * sizeof(unsigned);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(pp_graph_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (kPpNodeArrays * (kPpLdsNodes + 4) + kPpLdsEdges) * 4) != hipSuccess)
-      return MTMC_E_HIP;
-    attr_set = true;
-  }
+  if (!allow_big_lds(reinterpret_cast<const void*>(pp_graph_kernel), (kPpNodeArrays * (kPpLdsNodes + 4) + kPpLdsEdges) * 4))
+    return MTMC_E_HIP;
   hipLaunchKernelGGL(pp_graph_kernel, dim3(1), dim3(kPpThreads), lds, s, p, lds_nodes);
   return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
 }

@@ -91,3 +91,28 @@ def test_out_of_range_node_ids_are_clamped_and_reported():
     out = mtmc_mpn.postprocess(logits, ei, 3, 2, check=False)                # no fault, no exception without the check
     torch.cuda.synchronize()
     assert out.info_dev.cpu()[3].item() == 4
+
+
+def _vs_oracle(kw, flags):
+    s = pp_cases.scenario(**kw)
+    out = mtmc_mpn.postprocess(s.logits.to(DEV), s.edge_index.to(DEV), s.n_nodes, s.n_cams, *flags)
+    p1 = out.preds_prob1.cpu()
+    ids, pred = po.post_processing(s.n_cams, torch.argmax(s.logits, 1), s.edge_index, s.n_nodes,
+                                   torch.stack([1 - p1, p1], dim=1), *flags)
+    assert torch.equal(out.predictions.cpu(), pred), kw
+    assert torch.equal(out.ID_pred.cpu(), ids), kw
+    return s, out
+
+
+def test_csr_moves_from_global_memory_to_lds_after_compaction():
+    """More than 8192 active edges come in (first CSR in global memory), at most 8192 survive cut / prune / cut
+    (second CSR, and every walk, in LDS)."""
+    s, out = _vs_oracle(dict(n_ids=250, n_cams=4, seed=46, fp_rate=0.006, fn_rate=0.05, pair_fp=0.0), (True, True, True))
+    assert s.n_nodes <= 2048 and out.info["active_in"] > 8192 and out.info["active_out"] <= 8192, (s.n_nodes, out.info)
+
+
+def test_node_arrays_in_lds_csr_in_global_memory():
+    """N <= 2048 with more than 8192 surviving edges: the walk runs on generic pointers over LDS node arrays and a
+    global-memory CSR."""
+    s, out = _vs_oracle(dict(n_ids=400, n_cams=6, seed=48, fp_rate=0.0, fn_rate=0.01, pair_fp=0.0002), (True, False, False))
+    assert s.n_nodes <= 2048 and out.info["active_out"] > 8192, (s.n_nodes, out.info)
