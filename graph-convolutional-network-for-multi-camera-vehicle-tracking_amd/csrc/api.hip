@@ -203,36 +203,34 @@ int32_t mtmc_mpn_forward(const mtmc_mpn_model* model, const mtmc_mpn_call* call)
   return run_phase(x, MTMC_PH_END, 0);
 }
 
-static int scatter_common(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                          float* out, float* count, int64_t* arg_out, int mode, void* stream) {
+static int scatter_common(const char* entry, const float* src, const int64_t* index, int64_t n_src, int64_t n_cols,
+                          int64_t dim_size, float* out, float* count, int64_t* arg_out, int mode, void* stream) {
   if (n_src < 0 || n_cols < 1 || dim_size < 0 || !out || (n_src > 0 && (!src || !index)))
-    return fail(MTMC_E_ARG, "bad scatter arguments");
-  if (mode == 1 && !count) return fail(MTMC_E_ARG, "scatter_mean needs count_scratch[dim_size]");
+    return fail(MTMC_E_ARG, "%s: n_src and dim_size must be >= 0, n_cols >= 1, and out (with rows: src and index) not NULL", entry);
+  if (mode == 1 && !count) return fail(MTMC_E_ARG, "%s: needs count_scratch[dim_size]", entry);
   if (dim_size == 0) return MTMC_OK;
   mtmc::launch_scatter(src, index, n_src, n_cols, dim_size, out, count, arg_out, mode, static_cast<hipStream_t>(stream));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "scatter launch failed: %s", hipGetErrorString(e));
+  return launched(entry);
 }
 int32_t mtmc_scatter_add(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                          float* out, void* stream) {
-  return scatter_common(src, index, n_src, n_cols, dim_size, out, nullptr, nullptr, 0, stream);
+  return scatter_common("scatter_add", src, index, n_src, n_cols, dim_size, out, nullptr, nullptr, 0, stream);
 }
 int32_t mtmc_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                              int64_t* out, void* stream) {
   if (n_src < 0 || n_cols < 1 || dim_size < 0 || !out || (n_src > 0 && (!src || !index)))
-    return fail(MTMC_E_ARG, "bad scatter arguments");
+    return fail(MTMC_E_ARG, "scatter_add_i64: n_src and dim_size must be >= 0, n_cols >= 1, and out (with rows: src and index) not NULL");
   if (dim_size == 0) return MTMC_OK;
   mtmc::launch_scatter_add_i64(src, index, n_src, n_cols, dim_size, out, static_cast<hipStream_t>(stream));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "scatter launch failed: %s", hipGetErrorString(e));
+  return launched("scatter_add_i64");
 }
 int32_t mtmc_scatter_mean(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                           float* out, float* count_scratch, void* stream) {
-  return scatter_common(src, index, n_src, n_cols, dim_size, out, count_scratch, nullptr, 1, stream);
+  return scatter_common("scatter_mean", src, index, n_src, n_cols, dim_size, out, count_scratch, nullptr, 1, stream);
 }
 int32_t mtmc_scatter_max(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                          float* out, int64_t* arg_out, void* stream) {
-  return scatter_common(src, index, n_src, n_cols, dim_size, out, nullptr, arg_out, 2, stream);
+  return scatter_common("scatter_max", src, index, n_src, n_cols, dim_size, out, nullptr, arg_out, 2, stream);
 }
 
 int32_t mtmc_mlp_layer_forward(const mtmc_layer* layer, const float* x, int64_t x_row_stride, int64_t rows, float* y,

@@ -1,30 +1,17 @@
 // Internals shared by the C-ABI translation units (api.hip: forward + phases, api_train.hip: backward):
 // error text, workspace carving, per-phase parameter blocks and the phase launcher.
 #pragma once
+#include "api_error.h"
 #include "kernels.h"
 #include "train_kernels.h"
 
 #include <mutex>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
 
 namespace mtmc_api {
-
-
-inline thread_local char g_err[512] = "";
-
-inline int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-inline int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 

@@ -15,8 +15,8 @@
 // Every fp64 sum over slots or pairs is kept in 2^-55 fixed point in a 64-bit integer: which slot a key lands in depends
 // on the order of the insertions, integer addition does not, so the scores are the same bits on every run.  All the
 // sums are bounded by a few times ln n < 14, far from 2^8.
-#include "common.h"
-#include "../../include/mtmc_mpn.h"
+#include "api_error.h"
+#include "kernels.h"
 
 namespace mtmc {
 
@@ -100,22 +100,6 @@ __device__ __forceinline__ long long cs_term(uint32_t c, double n, double num, d
   return cs_fixed((double)c / n * log(num / den));
 }
 
-// adds v[0..NV) of the whole workgroup to dst[0..NV): shuffles inside a wave, LDS across the waves, one atomic per word
-template <int NV>
-__device__ __forceinline__ void cs_block_add(const long long (&v)[NV], u64* dst, u64* smem) {
-  if (threadIdx.x < NV) smem[threadIdx.x] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    long long x = v[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    if ((threadIdx.x & 63) == 0 && x) atomicAdd(smem + j, (u64)x);
-  }
-  __syncthreads();
-  if (threadIdx.x < NV && smem[threadIdx.x]) atomicAdd(dst + threadIdx.x, smem[threadIdx.x]);
-}
-
 __global__ __launch_bounds__(256) void cs_reduce_kernel(int64_t n, u64 cap, const u64* ckey, const uint32_t* tcnt,
                                                         const uint32_t* pcnt, const uint32_t* ccnt, uint32_t* hist_t,
                                                         uint32_t* hist_p, u64* acc) {
@@ -146,7 +130,7 @@ __global__ __launch_bounds__(256) void cs_reduce_kernel(int64_t n, u64 cap, cons
         v[kCsMi] += cs_term(c, dn, dn * (double)c, (double)tcnt[row] * (double)pcnt[col]);
     }
   }
-  cs_block_add<kCsMi + 1>(v, acc, smem);
+  block_count_add<kCsMi + 1>(v, acc, smem);
 }
 
 __global__ __launch_bounds__(256) void cs_sizes_kernel(int64_t n, const uint32_t* hist_t, const uint32_t* hist_p,
@@ -238,33 +222,18 @@ __global__ void cs_finalize_kernel(int64_t n, const u64* acc, double* scores, lo
   counts[3] = tp; counts[4] = fp; counts[5] = fn; counts[6] = tn;
 }
 
-static inline int cs_grid(int64_t items, int cap) {
-  const int64_t b = (items + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 // ---- mtmc_edge_prf: compute_P_R_F (reference inference.py:23-68) without its boolean-mask indexing -------------------
 __global__ __launch_bounds__(256) void prf_count_kernel(const int64_t* pred, int64_t sp, const int64_t* labels, int64_t sl,
                                                         int64_t n, u64* counts) {
   __shared__ unsigned int sh[4];
-  if (threadIdx.x < 4) sh[threadIdx.x] = 0;
-  __syncthreads();
   unsigned int c[4] = {0, 0, 0, 0};                  // at most 2^31 / (256 threads) rows per thread
   const int64_t nthreads = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
     const int64_t y = labels[i * sl], p = pred[i * sp];
     if ((y != 0 && y != 1) || (p != 0 && p != 1)) continue;
-    ++c[y == 1 ? (p ? 0 : 3) : (p ? 1 : 2)];
+    ++c[confusion_slot(y == 1, p == 1)];
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    unsigned int v = c[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&sh[j], v);
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 && sh[threadIdx.x]) atomicAdd(counts + threadIdx.x, (u64)sh[threadIdx.x]);
+  block_count_add<4>(c, counts, sh);
 }
 
 __global__ void prf_finalize_kernel(const long long* counts, double* out) {
@@ -289,41 +258,49 @@ int32_t mtmc_cluster_scores(const int64_t* labels_true, int64_t stride_true, con
                             int64_t n, double* scores, int64_t* counts, void* workspace, size_t workspace_bytes,
                             void* stream) {
   using namespace mtmc;
-  if (n < 1 || n > kCsMaxN || !labels_true || !labels_pred || !scores || !counts || !workspace) return MTMC_E_ARG;
-  if (stride_true < 0 || stride_pred < 0 || ((uintptr_t)workspace & 7)) return MTMC_E_ARG;
+  using mtmc_api::fail;
+  if (n < 1 || n > kCsMaxN) return fail(MTMC_E_ARG, "cluster_scores: n must be in [1, %lld]", (long long)kCsMaxN);
+  if (!labels_true || !labels_pred || !scores || !counts || !workspace)
+    return fail(MTMC_E_ARG, "cluster_scores: NULL labels_true, labels_pred, scores, counts or workspace");
+  if (stride_true < 0 || stride_pred < 0 || ((uintptr_t)workspace & 7))
+    return fail(MTMC_E_ARG, "cluster_scores: the strides must be >= 0 and the workspace 8-byte aligned");
   const CsLayout lo = cs_layout(n);
-  if (workspace_bytes < lo.total) return MTMC_E_ARG;
+  if (workspace_bytes < lo.total)
+    return fail(MTMC_E_ARG, "cluster_scores: workspace has %zu bytes, %zu needed (mtmc_cluster_scores_workspace_bytes)",
+                workspace_bytes, lo.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(workspace);
-  if (hipMemsetAsync(ws, 0, lo.zero_bytes, s) != hipSuccess) return MTMC_E_HIP;
+  if (hipMemsetAsync(ws, 0, lo.zero_bytes, s) != hipSuccess) return fail(MTMC_E_HIP, "cluster_scores: hipMemsetAsync failed");
   u64 *tkey = (u64*)(ws + lo.tkey), *pkey = (u64*)(ws + lo.pkey), *ckey = (u64*)(ws + lo.ckey), *acc = (u64*)(ws + lo.acc);
   uint32_t *tcnt = (uint32_t*)(ws + lo.tcnt), *pcnt = (uint32_t*)(ws + lo.pcnt), *ccnt = (uint32_t*)(ws + lo.ccnt);
   uint32_t *hist_t = (uint32_t*)(ws + lo.hist_t), *hist_p = (uint32_t*)(ws + lo.hist_p), *sizes = (uint32_t*)(ws + lo.sizes);
   double* lg = (double*)(ws + lo.lg);
   const u64 cap = (u64)lo.cap;
-  hipLaunchKernelGGL(cs_insert_kernel, dim3(cs_grid(n, 1024)), dim3(256), 0, s, labels_true, stride_true, labels_pred,
+  hipLaunchKernelGGL(cs_insert_kernel, dim3(blocks_for(n, 256, 1024)), dim3(256), 0, s, labels_true, stride_true, labels_pred,
                      stride_pred, n, cap, tkey, pkey, ckey, tcnt, pcnt, ccnt);
-  hipLaunchKernelGGL(cs_reduce_kernel, dim3(cs_grid(lo.cap + 1, 512)), dim3(256), 0, s, n, cap, (const u64*)ckey,
+  hipLaunchKernelGGL(cs_reduce_kernel, dim3(blocks_for(lo.cap + 1, 256, 512)), dim3(256), 0, s, n, cap, (const u64*)ckey,
                      (const uint32_t*)tcnt, (const uint32_t*)pcnt, (const uint32_t*)ccnt, hist_t, hist_p, acc);
-  hipLaunchKernelGGL(cs_sizes_kernel, dim3(cs_grid(n + 1, 1024)), dim3(256), 0, s, n, (const uint32_t*)hist_t,
+  hipLaunchKernelGGL(cs_sizes_kernel, dim3(blocks_for(n + 1, 256, 1024)), dim3(256), 0, s, n, (const uint32_t*)hist_t,
                      (const uint32_t*)hist_p, sizes, lg, acc);
   hipLaunchKernelGGL(cs_emi_kernel, dim3(512), dim3(256), 0, s, n, (const uint32_t*)sizes, (const double*)lg, acc);
   hipLaunchKernelGGL(cs_finalize_kernel, dim3(1), dim3(1), 0, s, n, (const u64*)acc, scores,
                      reinterpret_cast<long long*>(counts));
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return mtmc_api::launched("cluster_scores");
 }
 
 int32_t mtmc_edge_prf(const int64_t* predictions, int64_t stride_pred, const int64_t* labels, int64_t stride_labels,
                       int64_t n_edges, int64_t* counts, double* out, void* stream) {
-  if (n_edges < 0 || !counts || !out || stride_pred < 0 || stride_labels < 0) return MTMC_E_ARG;
-  if (n_edges > 0 && (!predictions || !labels)) return MTMC_E_ARG;
+  using mtmc_api::fail;
+  if (n_edges < 0 || stride_pred < 0 || stride_labels < 0) return fail(MTMC_E_ARG, "edge_prf: n_edges and the strides must be >= 0");
+  if (!counts || !out || (n_edges > 0 && (!predictions || !labels)))
+    return fail(MTMC_E_ARG, "edge_prf: NULL counts or out, or NULL predictions or labels with n_edges > 0");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) return MTMC_E_HIP;
+  if (hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) return fail(MTMC_E_HIP, "edge_prf: hipMemsetAsync failed");
   if (n_edges > 0)
-    hipLaunchKernelGGL(mtmc::prf_count_kernel, dim3(mtmc::cs_grid(n_edges, 256)), dim3(256), 0, s, predictions, stride_pred,
+    hipLaunchKernelGGL(mtmc::prf_count_kernel, dim3(mtmc::blocks_for(n_edges, 256, 256)), dim3(256), 0, s, predictions, stride_pred,
                        labels, stride_labels, n_edges, reinterpret_cast<mtmc::u64*>(counts));
   hipLaunchKernelGGL(mtmc::prf_finalize_kernel, dim3(1), dim3(1), 0, s, reinterpret_cast<const long long*>(counts), out);
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return mtmc_api::launched("edge_prf");
 }
 
 }  // extern "C"

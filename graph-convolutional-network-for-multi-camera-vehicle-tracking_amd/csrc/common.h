@@ -214,6 +214,30 @@ __device__ __forceinline__ void block_atomic_add(const double (&v)[NV], double* 
   __syncthreads();
 }
 
+// Block-wide sum of NV per-thread integers, added to dst[0 .. NV): shuffles inside a wave, LDS across the waves, one 64-bit
+// atomic per non-zero word.  T = unsigned: 32-bit counters in 32-bit LDS words (a workgroup's total stays below 2^32);
+// T = long long: 64-bit values in 64-bit words, added modulo 2^64 (signed fixed point included).  smem: NV words.  All
+// threads must call; ends with a barrier, so a caller may use smem again in a loop.
+template <int NV, typename T, typename Smem>
+__device__ __forceinline__ void block_count_add(const T (&v)[NV], unsigned long long* dst, Smem* smem) {
+  static_assert(sizeof(Smem) == sizeof(T) && (sizeof(T) == 4 || sizeof(T) == 8), "one LDS word per value, of its width");
+  if (threadIdx.x < NV) smem[threadIdx.x] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    T x = v[j];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    if ((threadIdx.x & 63) == 0 && x) atomicAdd(smem + j, (Smem)x);
+  }
+  __syncthreads();
+  if (threadIdx.x < NV && smem[threadIdx.x]) atomicAdd(dst + threadIdx.x, (unsigned long long)smem[threadIdx.x]);
+  __syncthreads();
+}
+
+// where one (label, prediction) pair counts in a {TP, FP, TN, FN} vector
+__device__ __forceinline__ int confusion_slot(bool y, bool pred) { return y ? (pred ? 0 : 3) : (pred ? 1 : 2); }
+
 // BatchNorm (batch statistics) as y = s*z + t from fp64 (sum, sumsq) over `count` rows.
 // Latency matters (this sits in kernel prologues): no fp64 division or square root -- multiply by 1/count,
 // take v_rsq_f32 of the variance and polish it with one fp64 Newton step (error ~1e-14 relative).

@@ -6,6 +6,7 @@
 // The per-edge 2048-d gather (16 KB per edge in the reference) becomes ONE Gram matrix G = X X^T on the fp32
 // matrix cores (gemm_bn_kernel) plus an 8-byte-per-edge epilogue:
 //     ||a-b+eps||^2 = |a|^2 + |b|^2 - 2 a.b + 2 eps (sum a - sum b) + F eps^2,    cos = a.b / (max(|a|,e) max(|b|,e))
+#include "api_error.h"
 #include "kernels.h"
 
 namespace mtmc {
@@ -416,6 +417,9 @@ GBLayout graph_bwd_layout(int64_t n, int f) {
 
 extern "C" {
 
+using mtmc_api::fail;
+using mtmc_api::launched;
+
 size_t mtmc_graph_workspace_bytes(int64_t n_nodes, int32_t feat_dim) {
   if (n_nodes < 1 || n_nodes > 46000 || feat_dim < 32) return 0;
   return graph_layout(n_nodes, feat_dim).total;
@@ -426,12 +430,19 @@ int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_
                          const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
                          float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                          void* workspace, size_t workspace_bytes, void* stream) {
-  if (!feats || !x_out || n_nodes < 1 || n_nodes > 46000 || feat_dim % 32 != 0 || feat_dim < 32 || n_cams < 1) return MTMC_E_ARG;
-  if (n_edges > 0 && (!in_list || !in_off || !out_list || !out_off || !block_off || !edge_index_out || !edge_attr_out)) return MTMC_E_ARG;
-  if (edge_labels_out && !node_labels) return MTMC_E_ARG;
-  if (((uintptr_t)feats & 15) || (feat_row_stride & 3) || ((uintptr_t)x_out & 15) || ((uintptr_t)workspace & 255)) return MTMC_E_ARG;
+  if (!feats || !x_out) return fail(MTMC_E_ARG, "build_graph: NULL feats or x_out");
+  if (n_nodes < 1 || n_nodes > 46000 || feat_dim % 32 != 0 || feat_dim < 32 || n_cams < 1)
+    return fail(MTMC_E_ARG, "build_graph: n_nodes must be in [1, 46000], feat_dim a multiple of 32 and n_cams >= 1");
+  if (n_edges > 0 && (!in_list || !in_off || !out_list || !out_off || !block_off || !edge_index_out || !edge_attr_out))
+    return fail(MTMC_E_ARG, "build_graph: NULL camera table or edge output with n_edges > 0");
+  if (edge_labels_out && !node_labels) return fail(MTMC_E_ARG, "build_graph: edge_labels_out needs node_labels");
+  if (((uintptr_t)feats & 15) || (feat_row_stride & 3) || ((uintptr_t)x_out & 15) || ((uintptr_t)workspace & 255))
+    return fail(MTMC_E_ARG, "build_graph: feats and x_out must be 16-byte and the workspace 256-byte aligned, the row stride a "
+                            "multiple of 4");
   const GLayout l = graph_layout(n_nodes, feat_dim);
-  if (!workspace || workspace_bytes < l.total) return MTMC_E_WORKSPACE;
+  if (!workspace || workspace_bytes < l.total)
+    return fail(MTMC_E_WORKSPACE, "build_graph: workspace has %zu bytes, %zu needed (mtmc_graph_workspace_bytes)",
+                workspace ? workspace_bytes : (size_t)0, l.total);
   char* ws = static_cast<char*>(workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* colsq = reinterpret_cast<double*>(ws + l.colsq);
@@ -439,8 +450,9 @@ int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_
   float* row_sum = reinterpret_cast<float*>(ws + l.row_sum);
   float* G = reinterpret_cast<float*>(ws + l.G);
   float* zeros = reinterpret_cast<float*>(ws + l.zeros);
-  if (hipMemsetAsync(colsq, 0, (size_t)feat_dim * sizeof(double), s) != hipSuccess) return MTMC_E_HIP;
-  if (hipMemsetAsync(zeros, 0, (size_t)n_nodes * sizeof(float), s) != hipSuccess) return MTMC_E_HIP;
+  if (hipMemsetAsync(colsq, 0, (size_t)feat_dim * sizeof(double), s) != hipSuccess ||
+      hipMemsetAsync(zeros, 0, (size_t)n_nodes * sizeof(float), s) != hipSuccess)
+    return fail(MTMC_E_HIP, "build_graph: hipMemsetAsync failed");
   if (l2norm)
     hipLaunchKernelGGL(mtmc::gb_colnorm_kernel, dim3((feat_dim + 63) / 64, (unsigned)((n_nodes + 63) / 64)), dim3(256), 0, s,
                        feats, feat_row_stride, n_nodes, feat_dim, colsq);
@@ -451,16 +463,15 @@ int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_
     int sk = 1;
     mtmc::gemm_plan(n_nodes, feat_dim, (int)n_nodes, &sk);
     if (sk > 1 && l.slab != l.total) g.slab = reinterpret_cast<float*>(ws + l.slab);
-    if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return MTMC_E_ARG;
+    if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "build_graph: the Gram-matrix GEMM refused its shape");
     mtmc::EdgeBuildParams p;
     p.in_list = in_list; p.in_off = in_off; p.out_list = out_list; p.out_off = out_off; p.block_off = block_off;
     p.n_cams = n_cams; p.n_nodes = n_nodes; p.n_edges = n_edges; p.f = feat_dim;
     p.G = G; p.row_sq = row_sq; p.row_sum = row_sum; p.node_labels = node_labels;
     p.edge_index = edge_index_out; p.edge_attr = edge_attr_out; p.edge_labels = edge_labels_out;
-    const int64_t blocks = (n_edges + 255) / 256;
-    hipLaunchKernelGGL(mtmc::gb_edges_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(mtmc::gb_edges_kernel, dim3(mtmc::blocks_for(n_edges, 256, 4096)), dim3(256), 0, s, p);
   }
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("build_graph");
 }
 
 size_t mtmc_graph_backward_workspace_bytes(int64_t n_nodes, int32_t feat_dim) {
@@ -473,15 +484,22 @@ int32_t mtmc_build_graph_backward(const float* feats, int64_t feat_row_stride, i
                                   const int64_t* out_off, const int64_t* block_off, int32_t n_cams, int64_t n_edges,
                                   const float* x, const float* edge_attr, const float* d_x, const float* d_edge_attr,
                                   float* d_feats_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!feats || !x || !d_feats_out || n_nodes < 1 || n_nodes > 46000 || feat_dim % 32 != 0 || feat_dim < 32 || n_cams < 1) return MTMC_E_ARG;
-  if (n_edges < 0 || (n_edges > 0 && (!in_list || !in_off || !out_list || !out_off || !block_off || !edge_attr))) return MTMC_E_ARG;
-  if (n_edges > 0 && !d_x && !d_edge_attr) return MTMC_E_ARG;
-  if (d_x == d_feats_out || x == d_feats_out) return MTMC_E_ARG;
+  if (!feats || !x || !d_feats_out) return fail(MTMC_E_ARG, "build_graph_backward: NULL feats, x or d_feats_out");
+  if (n_nodes < 1 || n_nodes > 46000 || feat_dim % 32 != 0 || feat_dim < 32 || n_cams < 1 || n_edges < 0)
+    return fail(MTMC_E_ARG, "build_graph_backward: n_nodes must be in [1, 46000], feat_dim a multiple of 32, n_cams >= 1 and "
+                            "n_edges >= 0");
+  if (n_edges > 0 && (!in_list || !in_off || !out_list || !out_off || !block_off || !edge_attr))
+    return fail(MTMC_E_ARG, "build_graph_backward: NULL camera table or edge_attr with n_edges > 0");
+  if (n_edges > 0 && !d_x && !d_edge_attr) return fail(MTMC_E_ARG, "build_graph_backward: neither d_x nor d_edge_attr is given");
+  if (d_x == d_feats_out || x == d_feats_out) return fail(MTMC_E_ARG, "build_graph_backward: d_feats_out must not alias x or d_x");
   if (((uintptr_t)feats & 15) || (feat_row_stride & 3) || ((uintptr_t)x & 15) || ((uintptr_t)d_x & 15) ||
       ((uintptr_t)d_feats_out & 15) || ((uintptr_t)edge_attr & 7) || ((uintptr_t)d_edge_attr & 7) || ((uintptr_t)workspace & 255))
-    return MTMC_E_ARG;
+    return fail(MTMC_E_ARG, "build_graph_backward: feats, x, d_x and d_feats_out must be 16-byte, edge_attr and d_edge_attr "
+                            "8-byte and the workspace 256-byte aligned, the row stride a multiple of 4");
   const GBLayout l = graph_bwd_layout(n_nodes, feat_dim);
-  if (!workspace || workspace_bytes < l.total) return MTMC_E_WORKSPACE;
+  if (!workspace || workspace_bytes < l.total)
+    return fail(MTMC_E_WORKSPACE, "build_graph_backward: workspace has %zu bytes, %zu needed (mtmc_graph_backward_workspace_bytes)",
+                workspace ? workspace_bytes : (size_t)0, l.total);
   char* ws = static_cast<char*>(workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* colsq = reinterpret_cast<double*>(ws + l.colsq);
@@ -498,8 +516,9 @@ int32_t mtmc_build_graph_backward(const float* feats, int64_t feat_row_stride, i
     c.S = reinterpret_cast<float*>(ws + l.S);
     c.delta = reinterpret_cast<float*>(ws + l.delta); c.kappa = reinterpret_cast<float*>(ws + l.kappa);
     c.X = x; c.out = d_feats_out; c.f = feat_dim;
-    if (hipMemsetAsync(c.S, 0, (size_t)n_nodes * l.npad * sizeof(float), s) != hipSuccess) return MTMC_E_HIP;
-    if (hipMemsetAsync(node_cam, 0xFF, (size_t)n_nodes * sizeof(int), s) != hipSuccess) return MTMC_E_HIP;
+    if (hipMemsetAsync(c.S, 0, (size_t)n_nodes * l.npad * sizeof(float), s) != hipSuccess ||
+        hipMemsetAsync(node_cam, 0xFF, (size_t)n_nodes * sizeof(int), s) != hipSuccess)
+      return fail(MTMC_E_HIP, "build_graph_backward: hipMemsetAsync failed");
     hipLaunchKernelGGL(mtmc::gb_bwd_nodemap_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, in_list, in_off,
                        n_cams, n_nodes, node_cam, node_loc);
     hipLaunchKernelGGL(mtmc::gb_bwd_rownorm_kernel, dim3((unsigned)n_nodes), dim3(256), 0, s, x, feat_dim, rho);
@@ -510,20 +529,21 @@ int32_t mtmc_build_graph_backward(const float* feats, int64_t feat_row_stride, i
     hipLaunchKernelGGL(mtmc::gb_bwd_gemm_kernel, dim3((feat_dim + 63) / 64, (unsigned)((n_nodes + 63) / 64)), dim3(256), 0, s, g);
     hipLaunchKernelGGL(mtmc::gb_bwd_near_kernel, dim3((unsigned)n_nodes), dim3(256), 0, s, c);
   } else if (d_x) {                                   // no edge gradient: dXn = gX
-    if (hipMemcpyAsync(d_feats_out, d_x, nf_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return MTMC_E_HIP;
+    if (hipMemcpyAsync(d_feats_out, d_x, nf_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return fail(MTMC_E_HIP, "build_graph_backward: hipMemcpyAsync failed");
   } else {
-    if (hipMemsetAsync(d_feats_out, 0, nf_bytes, s) != hipSuccess) return MTMC_E_HIP;
+    if (hipMemsetAsync(d_feats_out, 0, nf_bytes, s) != hipSuccess) return fail(MTMC_E_HIP, "build_graph_backward: hipMemsetAsync failed");
   }
   if (l2norm) {
-    if (hipMemsetAsync(colsq, 0, (size_t)2 * feat_dim * sizeof(double), s) != hipSuccess) return MTMC_E_HIP;
+    if (hipMemsetAsync(colsq, 0, (size_t)2 * feat_dim * sizeof(double), s) != hipSuccess)
+      return fail(MTMC_E_HIP, "build_graph_backward: hipMemsetAsync failed");
     const dim3 col_grid((feat_dim + 63) / 64, (unsigned)((n_nodes + 63) / 64));
     hipLaunchKernelGGL(mtmc::gb_colnorm_kernel, col_grid, dim3(256), 0, s, feats, feat_row_stride, n_nodes, feat_dim, colsq);
     hipLaunchKernelGGL(mtmc::gb_bwd_coldot_kernel, col_grid, dim3(256), 0, s, x, d_feats_out, n_nodes, feat_dim, dot);
-    const int64_t blocks = ((int64_t)n_nodes * feat_dim / 4 + 255) / 256;
-    hipLaunchKernelGGL(mtmc::gb_bwd_normalize_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, x,
-                       n_nodes, feat_dim, colsq, dot, d_feats_out);
+    hipLaunchKernelGGL(mtmc::gb_bwd_normalize_kernel, dim3(mtmc::blocks_for((int64_t)n_nodes * feat_dim / 4, 256, 4096)),
+                       dim3(256), 0, s, x, n_nodes, feat_dim, colsq, dot, d_feats_out);
   }
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("build_graph_backward");
 }
 
 }  // extern "C"

@@ -32,6 +32,13 @@ struct Knobs {
 };
 const Knobs& knobs();
 
+// Workgroups of a grid-stride launch over `items`: ceil(items / per_block), at least 1, at most `cap`.  The stand-alone
+// operators size their grids with it; every site keeps its own cap.
+inline int blocks_for(int64_t items, int per_block, int cap) {
+  const int64_t b = (items + per_block - 1) / per_block;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
 // |.|max of a [rows][cols] fp32 matrix (row stride ld), accumulated with atomicMax on the bit pattern: scales of the
 // fp16 two-piece node-encoder GEMM.  Done by extra workgroups of prep_kernel, i.e. without a launch of its own.
 constexpr int kAmaxRep = 16;   // replicas of every |.|max word: same-address atomics serialise in L2

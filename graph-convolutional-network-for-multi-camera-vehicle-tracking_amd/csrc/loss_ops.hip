@@ -5,8 +5,8 @@
 //   forward : l_i = w[y_i] * (logsumexp(x_i) - x_i[y_i]);  sums = (sum_i l_i, sum_i w[y_i])  in fp64
 //   backward: d x_i[c] = g_i * w[y_i] * (softmax(x_i)[c] - [c == y_i]),
 //             g_i = grad / sum_w (mean), grad (sum), grad_i (none);  rows with y_i == ignore_index contribute nothing
+#include "api_error.h"
 #include "kernels.h"
-#include "../../include/mtmc_mpn.h"
 
 namespace mtmc {
 
@@ -81,8 +81,6 @@ __global__ __launch_bounds__(256) void ce_backward_kernel(const float* logits, c
 __global__ __launch_bounds__(256) void confusion_kernel(const float* logits, const int64_t* labels, int64_t n, int C,
                                                         unsigned long long* counts) {
   __shared__ unsigned int sh[4];
-  if (threadIdx.x < 4) sh[threadIdx.x] = 0;
-  __syncthreads();
   unsigned int c[4] = {0, 0, 0, 0};
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthreads) {
@@ -91,31 +89,15 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* logits, con
     int best = 0;
     float bv = logits[i * C];
     for (int k = 1; k < C; ++k) { const float v = logits[i * C + k]; if (v > bv) { bv = v; best = k; } }   // first maximum
-    const int pred = best == 1;
-    ++c[y == 1 ? (pred ? 0 : 3) : (pred ? 1 : 2)];
+    ++c[confusion_slot(y == 1, best == 1)];
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    unsigned int v = c[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&sh[j], v);
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 && sh[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)sh[threadIdx.x]);
+  block_count_add<4>(c, counts, sh);
 }
 
-static inline int ce_grid(int64_t n) {
-  const int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
-// the forward ends in two fp64 atomics per workgroup on 16 replicas: 2048 workgroups of one row per thread spent most of
-// their 14.6 us (3 x 173k rows) queueing on those 32 words; 512 workgroups, four rows per thread there
-static inline int ce_grid_fwd(int64_t n) {
-  const int g = ce_grid(n);
-  return g > 512 ? 512 : g;
-}
-
+// Most workgroups (of 256 rows) of a launch.  The backward passes: 2048.  The forward ends in two fp64 atomics per workgroup
+// on 16 replicas: 2048 workgroups of one row per thread spent most of their 14.6 us (3 x 173k rows) queueing on those 32
+// words; 512 workgroups, four rows per thread there.  The confusion counts: 256.
+constexpr int kCeBlocks = 2048, kCeBlocksFwd = 512, kConfusionBlocks = 256;
 
 // ---- mtmc_edge_loss_*: loss and metrics of every classified step in one pass (include/mtmc_mpn.h) -------------------
 // Both class counts reduce to one scalar per row, the margin z of the true class (x[y] - x[1-y]; one logit: +-x): the row
@@ -151,8 +133,6 @@ __global__ __launch_bounds__(256) void el_forward_kernel(const float* logits, co
   __shared__ unsigned int cnt[4];
   const int64_t nthreads = (int64_t)gridDim.x * 256;
   for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
-    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
-    __syncthreads();
     const float* x = logits + (int64_t)s * n * C;
     double acc[4] = {0, 0, 0, 0};
     unsigned int c[4] = {0, 0, 0, 0};
@@ -165,22 +145,11 @@ __global__ __launch_bounds__(256) void el_forward_kernel(const float* logits, co
       float l, p, q;
       el_row(z, l, p, q);
       if (y) { acc[1] += l; acc[3] += p; } else { acc[0] += l; acc[2] += p; }
-      c[0] += y && pred; c[1] += !y && pred; c[2] += !y && !pred; c[3] += y && !pred;
+      ++c[confusion_slot(y, pred)];
     }
     double* rep = scratch + (int64_t)s * kStatRep * kElStride;
     block_atomic_add<4>(acc, rep, kElStride, red);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned int v = c[j];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if ((threadIdx.x & 63) == 0 && v) atomicAdd(&cnt[j], v);
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && cnt[threadIdx.x])
-      atomicAdd(reinterpret_cast<unsigned long long*>(rep + (blockIdx.x % kStatRep) * kElStride + 4) + threadIdx.x,
-                (unsigned long long)cnt[threadIdx.x]);
-    __syncthreads();
+    block_count_add<4>(c, reinterpret_cast<unsigned long long*>(rep + (blockIdx.x % kStatRep) * kElStride + 4), cnt);
   }
 }
 
@@ -252,29 +221,34 @@ __global__ __launch_bounds__(256) void el_backward_kernel(const float* logits, c
   }
 }
 
-// x: row blocks up to `cap` workgroups in all (the forward ends in eight 64-bit atomics per workgroup: 512, as ce_grid_fwd)
+// x: row blocks up to `cap` workgroups in all (the forward ends in eight 64-bit atomics per workgroup: 512, as kCeBlocksFwd)
 static inline dim3 el_grid(int64_t n, int n_steps, int cap) {
   const int gy = n_steps < 1024 ? n_steps : 1024;
-  const int64_t b = (n + 255) / 256, bx = cap / gy < 1 ? 1 : cap / gy;
-  return dim3((unsigned)(b < 1 ? 1 : (b > bx ? bx : b)), (unsigned)gy);
+  return dim3((unsigned)blocks_for(n, 256, cap / gy < 1 ? 1 : cap / gy), (unsigned)gy);
 }
 
 }  // namespace mtmc
 
 extern "C" {
 
+using mtmc_api::fail;
+using mtmc_api::launched;
+
 int32_t mtmc_cross_entropy_forward(const float* logits, const int64_t* labels, const float* weight, int64_t n, int32_t n_classes,
                                    int64_t ignore_index, int32_t mode, float* per_sample, double* sums, float* loss_out,
                                    void* stream) {
-  if (!logits || !labels || !sums || n < 0 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES) return MTMC_E_ARG;
-  if (n_classes == 2 && ((uintptr_t)logits & 7)) return MTMC_E_ARG;
+  if (!logits || !labels || !sums) return fail(MTMC_E_ARG, "cross_entropy_forward: NULL logits, labels or sums");
+  if (n < 0 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
+    return fail(MTMC_E_ARG, "cross_entropy_forward: n must be >= 0 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
+  if (n_classes == 2 && ((uintptr_t)logits & 7)) return fail(MTMC_E_ARG, "cross_entropy_forward: [n, 2] logits must be 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * mtmc::kStatRep, s) != hipSuccess) return MTMC_E_HIP;
+  if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * mtmc::kStatRep, s) != hipSuccess)
+    return fail(MTMC_E_HIP, "cross_entropy_forward: hipMemsetAsync failed");
   if (n > 0)
-    hipLaunchKernelGGL(mtmc::ce_forward_kernel, dim3(mtmc::ce_grid_fwd(n)), dim3(256), 0, s, logits, labels, weight, n,
-                       n_classes, ignore_index, per_sample, sums, (int64_t)0);
+    hipLaunchKernelGGL(mtmc::ce_forward_kernel, dim3(mtmc::blocks_for(n, 256, mtmc::kCeBlocksFwd)), dim3(256), 0, s, logits,
+                       labels, weight, n, n_classes, ignore_index, per_sample, sums, (int64_t)0);
   hipLaunchKernelGGL(mtmc::ce_finalize_kernel, dim3(1), dim3(1), 0, s, sums, mode, loss_out, 1.0);
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("cross_entropy_forward");
 }
 
 // The training loop's `sum(criterion(step, labels) for step in outputs['classified_edges'])` (reference train.py:118-138:
@@ -284,52 +258,67 @@ int32_t mtmc_cross_entropy_forward(const float* logits, const int64_t* labels, c
 int32_t mtmc_cross_entropy_steps_forward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
                                          int32_t n_classes, int32_t n_steps, int64_t ignore_index, int32_t mode,
                                          double* sums, float* loss_out, void* stream) {
-  if (!logits || !labels || !sums || n < 0 || n_steps < 1 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES) return MTMC_E_ARG;
-  if (mode < 0 || mode > 1 || (n_classes == 2 && ((uintptr_t)logits & 7))) return MTMC_E_ARG;
+  if (!logits || !labels || !sums) return fail(MTMC_E_ARG, "cross_entropy_steps_forward: NULL logits, labels or sums");
+  if (n < 0 || n_steps < 1 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
+    return fail(MTMC_E_ARG, "cross_entropy_steps_forward: n must be >= 0, n_steps >= 1 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
+  if (mode < 0 || mode > 1) return fail(MTMC_E_ARG, "cross_entropy_steps_forward: mode must be 0 (mean) or 1 (sum)");
+  if (n_classes == 2 && ((uintptr_t)logits & 7))
+    return fail(MTMC_E_ARG, "cross_entropy_steps_forward: [n, 2] logits must be 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * mtmc::kStatRep, s) != hipSuccess) return MTMC_E_HIP;
+  if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * mtmc::kStatRep, s) != hipSuccess)
+    return fail(MTMC_E_HIP, "cross_entropy_steps_forward: hipMemsetAsync failed");
   if (n > 0)
-    hipLaunchKernelGGL(mtmc::ce_forward_kernel, dim3(mtmc::ce_grid_fwd(n * n_steps)), dim3(256), 0, s, logits, labels, weight,
-                       n * n_steps, n_classes, ignore_index, (float*)nullptr, sums, n);
+    hipLaunchKernelGGL(mtmc::ce_forward_kernel, dim3(mtmc::blocks_for(n * n_steps, 256, mtmc::kCeBlocksFwd)), dim3(256), 0, s,
+                       logits, labels, weight, n * n_steps, n_classes, ignore_index, (float*)nullptr, sums, n);
   hipLaunchKernelGGL(mtmc::ce_finalize_kernel, dim3(1), dim3(1), 0, s, sums, mode, loss_out, (double)n_steps);
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("cross_entropy_steps_forward");
 }
 
 int32_t mtmc_cross_entropy_steps_backward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
                                           int32_t n_classes, int32_t n_steps, int64_t ignore_index, int32_t mode,
                                           const float* grad, const double* sums, float* d_logits, void* stream) {
-  if (!logits || !labels || !grad || !sums || !d_logits || n < 0 || n_steps < 1 || n_classes < 1 ||
-      n_classes > MTMC_MAX_CLASSES || mode < 0 || mode > 1)
-    return MTMC_E_ARG;
-  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7))) return MTMC_E_ARG;
+  if (!logits || !labels || !grad || !sums || !d_logits)
+    return fail(MTMC_E_ARG, "cross_entropy_steps_backward: NULL logits, labels, grad, sums or d_logits");
+  if (n < 0 || n_steps < 1 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
+    return fail(MTMC_E_ARG, "cross_entropy_steps_backward: n must be >= 0, n_steps >= 1 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
+  if (mode < 0 || mode > 1) return fail(MTMC_E_ARG, "cross_entropy_steps_backward: mode must be 0 (mean) or 1 (sum)");
+  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7)))
+    return fail(MTMC_E_ARG, "cross_entropy_steps_backward: [n, 2] logits and d_logits must be 8-byte aligned");
   if (n > 0)
-    hipLaunchKernelGGL(mtmc::ce_backward_kernel, dim3(mtmc::ce_grid(n * n_steps)), dim3(256), 0,
+    hipLaunchKernelGGL(mtmc::ce_backward_kernel, dim3(mtmc::blocks_for(n * n_steps, 256, mtmc::kCeBlocks)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), logits, labels, weight, n * n_steps, n_classes, ignore_index, mode,
                        grad, sums, d_logits, n, (double)n_steps);
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("cross_entropy_steps_backward");
 }
 
 int32_t mtmc_cross_entropy_backward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
                                     int32_t n_classes, int64_t ignore_index, int32_t mode, const float* grad,
                                     const double* sums, float* d_logits, void* stream) {
-  if (!logits || !labels || !grad || !d_logits || n < 0 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES) return MTMC_E_ARG;
-  if (mode < 0 || mode > 2 || (mode == 0 && !sums)) return MTMC_E_ARG;
-  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7))) return MTMC_E_ARG;
+  if (!logits || !labels || !grad || !d_logits) return fail(MTMC_E_ARG, "cross_entropy_backward: NULL logits, labels, grad or d_logits");
+  if (n < 0 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
+    return fail(MTMC_E_ARG, "cross_entropy_backward: n must be >= 0 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
+  if (mode < 0 || mode > 2 || (mode == 0 && !sums))
+    return fail(MTMC_E_ARG, "cross_entropy_backward: mode must be 0 (mean, with the forward's sums), 1 (sum) or 2 (none)");
+  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7)))
+    return fail(MTMC_E_ARG, "cross_entropy_backward: [n, 2] logits and d_logits must be 8-byte aligned");
   if (n > 0)
-    hipLaunchKernelGGL(mtmc::ce_backward_kernel, dim3(mtmc::ce_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       logits, labels, weight, n, n_classes, ignore_index, mode, grad, sums, d_logits, (int64_t)0, 1.0);
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+    hipLaunchKernelGGL(mtmc::ce_backward_kernel, dim3(mtmc::blocks_for(n, 256, mtmc::kCeBlocks)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), logits, labels, weight, n, n_classes, ignore_index, mode, grad, sums,
+                       d_logits, (int64_t)0, 1.0);
+  return launched("cross_entropy_backward");
 }
 
 int32_t mtmc_edge_confusion(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int64_t* counts,
                             void* stream) {
-  if (!logits || !labels || !counts || n < 0 || n_classes < 2 || n_classes > MTMC_MAX_CLASSES) return MTMC_E_ARG;
+  if (!logits || !labels || !counts) return fail(MTMC_E_ARG, "edge_confusion: NULL logits, labels or counts");
+  if (n < 0 || n_classes < 2 || n_classes > MTMC_MAX_CLASSES)
+    return fail(MTMC_E_ARG, "edge_confusion: n must be >= 0 and n_classes in [2, %d]", MTMC_MAX_CLASSES);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) return MTMC_E_HIP;
+  if (hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) return fail(MTMC_E_HIP, "edge_confusion: hipMemsetAsync failed");
   if (n > 0)
-    hipLaunchKernelGGL(mtmc::confusion_kernel, dim3(mtmc::ce_grid(n) > 256 ? 256 : mtmc::ce_grid(n)), dim3(256), 0, s, logits,
+    hipLaunchKernelGGL(mtmc::confusion_kernel, dim3(mtmc::blocks_for(n, 256, mtmc::kConfusionBlocks)), dim3(256), 0, s, logits,
                        labels, n, n_classes, reinterpret_cast<unsigned long long*>(counts));
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("edge_confusion");
 }
 
 size_t mtmc_edge_loss_scratch_bytes(int32_t n_steps) {
@@ -339,15 +328,19 @@ size_t mtmc_edge_loss_scratch_bytes(int32_t n_steps) {
 int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
                                size_t scratch_bytes, double* record, float* out, int64_t* confusion, void* stream) {
-  if (!logits || !labels || !scratch || !record || !out || !confusion || n < 0 || n_steps < 1) return MTMC_E_ARG;
-  if (n_classes != 1 && n_classes != 2) return MTMC_E_ARG;
+  if (!logits || !labels || !scratch || !record || !out || !confusion)
+    return fail(MTMC_E_ARG, "edge_loss_forward: NULL logits, labels, scratch, record, out or confusion");
+  if (n < 0 || n_steps < 1 || (n_classes != 1 && n_classes != 2))
+    return fail(MTMC_E_ARG, "edge_loss_forward: n must be >= 0, n_steps >= 1 and n_classes 1 or 2");
   if (weight_mode < MTMC_EDGE_W_ONE || weight_mode > MTMC_EDGE_W_BALANCED || (weight_mode == MTMC_EDGE_W_GIVEN && !weight))
-    return MTMC_E_ARG;
-  if ((n_classes == 2 && ((uintptr_t)logits & 7)) || ((uintptr_t)scratch & 7)) return MTMC_E_ARG;
+    return fail(MTMC_E_ARG, "edge_loss_forward: weight_mode must be MTMC_EDGE_W_ONE, _GIVEN (with weight) or _BALANCED");
+  if ((n_classes == 2 && ((uintptr_t)logits & 7)) || ((uintptr_t)scratch & 7))
+    return fail(MTMC_E_ARG, "edge_loss_forward: [n, 2] logits and scratch must be 8-byte aligned");
   const size_t need = mtmc_edge_loss_scratch_bytes(n_steps);
-  if (scratch_bytes < need) return MTMC_E_ARG;
+  if (scratch_bytes < need)
+    return fail(MTMC_E_ARG, "edge_loss_forward: scratch has %zu bytes, %zu needed (mtmc_edge_loss_scratch_bytes)", scratch_bytes, need);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, need, s) != hipSuccess) return MTMC_E_HIP;
+  if (hipMemsetAsync(scratch, 0, need, s) != hipSuccess) return fail(MTMC_E_HIP, "edge_loss_forward: hipMemsetAsync failed");
   double* acc = static_cast<double*>(scratch);
   if (n > 0) {
     const dim3 grid = mtmc::el_grid(n, n_steps, 512);
@@ -358,14 +351,17 @@ int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64
   }
   hipLaunchKernelGGL(mtmc::el_finalize_kernel, dim3(1), dim3(64), 0, s, acc, n_steps, n_classes, weight_mode, weight,
                      fpr_alpha, record, out, reinterpret_cast<long long*>(confusion));
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("edge_loss_forward");
 }
 
 int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                 const float* grad, const double* record, float* d_logits, void* stream) {
-  if (!logits || !labels || !grad || !record || !d_logits || n < 0 || n_steps < 1) return MTMC_E_ARG;
-  if (n_classes != 1 && n_classes != 2) return MTMC_E_ARG;
-  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7))) return MTMC_E_ARG;
+  if (!logits || !labels || !grad || !record || !d_logits)
+    return fail(MTMC_E_ARG, "edge_loss_backward: NULL logits, labels, grad, record or d_logits");
+  if (n < 0 || n_steps < 1 || (n_classes != 1 && n_classes != 2))
+    return fail(MTMC_E_ARG, "edge_loss_backward: n must be >= 0, n_steps >= 1 and n_classes 1 or 2");
+  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7)))
+    return fail(MTMC_E_ARG, "edge_loss_backward: [n, 2] logits and d_logits must be 8-byte aligned");
   if (n > 0) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
@@ -374,7 +370,7 @@ int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int6
     else
       hipLaunchKernelGGL(mtmc::el_backward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, record, d_logits);
   }
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return launched("edge_loss_backward");
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 // anything, and what was wrong with them is reported in info[0] (0 ok; 1 not strictly increasing or outside [0, D];
 // 2 offsets[0] != 0 or offsets[N] != D -- the larger one if both), info[1] = how many tracklets had a bad range.
 #include "api_internal.h"
+#include <limits.h>
 
 namespace mtmc {
 
@@ -166,7 +167,7 @@ static inline size_t pool_partial_bytes(int64_t n_rows, int32_t feat_dim) {
 }
 static inline unsigned pool_grid(int64_t items, int32_t feat_dim) {      // four waves per workgroup
   const int64_t waves = items * ((feat_dim + kPoolSlab - 1) / kPoolSlab);
-  return (unsigned)((waves + 3) / 4);
+  return (unsigned)blocks_for(waves, 4, INT_MAX);
 }
 
 }  // namespace mtmc
@@ -203,8 +204,7 @@ int32_t mtmc_pool_tracklets(const float* embeds, int64_t row_stride, int64_t n_r
                      n_rows, (int)feat_dim, offsets, n_tracklets, out, partial, reinterpret_cast<int*>(info));
   hipLaunchKernelGGL(pool_finish_kernel, dim3(pool_grid(n_tracklets, feat_dim)), dim3(256), 0, s, n_rows, (int)feat_dim, offsets,
                      n_tracklets, out, (const float*)partial, reinterpret_cast<int*>(info));
-  if (hipGetLastError() != hipSuccess) return fail(MTMC_E_HIP, "pool_tracklets: kernel launch failed");
-  return MTMC_OK;
+  return mtmc_api::launched("pool_tracklets");
 }
 
 int32_t mtmc_pool_tracklets_backward(const float* grad_out, int64_t n_rows, int32_t feat_dim, const int64_t* offsets,
@@ -222,8 +222,7 @@ int32_t mtmc_pool_tracklets_backward(const float* grad_out, int64_t n_rows, int3
   hipLaunchKernelGGL(pool_backward_kernel, dim3(pool_grid(pool_chunks(n_rows), feat_dim)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), grad_out, n_rows, (int)feat_dim, offsets, n_tracklets, grad_embeds,
                      grad_row_stride);
-  if (hipGetLastError() != hipSuccess) return fail(MTMC_E_HIP, "pool_tracklets_backward: kernel launch failed");
-  return MTMC_OK;
+  return mtmc_api::launched("pool_tracklets_backward");
 }
 
 }  // extern "C"

@@ -16,8 +16,8 @@
 //                        is defined by networkx's depth-first traversal order (utils.py:31), which is inherently
 //                        sequential, so that walk runs on lane 0 -- out of LDS whenever N <= 2048 and A <= 8192.
 // No host round trip, no dynamic allocation: a caller can enqueue it right behind the forward.
+#include "api_error.h"
 #include "kernels.h"
-#include "../../include/mtmc_mpn.h"
 
 #include <stdint.h>
 
@@ -714,7 +714,11 @@ int launch_postprocess(const float* logits, const int64_t* row, const int64_t* c
   PpParams p;
   p.logits = logits; p.row = row; p.col = col; p.idx_stride = idx_stride; p.n_nodes = n_nodes; p.n_edges = n_edges;
   p.num_cameras = num_cameras; p.flags = flags; p.prob1 = prob1; p.pred = pred; p.id_pred = id_pred; p.info = info;
-  if (workspace_bytes < pp_carve(p, max_active, nullptr)) return MTMC_E_WORKSPACE;
+  using mtmc_api::fail;
+  const size_t need = pp_carve(p, max_active, nullptr);
+  if (workspace_bytes < need)
+    return fail(MTMC_E_WORKSPACE, "postprocess: workspace has %zu bytes, %zu needed (mtmc_postprocess_workspace_bytes)",
+                workspace_bytes, need);
   pp_carve(p, max_active, static_cast<char*>(workspace));
   const int nb = (int)((n_edges + kPpChunk - 1) / kPpChunk);
   if (nb > 0) hipLaunchKernelGGL(pp_classify_kernel, dim3(nb), dim3(256), 0, s, p);
@@ -724,9 +728,9 @@ int launch_postprocess(const float* logits, const int64_t* row, const int64_t* c
   const size_t npad = ((size_t)n_nodes + 4) & ~(size_t)3;
   const size_t lds = (lds_nodes ? kPpNodeArrays * npad * sizeof(int) : 0) + (size_t)kPpLdsEdges * sizeof(unsigned);
   if (!allow_big_lds(reinterpret_cast<const void*>(pp_graph_kernel), (kPpNodeArrays * (kPpLdsNodes + 4) + kPpLdsEdges) * 4))
-    return MTMC_E_HIP;
+    return fail(MTMC_E_HIP, "postprocess: HIP refused the graph kernel's dynamic LDS size");
   hipLaunchKernelGGL(pp_graph_kernel, dim3(1), dim3(kPpThreads), lds, s, p, lds_nodes);
-  return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
+  return mtmc_api::launched("postprocess");
 }
 
 }  // namespace mtmc
@@ -742,10 +746,14 @@ int32_t mtmc_postprocess(const float* logits, const int64_t* row, const int64_t*
                          int64_t n_nodes, int64_t n_edges, int32_t num_cameras, int32_t flags, int64_t max_active,
                          float* prob1, int64_t* predictions, int64_t* id_pred, int32_t* info,
                          void* workspace, size_t workspace_bytes, void* stream) {
-  if (n_nodes < 1 || n_edges < 0 || n_nodes >= (1ll << 31) || n_edges >= (1ll << 31) || num_cameras < 1) return MTMC_E_ARG;
-  if (!prob1 || !predictions || !id_pred || !info || !workspace || idx_stride < 1) return MTMC_E_ARG;
-  if (n_edges > 0 && (!row || !col)) return MTMC_E_ARG;
-  if (((uintptr_t)workspace & 255) || (logits && ((uintptr_t)logits & 7))) return MTMC_E_ARG;
+  using mtmc_api::fail;
+  if (n_nodes < 1 || n_edges < 0 || n_nodes >= (1ll << 31) || n_edges >= (1ll << 31) || num_cameras < 1)
+    return fail(MTMC_E_ARG, "postprocess: n_nodes must be in [1, 2^31), n_edges in [0, 2^31) and num_cameras >= 1");
+  if (!prob1 || !predictions || !id_pred || !info || !workspace || (n_edges > 0 && (!row || !col)))
+    return fail(MTMC_E_ARG, "postprocess: NULL prob1, predictions, id_pred, info or workspace, or NULL row or col with n_edges > 0");
+  if (idx_stride < 1) return fail(MTMC_E_ARG, "postprocess: idx_stride must be >= 1");
+  if (((uintptr_t)workspace & 255) || (logits && ((uintptr_t)logits & 7)))
+    return fail(MTMC_E_ARG, "postprocess: the workspace must be 256-byte and logits 8-byte aligned");
   return mtmc::launch_postprocess(logits, row, col, idx_stride, n_nodes, n_edges, num_cameras, flags, max_active, prob1,
                                   predictions, id_pred, info, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }

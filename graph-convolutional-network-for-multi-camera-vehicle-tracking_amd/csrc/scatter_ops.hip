@@ -83,43 +83,40 @@ __global__ void scatter_add_i64_kernel(const int64_t* src, const int64_t* index,
   }
 }
 
-static inline int sgrid(int64_t n) {
-  const int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+constexpr int kScatterBlocks = 4096;      // most workgroups (of 256 elements) of a launch
 
 // mode 0 add, 1 mean, 2 max
 void launch_scatter(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                     float* out, float* count, int64_t* arg_out, int mode, hipStream_t s) {
   const int64_t n_out = dim_size * n_cols, n_in = n_src * n_cols;
+  const dim3 g_out(blocks_for(n_out, 256, kScatterBlocks)), g_in(blocks_for(n_in, 256, kScatterBlocks));
   if (mode == 2) {
-    hipLaunchKernelGGL(scatter_fill_kernel, dim3(sgrid(n_out)), dim3(256), 0, s, out, n_out, INT_MIN);
-    if (n_in > 0)
-      hipLaunchKernelGGL(scatter_max_kernel, dim3(sgrid(n_in)), dim3(256), 0, s, src, index, n_src, n_cols, dim_size, out);
+    hipLaunchKernelGGL(scatter_fill_kernel, g_out, dim3(256), 0, s, out, n_out, INT_MIN);
+    if (n_in > 0) hipLaunchKernelGGL(scatter_max_kernel, g_in, dim3(256), 0, s, src, index, n_src, n_cols, dim_size, out);
     if (arg_out) {
-      hipLaunchKernelGGL(scatter_fill_i64_kernel, dim3(sgrid(n_out)), dim3(256), 0, s, arg_out, n_out, n_src);
+      hipLaunchKernelGGL(scatter_fill_i64_kernel, g_out, dim3(256), 0, s, arg_out, n_out, n_src);
       if (n_in > 0)
-        hipLaunchKernelGGL(scatter_argmax_kernel, dim3(sgrid(n_in)), dim3(256), 0, s, src, index, n_src, n_cols,
-                           dim_size, out, arg_out);
+        hipLaunchKernelGGL(scatter_argmax_kernel, g_in, dim3(256), 0, s, src, index, n_src, n_cols, dim_size, out, arg_out);
     }
-    hipLaunchKernelGGL(scatter_unkey_kernel, dim3(sgrid(n_out)), dim3(256), 0, s, out, n_out);
+    hipLaunchKernelGGL(scatter_unkey_kernel, g_out, dim3(256), 0, s, out, n_out);
     return;
   }
-  hipLaunchKernelGGL(scatter_fill_kernel, dim3(sgrid(n_out)), dim3(256), 0, s, out, n_out, 0);
-  if (mode == 1) hipLaunchKernelGGL(scatter_fill_kernel, dim3(sgrid(dim_size)), dim3(256), 0, s, count, dim_size, 0);
-  if (n_in > 0)
-    hipLaunchKernelGGL(scatter_add_kernel, dim3(sgrid(n_in)), dim3(256), 0, s, src, index, n_src, n_cols, dim_size, out,
-                       mode == 1 ? count : nullptr);
+  hipLaunchKernelGGL(scatter_fill_kernel, g_out, dim3(256), 0, s, out, n_out, 0);
   if (mode == 1)
-    hipLaunchKernelGGL(scatter_div_kernel, dim3(sgrid(n_out)), dim3(256), 0, s, out, count, dim_size, n_cols);
+    hipLaunchKernelGGL(scatter_fill_kernel, dim3(blocks_for(dim_size, 256, kScatterBlocks)), dim3(256), 0, s, count, dim_size, 0);
+  if (n_in > 0)
+    hipLaunchKernelGGL(scatter_add_kernel, g_in, dim3(256), 0, s, src, index, n_src, n_cols, dim_size, out,
+                       mode == 1 ? count : nullptr);
+  if (mode == 1) hipLaunchKernelGGL(scatter_div_kernel, g_out, dim3(256), 0, s, out, count, dim_size, n_cols);
 }
 
 void launch_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                             int64_t* out, hipStream_t s) {
-  hipLaunchKernelGGL(scatter_fill_i64_kernel, dim3(sgrid(dim_size * n_cols)), dim3(256), 0, s, out, dim_size * n_cols, (int64_t)0);
-  if (n_src * n_cols > 0)
-    hipLaunchKernelGGL(scatter_add_i64_kernel, dim3(sgrid(n_src * n_cols)), dim3(256), 0, s, src, index, n_src, n_cols,
-                       dim_size, out);
+  const int64_t n_out = dim_size * n_cols, n_in = n_src * n_cols;
+  hipLaunchKernelGGL(scatter_fill_i64_kernel, dim3(blocks_for(n_out, 256, kScatterBlocks)), dim3(256), 0, s, out, n_out, (int64_t)0);
+  if (n_in > 0)
+    hipLaunchKernelGGL(scatter_add_i64_kernel, dim3(blocks_for(n_in, 256, kScatterBlocks)), dim3(256), 0, s, src, index, n_src,
+                       n_cols, dim_size, out);
 }
 
 }  // namespace mtmc

@@ -13,7 +13,7 @@ import types
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
 
 MAX_NODES = 46000
 
@@ -58,16 +58,13 @@ def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool):
     if need == 0:
         raise RuntimeError("mtmc_mpn.build_graph: unsupported size")
     ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.mtmc_build_graph(
-            feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
-            t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
-            n_cams, e, labels_dev.data_ptr() if labels_dev is not None else None,
-            x.data_ptr(), edge_pairs.data_ptr() if e else None, edge_attr.data_ptr() if e else None,
-            edge_labels.data_ptr() if edge_labels is not None else None,
-            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"mtmc_mpn.build_graph failed (code {rc})")
+    _call.run(dev, lib.mtmc_build_graph,
+              feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
+              t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
+              n_cams, e, labels_dev.data_ptr() if labels_dev is not None else None,
+              x.data_ptr(), edge_pairs.data_ptr() if e else None, edge_attr.data_ptr() if e else None,
+              edge_labels.data_ptr() if edge_labels is not None else None,
+              ws.data_ptr(), ws.numel(), _call.stream(dev))
     return (x, edge_pairs, edge_attr, edge_labels, labels_dev), (feats, (t_in, t_inoff, t_out, t_outoff, t_blk), n_cams, e)
 
 
@@ -101,15 +98,12 @@ class _BuildGraph(torch.autograd.Function):
         lib = _lib.load()
         d_feats = torch.empty((n, f), dtype=torch.float32, device=dev)
         ws = torch.empty(lib.mtmc_graph_backward_workspace_bytes(n, f) + 256, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.mtmc_build_graph_backward(
-                feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
-                t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
-                n_cams, e, x.data_ptr(), edge_attr.data_ptr() if e else None,
-                g_x.data_ptr() if g_x is not None else None, g_attr.data_ptr() if g_attr is not None else None,
-                d_feats.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mtmc_mpn.build_graph backward failed (code {rc})")
+        _call.run(dev, lib.mtmc_build_graph_backward,
+                  feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
+                  t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
+                  n_cams, e, x.data_ptr(), edge_attr.data_ptr() if e else None,
+                  g_x.data_ptr() if g_x is not None else None, g_attr.data_ptr() if g_attr is not None else None,
+                  d_feats.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
         return d_feats, None, None, None
 
 
@@ -117,8 +111,7 @@ def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: boo
     """node_feats: [N, F] float32 on a ROCm GPU (the stacked per-tracklet ReID features); cam_ids: N camera ids
     (host list / array, as the reference keeps them); node_labels: optional N identities (edge labels for training).
     With grad mode on and `node_feats.requires_grad`, `x` and `edge_attr` carry the gradient back to `node_feats`."""
-    if not (isinstance(node_feats, torch.Tensor) and node_feats.is_cuda):
-        raise RuntimeError("mtmc_mpn.build_graph: node_feats must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu("build_graph", node_feats)
     if node_feats.dim() != 2 or node_feats.dtype != torch.float32 or node_feats.shape[1] % 32:
         raise RuntimeError("mtmc_mpn.build_graph: node_feats must be float32 [N, F] with F a multiple of 32")
     n, f = node_feats.shape

@@ -18,7 +18,7 @@ import types
 
 import torch
 
-from . import _lib
+from . import _call, _lib
 from .postprocess import postprocess
 
 ClusterScores = collections.namedtuple("ClusterScores", ["ari", "ami", "homogeneity", "completeness", "v_measure",
@@ -27,17 +27,6 @@ EdgePRF = collections.namedtuple("EdgePRF", ["confusion", "precision", "recall",
 
 MAX_LABELS = _lib.CLUSTER_SCORES_MAX_N
 _INT_TYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _on_gpu(name, *tensors):
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError(f"mtmc_mpn.{name}: tensors must be on a ROCm GPU (no CPU path)")
-    if any(t.device != tensors[0].device for t in tensors):
-        raise RuntimeError(f"mtmc_mpn.{name}: the tensors must be on one device")
 
 
 def cluster_scores(labels_true, labels_pred):
@@ -56,7 +45,7 @@ def cluster_scores(labels_true, labels_pred):
     n = t.shape[0]
     if n < 1 or n > MAX_LABELS:
         raise ValueError(f"mtmc_mpn.cluster_scores: n = {n} is outside [1, {MAX_LABELS}]")
-    _on_gpu("cluster_scores", t, p)
+    _call.require_gpu("cluster_scores", t, p)
     dev = t.device
     t, p = t.long(), p.long()                                   # (no copy of an int64 tensor; its stride goes to the kernel)
     lib = _lib.load()
@@ -64,9 +53,8 @@ def cluster_scores(labels_true, labels_pred):
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     scores = torch.empty(_lib.CLUSTER_SCORES, dtype=torch.float64, device=dev)
     counts = torch.empty(_lib.CLUSTER_COUNTS, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mtmc_cluster_scores(t.data_ptr(), t.stride(0), p.data_ptr(), p.stride(0), n, scores.data_ptr(),
-                                           counts.data_ptr(), ws.data_ptr(), need, _stream(dev)))
+    _call.run(dev, lib.mtmc_cluster_scores, t.data_ptr(), t.stride(0), p.data_ptr(), p.stride(0), n, scores.data_ptr(),
+              counts.data_ptr(), ws.data_ptr(), need, _call.stream(dev))
     return ClusterScores(*scores.unbind(0), counts)
 
 
@@ -79,16 +67,14 @@ def edge_prf(predictions, labels):
     y, x = predictions, labels
     if y.dim() != 1 or x.shape != y.shape or y.dtype not in _INT_TYPES:
         raise ValueError("mtmc_mpn.edge_prf: predictions must be an [E] integer tensor, labels [E]")
-    _on_gpu("edge_prf", y, x)
+    _call.require_gpu("edge_prf", y, x)
     dev = y.device
     y, x = y.long(), x.long()
     e = y.shape[0]
     confusion = torch.empty(4, dtype=torch.int64, device=dev)
     out = torch.empty(_lib.EDGE_PRF, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().mtmc_edge_prf(y.data_ptr() if e else None, y.stride(0) if e else 1,
-                                             x.data_ptr() if e else None, x.stride(0) if e else 1, e,
-                                             confusion.data_ptr(), out.data_ptr(), _stream(dev)))
+    _call.run(dev, _lib.load().mtmc_edge_prf, y.data_ptr() if e else None, y.stride(0) if e else 1,
+              x.data_ptr() if e else None, x.stride(0) if e else 1, e, confusion.data_ptr(), out.data_ptr(), _call.stream(dev))
     return EdgePRF(confusion, out[0], out[1], out[2], out[3:5])
 
 
@@ -97,7 +83,7 @@ def evaluate(ID_pred, predictions, edge_index, edge_labels, num_nodes: int):
     connected components of the label-1 edges (what `compute_SCC_and_Clusters` makes of `G_GT`; the scores do not depend
     on how the clusters are numbered), then `cluster_scores(ID_GT, ID_pred)` and `edge_prf(predictions, edge_labels)`.
     Returns a namespace with ID_GT [N] int64, clusters (ClusterScores) and edges (EdgePRF)."""
-    _on_gpu("evaluate", edge_labels, ID_pred, predictions, edge_index)
+    _call.require_gpu("evaluate", edge_labels, ID_pred, predictions, edge_index)
     gt = postprocess(None, edge_index, num_nodes, 1, cutting=False, pruning=False, splitting=False,
                      preds_prob=edge_labels, predictions=edge_labels, check=False)
     return types.SimpleNamespace(ID_GT=gt.ID_pred, clusters=cluster_scores(gt.ID_pred, ID_pred),

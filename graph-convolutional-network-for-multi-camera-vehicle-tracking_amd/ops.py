@@ -20,40 +20,33 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _call, _lib
 from . import torch_ops  # noqa: F401  (registers torch.ops.mtmc_mpn.*)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _check_scatter(src, index, out, name):
+def _scatter(name, src, index, dim, out, dim_size):
     if out is not None:
         raise NotImplementedError(f"mtmc_mpn.{name}: `out=` is not supported")
-    if not (src.is_cuda and index.is_cuda):
-        raise RuntimeError("mtmc_mpn.scatter_*: tensors must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu(name, src, index)
+    return getattr(torch.ops.mtmc_mpn, name)(src, index, dim, dim_size)
 
 
 def scatter_add(src, index, dim=0, out=None, dim_size=None):
     """`torch_scatter.scatter_add(src, index, dim=0, dim_size=N)`; integer `src` (the 1-D int64 form of reference
     utils.py:173-174) is summed exactly and keeps its dtype."""
-    _check_scatter(src, index, out, "scatter_add")
-    return torch.ops.mtmc_mpn.scatter_add(src, index, dim, dim_size)
+    return _scatter("scatter_add", src, index, dim, out, dim_size)
 
 
 scatter_sum = scatter_add
 
 
 def scatter_mean(src, index, dim=0, out=None, dim_size=None):
-    _check_scatter(src, index, out, "scatter_mean")
-    return torch.ops.mtmc_mpn.scatter_mean(src, index, dim, dim_size)
+    return _scatter("scatter_mean", src, index, dim, out, dim_size)
 
 
 def scatter_max(src, index, dim=0, out=None, dim_size=None):
     """Returns (values, argmax) like torch_scatter; rows nobody writes hold 0 and argmax = src.size(0)."""
-    _check_scatter(src, index, out, "scatter_max")
-    return torch.ops.mtmc_mpn.scatter_max(src, index, dim, dim_size)
+    return _scatter("scatter_max", src, index, dim, out, dim_size)
 
 
 def layer_forward(a: torch.Tensor, weight, bias, gamma=None, beta=None) -> torch.Tensor:
@@ -71,16 +64,14 @@ def layer_forward(a: torch.Tensor, weight, bias, gamma=None, beta=None) -> torch
     lay.in_dim, lay.out_dim = in_dim, out_dim
     y = torch.empty((a.shape[0], out_dim), dtype=torch.float32, device=a.device)
     stats = torch.empty((2 * out_dim,), dtype=torch.float64, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().mtmc_mlp_layer_forward(C.byref(lay), a.data_ptr(), a.stride(0), a.shape[0], y.data_ptr(),
-                                                      stats.data_ptr(), _stream(a.device)))
+    _call.run(a.device, _lib.load().mtmc_mlp_layer_forward, C.byref(lay), a.data_ptr(), a.stride(0), a.shape[0], y.data_ptr(),
+              stats.data_ptr(), _call.stream(a.device))
     return y
 
 
 def mlp_forward(mlp, inp: torch.Tensor) -> torch.Tensor:
     """Eval-mode `MLP.forward`: per hidden layer Linear -> BatchNorm1d (batch statistics) -> ReLU."""
-    if not inp.is_cuda:
-        raise RuntimeError("mtmc_mpn.MLP: input must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu("MLP", inp)
     if mlp.training and any(l.dropout_p for l in mlp.layers):
         raise NotImplementedError("mtmc_mpn.MLP: training-mode Dropout is not built yet; use .eval()")
     if torch.is_grad_enabled() and (inp.requires_grad or any(p.requires_grad for p in mlp.parameters())):
@@ -108,11 +99,10 @@ class _CrossEntropy(torch.autograd.Function):
         sums = torch.empty(2 * _lib.STAT_REPLICAS, dtype=torch.float64, device=dev)
         per = torch.empty(n, dtype=torch.float32, device=dev) if mode == 2 else None
         loss = torch.empty((), dtype=torch.float32, device=dev) if mode != 2 else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mtmc_cross_entropy_forward(
-                x.data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c, ignore_index,
-                mode, per.data_ptr() if per is not None else None, sums.data_ptr(),
-                loss.data_ptr() if loss is not None else None, _stream(dev)))
+        _call.run(dev, _lib.load().mtmc_cross_entropy_forward,
+                  x.data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c, ignore_index,
+                  mode, per.data_ptr() if per is not None else None, sums.data_ptr(),
+                  loss.data_ptr() if loss is not None else None, _call.stream(dev))
         ctx.save_for_backward(x, target, weight, sums)
         ctx.mode, ctx.ignore_index = mode, ignore_index
         return per if mode == 2 else loss
@@ -124,26 +114,21 @@ class _CrossEntropy(torch.autograd.Function):
         dev = x.device
         d = torch.empty_like(x)
         g = grad.contiguous().float()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mtmc_cross_entropy_backward(
-                x.data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
-                ctx.ignore_index, ctx.mode, g.data_ptr(), sums.data_ptr(), d.data_ptr(), _stream(dev)))
+        _call.run(dev, _lib.load().mtmc_cross_entropy_backward,
+                  x.data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
+                  ctx.ignore_index, ctx.mode, g.data_ptr(), sums.data_ptr(), d.data_ptr(), _call.stream(dev))
         return d, None, None, None, None
 
 
 def cross_entropy(input, target, weight=None, reduction: str = "mean", ignore_index: int = -100):
     """Drop-in for `torch.nn.functional.cross_entropy(input, target, weight=weight, reduction=reduction)` with class
     indices as targets, for the [E, C<=4] float32 edge logits of the MPN."""
-    if not (input.is_cuda and target.is_cuda):
-        raise RuntimeError("mtmc_mpn.cross_entropy: tensors must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu("cross_entropy", input, target)
     if input.dim() != 2 or input.dtype != torch.float32 or input.shape[1] > 4 or target.shape != input.shape[:1]:
         raise NotImplementedError("mtmc_mpn.cross_entropy: input must be float32 [E, C<=4], target int64 [E]")
     if reduction not in _REDUCTIONS:
         raise ValueError(f"{reduction} is not a valid value for reduction")
-    if weight is not None:
-        weight = weight.to(device=input.device, dtype=torch.float32).contiguous()
-        if weight.numel() != input.shape[1]:
-            raise RuntimeError("mtmc_mpn.cross_entropy: weight must have one entry per class")
+    weight = _call.class_weight(weight, input.device, input.shape[1], "cross_entropy")
     return _CrossEntropy.apply(input, target.contiguous().long(), weight, _REDUCTIONS[reduction], int(ignore_index))
 
 
@@ -156,10 +141,9 @@ class _CrossEntropySteps(torch.autograd.Function):
         dev = steps[0].device
         sums = torch.empty(2 * _lib.STAT_REPLICAS, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mtmc_cross_entropy_steps_forward(
-                steps[0].data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
-                len(steps), ignore_index, mode, sums.data_ptr(), loss.data_ptr(), _stream(dev)))
+        _call.run(dev, _lib.load().mtmc_cross_entropy_steps_forward,
+                  steps[0].data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
+                  len(steps), ignore_index, mode, sums.data_ptr(), loss.data_ptr(), _call.stream(dev))
         ctx.save_for_backward(target, weight, sums, *steps)
         ctx.mode, ctx.ignore_index = mode, ignore_index
         return loss
@@ -171,10 +155,9 @@ class _CrossEntropySteps(torch.autograd.Function):
         dev = steps[0].device
         d = torch.empty((len(steps), n, c), dtype=torch.float32, device=dev)
         g = grad.contiguous().float()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mtmc_cross_entropy_steps_backward(
-                steps[0].data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
-                len(steps), ctx.ignore_index, ctx.mode, g.data_ptr(), sums.data_ptr(), d.data_ptr(), _stream(dev)))
+        _call.run(dev, _lib.load().mtmc_cross_entropy_steps_backward,
+                  steps[0].data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
+                  len(steps), ctx.ignore_index, ctx.mode, g.data_ptr(), sums.data_ptr(), d.data_ptr(), _call.stream(dev))
         return (None, None, None, None) + tuple(d[i] for i in range(len(steps)))
 
 
@@ -190,30 +173,23 @@ def cross_entropy_steps(steps, target, weight=None, reduction: str = "mean", ign
         raise ValueError("cross_entropy_steps: reduction must be 'mean' or 'sum'")
     s0 = steps[0]
     block = (s0.dim() == 2 and s0.dtype == torch.float32 and s0.is_cuda and target.is_cuda and s0.shape[1] <= 4
-             and target.shape == s0.shape[:1]
-             and all(t.shape == s0.shape and t.dtype == s0.dtype and t.device == s0.device and t.is_contiguous()
-                     and t.data_ptr() == s0.data_ptr() + i * s0.numel() * 4 for i, t in enumerate(steps)))
+             and target.shape == s0.shape[:1] and _call.steps_block(steps))
     if not block or len(steps) == 1:
         return sum(cross_entropy(t, target, weight=weight, reduction=reduction, ignore_index=ignore_index) for t in steps)
-    if weight is not None:
-        weight = weight.to(device=s0.device, dtype=torch.float32).contiguous()
-        if weight.numel() != s0.shape[1]:
-            raise RuntimeError("mtmc_mpn.cross_entropy_steps: weight must have one entry per class")
+    weight = _call.class_weight(weight, s0.device, s0.shape[1], "cross_entropy_steps")
     return _CrossEntropySteps.apply(target.contiguous().long(), weight, _REDUCTIONS[reduction], int(ignore_index), *steps)
 
 
 def edge_confusion(logits, labels):
     """int64 tensor [TP, FP, TN, FN] (on the device) of `argmax(logits, 1) == 1` against 0/1 `labels`; e.g.
     FPR = FP / (FP + TN) as in train.py:100-102.  No host synchronisation."""
-    if not (logits.is_cuda and labels.is_cuda):
-        raise RuntimeError("mtmc_mpn.edge_confusion: tensors must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu("edge_confusion", logits, labels)
     if logits.dim() != 2 or logits.dtype != torch.float32 or not 2 <= logits.shape[1] <= 4 or labels.shape != logits.shape[:1]:
         raise NotImplementedError("mtmc_mpn.edge_confusion: logits must be float32 [E, 2..4], labels [E]")
     x, y = logits.contiguous(), labels.contiguous().long()
     out = torch.empty(4, dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().mtmc_edge_confusion(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(),
-                                                   _stream(x.device)))
+    _call.run(x.device, _lib.load().mtmc_edge_confusion, x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(),
+              _call.stream(x.device))
     return out
 
 
@@ -234,10 +210,9 @@ class _EdgeLoss(torch.autograd.Function):
         record = torch.empty(_lib.EDGE_LOSS_RECORD, dtype=torch.float64, device=dev)
         out = torch.empty(3 + 5 * s, dtype=torch.float32, device=dev)
         confusion = torch.empty((s, 4), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mtmc_edge_loss_forward(
-                steps[0].data_ptr(), target.data_ptr(), n, c, s, mode, weight.data_ptr() if weight is not None else None,
-                fpr_alpha, scratch.data_ptr(), nbytes, record.data_ptr(), out.data_ptr(), confusion.data_ptr(), _stream(dev)))
+        _call.run(dev, lib.mtmc_edge_loss_forward,
+                  steps[0].data_ptr(), target.data_ptr(), n, c, s, mode, weight.data_ptr() if weight is not None else None,
+                  fpr_alpha, scratch.data_ptr(), nbytes, record.data_ptr(), out.data_ptr(), confusion.data_ptr(), _call.stream(dev))
         ctx.save_for_backward(target, record, *steps)
         r = (out[0], out[3:3 + 2 * s].view(s, 2), out[3 + 2 * s:3 + 4 * s].view(s, 2), confusion, out[3 + 4 * s:], out[1:3])
         ctx.mark_non_differentiable(*r[1:])
@@ -250,10 +225,9 @@ class _EdgeLoss(torch.autograd.Function):
         dev = steps[0].device
         d = torch.empty((len(steps), n, c), dtype=torch.float32, device=dev)
         g = grad.contiguous().float()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mtmc_edge_loss_backward(
-                steps[0].data_ptr(), target.data_ptr(), n, c, len(steps), g.data_ptr(), record.data_ptr(), d.data_ptr(),
-                _stream(dev)))
+        _call.run(dev, _lib.load().mtmc_edge_loss_backward,
+                  steps[0].data_ptr(), target.data_ptr(), n, c, len(steps), g.data_ptr(), record.data_ptr(), d.data_ptr(),
+                  _call.stream(dev))
         return (None, None, None, None) + tuple(d[i] for i in range(len(steps)))
 
 
@@ -284,8 +258,7 @@ def edge_loss(steps, labels, weight=None, pos_weight=None, fpr_alpha: float = 0.
         raise ValueError(f"mtmc_mpn.edge_loss: [E, {c}] logits take `{name}`, not `{'pos_weight' if c == 2 else 'weight'}`")
     if isinstance(given, str) and given != "balanced":
         raise ValueError(f"mtmc_mpn.edge_loss: {name} must be None, a tensor or 'balanced', got {given!r}")
-    if not (s0.is_cuda and labels.is_cuda):
-        raise RuntimeError("mtmc_mpn.edge_loss: tensors must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu("edge_loss", s0, labels)
     if given is None:
         mode = _lib.EDGE_W_ONE
     elif isinstance(given, str):
@@ -297,7 +270,6 @@ def edge_loss(steps, labels, weight=None, pos_weight=None, fpr_alpha: float = 0.
         given = given.detach().to(device=s0.device, dtype=torch.float32).contiguous().view(-1)
         if given.numel() != (2 if c == 2 else 1):
             raise ValueError(f"mtmc_mpn.edge_loss: {name} must have {2 if c == 2 else 1} element(s)")
-    block = all(t.is_contiguous() and t.data_ptr() == s0.data_ptr() + i * s0.numel() * 4 for i, t in enumerate(steps))
-    if not block:
+    if not _call.steps_block(steps):
         steps = list(torch.stack(steps).unbind(0))           # autograd reaches the pieces through the stack
     return EdgeLoss(*_EdgeLoss.apply(labels.contiguous().long(), given, mode, float(fpr_alpha), *steps))

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
 
 CHUNK_ROWS = 32          # mtmc_pool_chunk_rows(): rows per chunk of the kernels' decomposition
 MAX_FEAT_DIM = 16384
@@ -68,10 +68,8 @@ def _forward_raw(embeds: torch.Tensor, offsets_dev: torch.Tensor, out=None, info
     if need == 0:
         raise RuntimeError("mtmc_mpn.pool_tracklets: unsupported size")
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.mtmc_pool_tracklets(embeds.data_ptr(), embeds.stride(0), d, f, offsets_dev.data_ptr(), n, out.data_ptr(),
-                                           info.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           torch.cuda.current_stream(dev).cuda_stream))
+    _call.run(dev, lib.mtmc_pool_tracklets, embeds.data_ptr(), embeds.stride(0), d, f, offsets_dev.data_ptr(), n, out.data_ptr(),
+              info.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
     return out
 
 
@@ -89,10 +87,8 @@ def _backward_raw(grad_out: torch.Tensor, offsets_dev: torch.Tensor, n_rows: int
     if n == 0 or n_rows == 0:
         out.zero_()
         return out
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.mtmc_pool_tracklets_backward(grad_out.data_ptr(), n_rows, f, offsets_dev.data_ptr(), n, out.data_ptr(),
-                                                    out.stride(0), torch.cuda.current_stream(dev).cuda_stream))
+    _call.run(dev, _lib.load().mtmc_pool_tracklets_backward, grad_out.data_ptr(), n_rows, f, offsets_dev.data_ptr(), n,
+              out.data_ptr(), out.stride(0), _call.stream(dev))
     return out
 
 
@@ -125,8 +121,7 @@ def pool_tracklets(embeds: torch.Tensor, lengths=None, *, offsets=None, check: b
     With grad mode on and `embeds.requires_grad` the result carries the gradient back to `embeds`."""
     if (lengths is None) == (offsets is None):
         raise ValueError("mtmc_mpn.pool_tracklets: give exactly one of lengths and offsets")
-    if not (isinstance(embeds, torch.Tensor) and embeds.is_cuda):
-        raise RuntimeError("mtmc_mpn.pool_tracklets: embeds must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu("pool_tracklets", embeds)
     if embeds.dim() != 2 or embeds.dtype != torch.float32 or embeds.shape[1] % 4 or not 4 <= embeds.shape[1] <= MAX_FEAT_DIM:
         raise RuntimeError(f"mtmc_mpn.pool_tracklets: embeds must be float32 [D, F] with F a multiple of 4, at most {MAX_FEAT_DIM}")
     dev = embeds.device

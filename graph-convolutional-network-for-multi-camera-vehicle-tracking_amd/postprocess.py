@@ -10,7 +10,7 @@ import types
 
 import torch
 
-from . import _lib
+from . import _call, _lib
 
 CUTTING, PRUNING, SPLITTING = 1, 2, 4
 _STATUS = {1: "more active edges than max_active: predictions left at argmax",
@@ -32,8 +32,7 @@ def postprocess(logits, edge_index, num_nodes: int, num_cameras: int, cutting=Tr
     Pass `preds_prob` ([E,2] or [E]) and `predictions` instead of logits (`logits=None`) to post-process given
     probabilities exactly."""
     ref = logits if logits is not None else predictions
-    if not (isinstance(ref, torch.Tensor) and ref.is_cuda):
-        raise RuntimeError("mtmc_mpn.postprocess: tensors must be on a ROCm GPU (no CPU path)")
+    _call.require_gpu("postprocess", ref)
     dev = ref.device
     e = int(edge_index.shape[1])
     if edge_index.dtype != torch.int64 or edge_index.shape[0] != 2 or edge_index.device != dev:
@@ -61,13 +60,10 @@ def postprocess(logits, edge_index, num_nodes: int, num_cameras: int, cutting=Tr
         raise RuntimeError("mtmc_mpn.postprocess: unsupported size")
     ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
     flags = (CUTTING if _flag(cutting) else 0) | (PRUNING if _flag(pruning) else 0) | (SPLITTING if _flag(splitting) else 0)
-    with torch.cuda.device(dev):
-        rc = lib.mtmc_postprocess(logits.data_ptr() if logits is not None else None, row.data_ptr() if e else None,
-                                  col.data_ptr() if e else None, row.stride(0) if e else 1, num_nodes, e, num_cameras,
-                                  flags, max_active, prob1.data_ptr(), pred.data_ptr(), ids.data_ptr(), info.data_ptr(),
-                                  ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"mtmc_mpn.postprocess failed (code {rc})")
+    _call.run(dev, lib.mtmc_postprocess, logits.data_ptr() if logits is not None else None, row.data_ptr() if e else None,
+              col.data_ptr() if e else None, row.stride(0) if e else 1, num_nodes, e, num_cameras,
+              flags, max_active, prob1.data_ptr(), pred.data_ptr(), ids.data_ptr(), info.data_ptr(),
+              ws.data_ptr(), ws.numel(), _call.stream(dev))
     out = types.SimpleNamespace(ID_pred=ids, predictions=pred, preds_prob1=prob1, info_dev=info, info=None)
     if check:
         v = info.cpu().tolist()

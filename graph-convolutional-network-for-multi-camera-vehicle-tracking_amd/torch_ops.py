@@ -25,7 +25,7 @@ import types
 
 import torch
 
-from . import _lib
+from . import _call, _lib
 from . import config as _config
 from .engine import ForwardEngine, _check_param, layer_slots, n_classified_steps
 
@@ -174,7 +174,7 @@ def _mp_backward(tape, x, edge_index, edge_attr, params, config, training, seed,
         steps = (C.c_void_p * max(n_steps, 1))(*[(dl.data_ptr() + i * step_bytes) if dl is not None and dl.numel() else None
                                                  for i in range(n_steps)])
     with torch.cuda.device(dev):
-        prep.call.stream = _stream(dev)
+        prep.call.stream = _call.stream(dev)
         _lib.check(eng.lib.mtmc_mpn_backward_flat(
             C.byref(prep.model), C.byref(prep.call), steps, dh.data_ptr() if dh is not None else None,
             flat.data_ptr(), flat.numel(), dx.data_ptr() if need_x else None, dattr.data_ptr() if need_attr else None))
@@ -302,9 +302,7 @@ def _scatter_args(src, index, dim, dim_size):
         raise NotImplementedError("mtmc_mpn.scatter_*: only dim=0 (the reference's call form) is implemented")
     if index.dim() != 1 or index.shape[0] != src.shape[0]:
         raise RuntimeError("mtmc_mpn.scatter_*: index must be 1-D with one entry per row of src")
-    if not src.is_cuda or index.device != src.device:
-        raise RuntimeError(f"mtmc_mpn.scatter_*: src and index must be on the same ROCm device (got {src.device} and "
-                           f"{index.device}); there is no CPU path")
+    _call.require_gpu("scatter_*", src, index)
     if index.dtype not in (torch.int64, torch.int32):
         raise RuntimeError("mtmc_mpn.scatter_*: index must be an integer tensor")
     if dim_size is None:
@@ -312,26 +310,17 @@ def _scatter_args(src, index, dim, dim_size):
     return src.reshape(src.shape[0], -1).contiguous(), index.contiguous().long(), int(dim_size)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 @torch.library.impl("mtmc_mpn::scatter_add", "CUDA")
 def _scatter_add(src, index, dim, dim_size):
     s2, idx, n = _scatter_args(src, index, dim, dim_size)
+    exact = not src.dtype.is_floating_point        # utils.py:173-174: int64 in, int64 out
+    s2 = s2.long() if exact else s2.float()
+    res = torch.empty((n, s2.shape[1]), dtype=s2.dtype, device=src.device)
     lib = _lib.load()
-    with torch.cuda.device(src.device):
-        if not src.dtype.is_floating_point:        # utils.py:173-174: int64 in, int64 out
-            s2 = s2.long()
-            res = torch.empty((n, s2.shape[1]), dtype=torch.int64, device=src.device)
-            _lib.check(lib.mtmc_scatter_add_i64(s2.data_ptr(), idx.data_ptr(), s2.shape[0], s2.shape[1], n,
-                                                res.data_ptr(), _stream(src.device)))
-            return res.reshape((n,) + tuple(src.shape[1:])).to(src.dtype)
-        s2 = s2.float()
-        res = torch.empty((n, s2.shape[1]), dtype=torch.float32, device=src.device)
-        _lib.check(lib.mtmc_scatter_add(s2.data_ptr(), idx.data_ptr(), s2.shape[0], s2.shape[1], n, res.data_ptr(),
-                                        _stream(src.device)))
-    return res.reshape((n,) + tuple(src.shape[1:]))
+    _call.run(src.device, lib.mtmc_scatter_add_i64 if exact else lib.mtmc_scatter_add, s2.data_ptr(), idx.data_ptr(),
+              s2.shape[0], s2.shape[1], n, res.data_ptr(), _call.stream(src.device))
+    res = res.reshape((n,) + tuple(src.shape[1:]))
+    return res.to(src.dtype) if exact else res
 
 
 @torch.library.impl("mtmc_mpn::scatter_mean", "CUDA")
@@ -340,9 +329,8 @@ def _scatter_mean(src, index, dim, dim_size):
     s2 = s2.float()
     res = torch.empty((n, s2.shape[1]), dtype=torch.float32, device=src.device)
     cnt = torch.empty((max(n, 1),), dtype=torch.float32, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.load().mtmc_scatter_mean(s2.data_ptr(), idx.data_ptr(), s2.shape[0], s2.shape[1], n,
-                                                 res.data_ptr(), cnt.data_ptr(), _stream(src.device)))
+    _call.run(src.device, _lib.load().mtmc_scatter_mean, s2.data_ptr(), idx.data_ptr(), s2.shape[0], s2.shape[1], n,
+              res.data_ptr(), cnt.data_ptr(), _call.stream(src.device))
     return res.reshape((n,) + tuple(src.shape[1:]))
 
 
@@ -352,9 +340,8 @@ def _scatter_max(src, index, dim, dim_size):
     s2 = s2.float()
     res = torch.empty((n, s2.shape[1]), dtype=torch.float32, device=src.device)
     arg = torch.empty((n, s2.shape[1]), dtype=torch.int64, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.load().mtmc_scatter_max(s2.data_ptr(), idx.data_ptr(), s2.shape[0], s2.shape[1], n,
-                                                res.data_ptr(), arg.data_ptr(), _stream(src.device)))
+    _call.run(src.device, _lib.load().mtmc_scatter_max, s2.data_ptr(), idx.data_ptr(), s2.shape[0], s2.shape[1], n,
+              res.data_ptr(), arg.data_ptr(), _call.stream(src.device))
     shape = (n,) + tuple(src.shape[1:])
     return res.reshape(shape), arg.reshape(shape)
 

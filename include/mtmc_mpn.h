@@ -30,7 +30,9 @@
  * All floating tensors are fp32, row-major, contiguous unless a stride argument says otherwise;
  * BatchNorm statistics are accumulated in fp64.  All work is enqueued on `stream` (a hipStream_t
  * passed as void*; NULL = the default stream); no entry point synchronises or allocates.
- * Return value: 0 on success, a negative MTMC_E_* code otherwise (mtmc_mpn_last_error() gives text).
+ * Return value: 0 on success, a negative MTMC_E_* code otherwise.  Every entry point that returns a code then leaves its
+ * reason in mtmc_mpn_last_error() (one text per host thread); the stand-alone operators start it with their own name
+ * without `mtmc_`, as in "edge_loss_forward: ...".
  */
 #ifndef MTMC_MPN_H
 #define MTMC_MPN_H

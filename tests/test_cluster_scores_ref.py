@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import cluster_scores_ref as ref
+from abi_refusal import refused
 from cs_cases import cpu_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,7 +113,8 @@ def test_workspace_query_is_host_only_monotonic_and_linear():
 
 
 def test_c_entry_points_refuse_before_any_launch():
-    """MTMC_E_ARG, checked with NULL / host values only (every check precedes the first launch)"""
+    """MTMC_E_ARG, checked with NULL / host values only (every check precedes the first launch); each refusal names its
+    entry point in mtmc_mpn_last_error()"""
     from mtmc_mpn import _lib
     lib = _lib.load()
     buf = (ctypes.c_double * 64)()
@@ -123,12 +125,12 @@ def test_c_entry_points_refuse_before_any_launch():
         return lib.mtmc_cluster_scores(t, st, pr, sp, n, scores, counts, ws, nbytes, None)
     for bad in (dict(n=0), dict(n=-1), dict(n=1048577), dict(t=None), dict(pr=None), dict(scores=None), dict(counts=None),
                 dict(ws=None), dict(ws=p + 4), dict(nbytes=need - 1), dict(st=-1), dict(sp=-2)):
-        assert cs(**bad) == _lib.E_ARG, bad
+        assert refused(lib, lambda: cs(**bad), _lib.E_ARG, "cluster_scores"), bad
 
     def prf(y=p, sy=1, x=p, sx=1, e=10, counts=p, out=p):
         return lib.mtmc_edge_prf(y, sy, x, sx, e, counts, out, None)
     for bad in (dict(e=-1), dict(y=None), dict(x=None), dict(counts=None), dict(out=None), dict(sy=-1), dict(sx=-1)):
-        assert prf(**bad) == _lib.E_ARG, bad
+        assert refused(lib, lambda: prf(**bad), _lib.E_ARG, "edge_prf"), bad
 
 
 def test_python_surface_refuses():

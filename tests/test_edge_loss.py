@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from abi_refusal import refused
 from edge_loss_ref import edge_loss_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +30,8 @@ def test_entry_points_are_declared_and_bound():
 
 
 def test_argument_errors_are_refused_before_any_launch():
-    """MTMC_E_ARG of the C entry points, checked with NULL / host values only (every check precedes the first launch)."""
+    """MTMC_E_ARG of the C entry points, checked with NULL / host values only (every check precedes the first launch); each
+    refusal names its entry point in mtmc_mpn_last_error()."""
     import ctypes
     from mtmc_mpn import _lib
     lib = _lib.load()
@@ -42,13 +44,13 @@ def test_argument_errors_are_refused_before_any_launch():
     for bad in (dict(c=0), dict(c=3), dict(s=0), dict(n=-1), dict(logits=None), dict(labels=None), dict(scratch=None),
                 dict(record=None), dict(out=None), dict(conf=None), dict(mode=3), dict(mode=-1), dict(mode=1, weight=None),
                 dict(logits=p + 4), dict(nbytes=need - 8)):
-        assert fwd(**bad) == _lib.E_ARG, bad
+        assert refused(lib, lambda: fwd(**bad), _lib.E_ARG, "edge_loss_forward"), bad
 
     def bwd(logits=p, labels=p, n=10, c=2, s=3, grad=p, record=p, d=p):
         return lib.mtmc_edge_loss_backward(logits, labels, n, c, s, grad, record, d, None)
     for bad in (dict(c=0), dict(c=4), dict(s=0), dict(n=-1), dict(logits=None), dict(labels=None), dict(grad=None),
                 dict(record=None), dict(d=None), dict(logits=p + 4), dict(d=p + 4)):
-        assert bwd(**bad) == _lib.E_ARG, bad
+        assert refused(lib, lambda: bwd(**bad), _lib.E_ARG, "edge_loss_backward"), bad
 
 
 def test_edge_loss_refuses():

@@ -87,6 +87,19 @@ def test_wave_and_workgroup_edges(name):
     check(name, t, p)
 
 
+@pytest.mark.parametrize("n", [1, 64, 257])
+def test_counts_with_one_two_and_n_distinct_labels(n):
+    """counts[7] exactly at one node, one wave and one row past a workgroup, for every pairing of 1, 2 and n distinct labels
+    on either side (n = 1: all the same partition)"""
+    i = np.arange(n, dtype=np.int64)
+    for kt in (1, 2, n):
+        for kp in (1, 2, n):
+            t, p = i % kt, (5 * i + 1) % kp                           # 5 is coprime to 64 and 257: kp = n gives a permutation
+            assert len(set(t.tolist())) == min(kt, n) and len(set(p.tolist())) == min(kp, n)
+            _, counts = check(f"n{n}_{kt}x{kp}", t, p)
+            assert counts[:2] == [min(kt, n), min(kp, n)] and sum(counts[3:]) == n * (n - 1)
+
+
 def test_full_tables_all_labels_distinct():
     g = np.random.default_rng(11)
     n = 4096
@@ -182,6 +195,19 @@ def test_edge_prf_cases():
     # any stride
     r = mtmc_mpn.edge_prf(torch.from_numpy(pred).cuda()[::3], torch.from_numpy(labels).cuda()[::3])
     assert r.confusion.cpu().tolist() == ref.edge_prf_ref(pred[::3], labels[::3])[0]
+
+
+@pytest.mark.parametrize("e", [1, 63, 64, 65, 255, 256, 257, 256 * 256 + 1])
+def test_edge_prf_at_wave_and_workgroup_edges(e):
+    """Exact counts around one wave (64) and one workgroup (256), and one row past a full grid of 256 workgroups, where the
+    grid-stride loop takes a second trip; rows whose label or prediction is neither 0 nor 1 are skipped."""
+    g = np.random.default_rng(e)
+    labels = (g.random(e) < 0.3).astype(np.int64)
+    pred = np.where(g.random(e) < 0.2, 1 - labels, labels).astype(np.int64)
+    labels[3::11] = -100
+    pred[4::13] = 2
+    counts, _ = check_prf(f"edge_e{e}", pred, labels)
+    assert sum(counts) == int((((labels == 0) | (labels == 1)) & ((pred == 0) | (pred == 1))).sum())
 
 
 # ---- evaluate ----------------------------------------------------------------------------------------------------

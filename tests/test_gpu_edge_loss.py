@@ -116,6 +116,20 @@ def test_past_the_forward_grids_cap(c):
 
 
 @pytest.mark.parametrize("c", [2, 1])
+@pytest.mark.parametrize("e, s", [(65, 1), (257, 3), (65, 1025)])
+def test_counts_at_wave_edges_and_past_the_step_grids_cap(e, s, c):
+    """confusion [S, 4] exactly, one row past a wave and past a workgroup; S = 1025 is one step more than the 1024 the grid's
+    y dimension takes, so one workgroup reduces two steps and uses its LDS words twice.  Loss and gradient at the file's
+    bars there as well."""
+    x, y = make_inputs(e, s, c, seed=900 + 10 * c + s)
+    kw = dict(weight="balanced") if c == 2 else dict(pos_weight="balanced")
+    r, grad = run_ours(x, y, fpr_alpha=1.0, **kw)
+    ref, ref_grad = run_ref(x, y, fpr_alpha=1.0, **kw)
+    assert r.confusion.shape == (s, 4) and r.confusion.sum(1).tolist() == [int(((y == 0) | (y == 1)).sum())] * s
+    compare(r, grad, ref, ref_grad, f"E={e} S={s} C={c}")
+
+
+@pytest.mark.parametrize("c", [2, 1])
 @pytest.mark.parametrize("only", ["0", "1"])
 def test_one_class_only(only, c):
     """All labels 0 / all labels 1: balanced falls back to (1, 1), the empty class reports 0 / 0.5, FPR is 0 without

@@ -1,4 +1,5 @@
 """mtmc_mpn.ops.cross_entropy (fused forward + backward) against torch.nn.functional.cross_entropy."""
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -72,6 +73,23 @@ def test_edge_confusion_counts():
     # the reference's FPR (train.py:100-102)
     fp = torch.sum(pred[y == 0]); tn = pred[y == 0].shape[0] - fp
     assert abs(got[1] / (got[1] + got[2]) - float(fp / (fp + tn))) < 1e-6      # torch divides in float32
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 256 * 256 + 1])
+def test_edge_confusion_at_wave_and_workgroup_edges(n):
+    """Exact counts around one wave (64) and one workgroup (256), and one row past a full grid of 256 workgroups, where the
+    grid-stride loop takes a second trip; three classes, ties and rows labelled neither 0 nor 1 included."""
+    g = np.random.default_rng(n)
+    x = g.standard_normal((n, 3)).astype(np.float32)
+    x[::5, 1] = x[::5, 0]                                            # ties between classes 0 and 1: the first maximum
+    y = (g.random(n) < 0.3).astype(np.int64)
+    y[3::11] = -100
+    y[4::13] = 2
+    pred, keep = np.argmax(x, 1) == 1, (y == 0) | (y == 1)
+    want = [int((pred & (y == 1)).sum()), int((pred & (y == 0)).sum()), int((~pred & (y == 0)).sum()),
+            int((~pred & (y == 1)).sum())]
+    assert sum(want) == int(keep.sum())
+    assert ops.edge_confusion(torch.from_numpy(x).to(DEV), torch.from_numpy(y).to(DEV)).cpu().tolist() == want
 
 
 @pytest.mark.parametrize("reduction,weighted", [("mean", True), ("mean", False), ("sum", True)])

@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+from abi_refusal import refused
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mtmc_graph_backward_workspace_bytes", "mtmc_build_graph_backward")
 
@@ -51,7 +53,6 @@ def test_bad_arguments_are_refused_before_any_launch():
                 dict(feats=0x10004), dict(x=0x70008), dict(d_x=0x90004), dict(out=0xb0008), dict(edge_attr=0x80004),
                 dict(d_attr=0xa0004), dict(stride=2049), dict(ws=0x100080),
                 dict(n=0), dict(n=46001), dict(f=2040), dict(f=0), dict(n_cams=0), dict(e=-1), dict(out=0x90000)):
-        assert call(lib, **bad) == _lib.E_ARG, bad
-    assert call(lib, ws=None) == _lib.E_WORKSPACE
-    assert call(lib, ws_bytes=lib.mtmc_graph_backward_workspace_bytes(450, 2048) - 1) == _lib.E_WORKSPACE
-    assert call(lib, ws_bytes=0) == _lib.E_WORKSPACE
+        assert refused(lib, lambda: call(lib, **bad), _lib.E_ARG, "build_graph_backward"), bad
+    for bad in (dict(ws=None), dict(ws_bytes=lib.mtmc_graph_backward_workspace_bytes(450, 2048) - 1), dict(ws_bytes=0)):
+        assert refused(lib, lambda: call(lib, **bad), _lib.E_WORKSPACE, "build_graph_backward"), bad
