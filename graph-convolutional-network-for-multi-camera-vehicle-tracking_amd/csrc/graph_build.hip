@@ -3,9 +3,17 @@
 // train.py:316-342):
 //     x = F.normalize(feats, p=2, dim=0);  edges = cross-camera cartesian products;  edge labels;
 //     edge_attr[e] = [ ||x_r - x_c + 1e-6||_2 ,  1 - cos(x_r, x_c) ]
-// The per-edge 2048-d gather (16 KB per edge in the reference) becomes ONE Gram matrix G = X X^T on the fp32
-// matrix cores (gemm_bn_kernel) plus an 8-byte-per-edge epilogue:
+// The per-edge 2048-d gather (16 KB per edge in the reference) becomes ONE Gram matrix G = X X^T plus an
+// 8-byte-per-edge epilogue:
 //     ||a-b+eps||^2 = |a|^2 + |b|^2 - 2 a.b + 2 eps (sum a - sum b) + F eps^2,    cos = a.b / (max(|a|,e) max(|b|,e))
+// G goes through launch_gemm_bn without |.|max words (M = Nout = N, K = F), so gemm_plan picks, at fp32 accuracy throughout:
+//     N <= 960            gemm_bn_kernel<1,1,*> (exact fp32 MFMA, 64 x 64 tiles): split-K 4 where F % 256 == 0, split-K 2 where
+//                         only F % 128 == 0, unsplit where F <= 128 or F % 128 != 0; BK = 64 where the slice is a multiple of 64,
+//                         else BK = 32
+//     961 <= N <= 1920    the same kernel, unsplit at every F (256 tiles or more)
+//     N >= 1921           gemm_bn_bf16x6_kernel<2,2,32> (128 x 128 tiles, six bf16 products per fp32 product)
+//     F > 6144            linear_generic_kernel (one thread per element, a chain of F fmaf) up to N = 2048; refused above that
+// tests/gram_cases.py names a case for each line and tests/test_gram_cases.py pins the splits.
 #include "api_error.h"
 #include "kernels.h"
 
@@ -131,9 +139,15 @@ struct GraphBwdCoef {
   const float* X; float* out; int f;                // gb_bwd_near_kernel: x [N][F] and dXn [N][F]
 };
 
-// Near-duplicate ends (d^2 < 1e-3 (rho_r^2 + rho_c^2)): the Gram form of the forward has lost d to cancellation there (its
-// absolute error is ~1e-6 (rho_r^2 + rho_c^2)) and -a x_c + a x_r would cancel again in the product, so the distance
-// term of such an edge stays out of S / delta / kappa and gb_bwd_near_kernel takes it from the 2048-d difference itself.
+// Near-duplicate ends (d^2 < 1e-3 (rho_r^2 + rho_c^2)): the Gram form of the forward has lost d to cancellation there and
+// -a x_c + a x_r would cancel again in the product, so the distance term of such an edge stays out of S / delta / kappa and
+// gb_bwd_near_kernel takes it from the F-dimensional difference itself.  The forward's absolute error on d^2 is
+// c (rho_r^2 + rho_c^2) with c growing with the length of the fp32 chain; measured worst case per regime on MI355X
+// (profiles/graph_build_envelope.txt; every case within 0.66 of twice a CPU model of the unsplit fp32 chain):
+//     exact fp32, F <= 384 (BK 32 / BK 64 / split 2): 1.9e-7 .. 5.8e-7        split-K 4, F = 256: 2.7e-7
+//     exact fp32 unsplit, F = 2048 (N 961..1920):     2.9e-6                  bf16x6: 3.6e-7 (F = 64), 1.5e-6 (F = 2048)
+//     scalar path, F = 6176:                          2.8e-6
+// i.e. 2e-4 to 3e-3 of the threshold: an edge just above it has its d^2 to 0.3 % or better.
 __device__ __forceinline__ bool gb_near(float d, float rho_r, float rho_c) {
   return d * d < 1e-3f * (rho_r * rho_r + rho_c * rho_c);
 }

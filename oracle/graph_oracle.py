@@ -19,15 +19,20 @@ import torch
 import torch.nn.functional as F
 
 
-def build(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: bool = True, chunk: int = 1 << 16):
-    x = F.normalize(node_feats, p=2, dim=0) if l2norm else node_feats
+def topology(cam_ids):
+    """edge_index [2, E] alone (inference.py:407-413): the integer reference of graphs too large for build()'s gathers."""
     cams = np.asarray(cam_ids)
     nodes = np.asarray(range(len(cams)))
     blocks = []
     for c in np.unique(cams):
         inside, outside = nodes[cams == c], nodes[cams != c]
         blocks.append(torch.cartesian_prod(torch.from_numpy(inside), torch.from_numpy(outside)))
-    edge_index = torch.cat(blocks, dim=0).T
+    return torch.cat(blocks, dim=0).T
+
+
+def build(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: bool = True, chunk: int = 1 << 16):
+    x = F.normalize(node_feats, p=2, dim=0) if l2norm else node_feats
+    edge_index = topology(cam_ids)
     row, col = edge_index[0], edge_index[1]
     attr = torch.empty(row.numel(), 2, dtype=x.dtype)
     for s in range(0, row.numel(), chunk):
