@@ -95,7 +95,8 @@ EXPORTS = ["mtmc_mpn_abi_version", "mtmc_mpn_last_error", "mtmc_mpn_workspace_by
            "mtmc_graph_backward_workspace_bytes", "mtmc_build_graph_backward",
            "mtmc_edge_loss_scratch_bytes", "mtmc_edge_loss_forward", "mtmc_edge_loss_backward",
            "mtmc_cluster_scores_workspace_bytes", "mtmc_cluster_scores", "mtmc_edge_prf",
-           "mtmc_pool_chunk_rows", "mtmc_pool_tracklets_workspace_bytes", "mtmc_pool_tracklets", "mtmc_pool_tracklets_backward"]
+           "mtmc_pool_chunk_rows", "mtmc_pool_tracklets_workspace_bytes", "mtmc_pool_tracklets", "mtmc_pool_tracklets_backward",
+           "mtmc_scatter_add_backward", "mtmc_scatter_mean_backward", "mtmc_scatter_max_backward"]
 
 _lib = None
 
@@ -217,6 +218,14 @@ def load() -> C.CDLL:
     lib.mtmc_scatter_max.restype = C.c_int32
     lib.mtmc_scatter_max.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
+    lib.mtmc_scatter_add_backward.restype = C.c_int32
+    lib.mtmc_scatter_add_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.mtmc_scatter_mean_backward.restype = C.c_int32
+    lib.mtmc_scatter_mean_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+    lib.mtmc_scatter_max_backward.restype = C.c_int32
+    lib.mtmc_scatter_max_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                              C.c_void_p]
     lib.mtmc_mlp_layer_forward.restype = C.c_int32
     lib.mtmc_mlp_layer_forward.argtypes = [C.POINTER(Layer), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p]

@@ -233,6 +233,39 @@ int32_t mtmc_scatter_max(const float* src, const int64_t* index, int64_t n_src, 
   return scatter_common("scatter_max", src, index, n_src, n_cols, dim_size, out, nullptr, arg_out, 2, stream);
 }
 
+static int scatter_backward_common(const char* entry, const float* grad_out, const int64_t* arg, const int64_t* index,
+                                   int64_t n_src, int64_t n_cols, int64_t dim_size, int32_t* count, float* grad_src, int mode,
+                                   void* stream) {
+  if (n_src < 0 || n_cols < 0 || dim_size < 0) return fail(MTMC_E_ARG, "%s: n_src, n_cols and dim_size must be >= 0", entry);
+  if (n_src == 0 || n_cols == 0) return MTMC_OK;
+  // (without destination rows there is no gradient to read: every row of grad_src is zero)
+  if (!index || !grad_src || (dim_size > 0 && !grad_out)) return fail(MTMC_E_ARG, "%s: NULL grad_out, index or grad_src", entry);
+  if (mode == 2 && dim_size > 0 && !arg) return fail(MTMC_E_ARG, "%s: NULL arg", entry);
+  if (mode == 1 && dim_size > 0 && !count) return fail(MTMC_E_ARG, "%s: needs count_scratch[dim_size]", entry);
+  if ((((uintptr_t)grad_out | (uintptr_t)grad_src | (uintptr_t)count) & 3) || (((uintptr_t)index | (uintptr_t)arg) & 7))
+    return fail(MTMC_E_ARG, "%s: grad_out, grad_src and count_scratch must be 4-byte, index and arg 8-byte aligned", entry);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mode == 1 && dim_size > 0 && hipMemsetAsync(count, 0, (size_t)dim_size * sizeof(int32_t), s) != hipSuccess)
+    return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
+  mtmc::launch_scatter_backward(grad_out, arg, index, n_src, n_cols, dim_size, count, grad_src, mode, s);
+  return launched(entry);
+}
+int32_t mtmc_scatter_add_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                                  float* grad_src, void* stream) {
+  return scatter_backward_common("scatter_add_backward", grad_out, nullptr, index, n_src, n_cols, dim_size, nullptr, grad_src, 0,
+                                 stream);
+}
+int32_t mtmc_scatter_mean_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                                   int32_t* count_scratch, float* grad_src, void* stream) {
+  return scatter_backward_common("scatter_mean_backward", grad_out, nullptr, index, n_src, n_cols, dim_size, count_scratch,
+                                 grad_src, 1, stream);
+}
+int32_t mtmc_scatter_max_backward(const float* grad_out, const int64_t* arg, const int64_t* index, int64_t n_src, int64_t n_cols,
+                                  int64_t dim_size, float* grad_src, void* stream) {
+  return scatter_backward_common("scatter_max_backward", grad_out, arg, index, n_src, n_cols, dim_size, nullptr, grad_src, 2,
+                                 stream);
+}
+
 int32_t mtmc_mlp_layer_forward(const mtmc_layer* layer, const float* x, int64_t x_row_stride, int64_t rows, float* y,
                                double* stats_scratch, void* stream) {
   if (!layer || !layer->weight || !layer->bias || !x || !y || rows < 1) return fail(MTMC_E_ARG, "bad mlp layer arguments");

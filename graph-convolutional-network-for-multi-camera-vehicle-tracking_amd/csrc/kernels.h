@@ -326,6 +326,9 @@ void launch_scatter(const float* src, const int64_t* index, int64_t n_src, int64
 
 void launch_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                             int64_t* out, hipStream_t s);
+// the gradient of launch_scatter's out with respect to src (mode as there); count: int[dim_size] zeroed on s (mean only)
+void launch_scatter_backward(const float* g, const int64_t* arg, const int64_t* index, int64_t n_src, int64_t n_cols,
+                             int64_t dim_size, int* count, float* d_src, int mode, hipStream_t s);
 
 size_t pp_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t max_active);
 int launch_postprocess(const float* logits, const int64_t* row, const int64_t* col, int64_t idx_stride, int64_t n_nodes,

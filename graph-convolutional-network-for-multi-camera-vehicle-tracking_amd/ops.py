@@ -1,7 +1,8 @@
 """Stand-alone ops of the hot path, for callers that use the pieces on their own:
 
   scatter_add / scatter_mean / scatter_max   the call forms of the third-party `torch_scatter` op the
-      reference aggregates with (`scatter_*(src, index, dim=0, dim_size=N)`, reference models/mpn.py:196-202)
+      reference aggregates with (`scatter_*(src, index, dim=0, dim_size=N)`, reference models/mpn.py:196-202);
+      differentiable (once) with respect to a floating `src`, like the op they stand in for
   mlp_forward                                `MLP.forward` (reference models/mlp.py:32-33), eval mode
   cross_entropy                              `F.cross_entropy(input, target, weight, reduction=...)` on the [E, C<=4]
       edge logits, forward and backward fused (the training callers' loss, reference train.py:88-93, :109-142)
@@ -33,7 +34,8 @@ def _scatter(name, src, index, dim, out, dim_size):
 
 def scatter_add(src, index, dim=0, out=None, dim_size=None):
     """`torch_scatter.scatter_add(src, index, dim=0, dim_size=N)`; integer `src` (the 1-D int64 form of reference
-    utils.py:173-174) is summed exactly and keeps its dtype."""
+    utils.py:173-174) is summed exactly and keeps its dtype.  Differentiable with respect to a floating `src`:
+    d_src[e] = grad[index[e]], zeros for a row whose index lies outside [0, N)."""
     return _scatter("scatter_add", src, index, dim, out, dim_size)
 
 
@@ -41,11 +43,15 @@ scatter_sum = scatter_add
 
 
 def scatter_mean(src, index, dim=0, out=None, dim_size=None):
+    """`torch_scatter.scatter_mean(src, index, dim=0, dim_size=N)`: the sum divided by max(count, 1).  Differentiable with
+    respect to `src`: d_src[e] = grad[index[e]] / max(count[index[e]], 1)."""
     return _scatter("scatter_mean", src, index, dim, out, dim_size)
 
 
 def scatter_max(src, index, dim=0, out=None, dim_size=None):
-    """Returns (values, argmax) like torch_scatter; rows nobody writes hold 0 and argmax = src.size(0)."""
+    """Returns (values, argmax) like torch_scatter; rows nobody writes hold 0 and argmax = src.size(0).  `values` is
+    differentiable with respect to `src`: the gradient of values[r, c] goes to row argmax[r, c], the first row that attains
+    the maximum, and to no other; the argmax carries none."""
     return _scatter("scatter_max", src, index, dim, out, dim_size)
 
 

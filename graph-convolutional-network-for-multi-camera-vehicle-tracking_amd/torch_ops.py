@@ -15,12 +15,16 @@ through `torch.ops.mtmc_mpn.mp_backward`.  CUDA (= ROCm) dispatch key only: CPU 
       -> (flat parameter gradients, d_x, d_edge_attr)         (reference train.py:424, loss.backward())
   encode_nodes(x, params, config) -> h0[N,32]                 the node encoder alone (models/mpn.py:131, eval mode)
   scatter_add / scatter_mean / scatter_max(src, index, dim, dim_size)   the torch_scatter call forms
-      (models/mpn.py:196-202; the 1-D int64 form of utils.py:173-174 returns int64)
+      (models/mpn.py:196-202; the 1-D int64 form of utils.py:173-174 returns int64); differentiable with respect to a
+      floating `src` through
+  scatter_add_backward / scatter_mean_backward(grad, index, n_src), scatter_max_backward(grad, arg, index, n_src)
+      -> d_src [n_src, ...] float32: gathers of grad [dim_size, ...] by index (csrc/scatter_ops.hip), bitwise repeatable
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 import types
 
 import torch
@@ -108,6 +112,9 @@ torch.library.define("mtmc_mpn::encode_nodes", "(Tensor x, Tensor[] params, str 
 torch.library.define("mtmc_mpn::scatter_add", "(Tensor src, Tensor index, int dim, int? dim_size) -> Tensor")
 torch.library.define("mtmc_mpn::scatter_mean", "(Tensor src, Tensor index, int dim, int? dim_size) -> Tensor")
 torch.library.define("mtmc_mpn::scatter_max", "(Tensor src, Tensor index, int dim, int? dim_size) -> (Tensor, Tensor)")
+torch.library.define("mtmc_mpn::scatter_add_backward", "(Tensor grad, Tensor index, int n_src) -> Tensor")
+torch.library.define("mtmc_mpn::scatter_mean_backward", "(Tensor grad, Tensor index, int n_src) -> Tensor")
+torch.library.define("mtmc_mpn::scatter_max_backward", "(Tensor grad, Tensor arg, Tensor index, int n_src) -> Tensor")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -307,7 +314,12 @@ def _scatter_args(src, index, dim, dim_size):
         raise RuntimeError("mtmc_mpn.scatter_*: index must be an integer tensor")
     if dim_size is None:
         dim_size = int(index.max()) + 1 if index.numel() else 0
-    return src.reshape(src.shape[0], -1).contiguous(), index.contiguous().long(), int(dim_size)
+    return _rows(src), index.contiguous().long(), int(dim_size)
+
+
+def _rows(t):
+    """`t` as a contiguous [t.shape[0], columns] matrix (the columns counted, not inferred: a tensor without rows has them too)."""
+    return t.reshape(t.shape[0], math.prod(t.shape[1:])).contiguous()
 
 
 @torch.library.impl("mtmc_mpn::scatter_add", "CUDA")
@@ -367,3 +379,94 @@ def _scatter_mean_fake(src, index, dim, dim_size):
 def _scatter_max_fake(src, index, dim, dim_size):
     shp = _scatter_fake_shape(src, index, dim_size)
     return src.new_empty(shp, dtype=torch.float32), src.new_empty(shp, dtype=torch.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the scatter backward: d_src[e] from grad[index[e]] (csrc/scatter_ops.hip), and autograd on the three forward ops
+# ---------------------------------------------------------------------------------------------------------------
+def _scatter_backward_args(name, grad, index, n_src, arg=None):
+    """grad [dim_size, ...] as a contiguous float32 matrix (an expanded, stride-0 gradient is what `.sum().backward()` hands
+    over), index as contiguous int64, arg as a contiguous int64 matrix of grad's shape: every pointer the kernels get."""
+    _call.require_gpu(name, grad, index, *(() if arg is None else (arg,)))
+    if grad.dim() < 1 or not grad.dtype.is_floating_point:
+        raise RuntimeError(f"mtmc_mpn.{name}: grad must be a floating tensor [dim_size, ...]")
+    if index.dim() != 1 or index.shape[0] != n_src or index.dtype not in (torch.int64, torch.int32):
+        raise RuntimeError(f"mtmc_mpn.{name}: index must be an int64 or int32 tensor [n_src]")
+    if arg is not None:
+        if arg.dtype != torch.int64 or arg.shape != grad.shape:
+            raise RuntimeError(f"mtmc_mpn.{name}: arg must be the int64 argmax of scatter_max, of grad's shape")
+        arg = _rows(arg)
+    return _rows(grad.float()), index.contiguous().long(), arg
+
+
+def _scatter_backward_out(grad, n_src):
+    """d_src as the kernels write it, [n_src, columns], and in the shape the op returns, [n_src, *grad.shape[1:]]."""
+    d = torch.empty((n_src, math.prod(grad.shape[1:])), dtype=torch.float32, device=grad.device)
+    return d, d.reshape((n_src,) + tuple(grad.shape[1:]))
+
+
+@torch.library.impl("mtmc_mpn::scatter_add_backward", "CUDA")
+def _scatter_add_backward(grad, index, n_src):
+    g2, idx, _ = _scatter_backward_args("scatter_add_backward", grad, index, n_src)
+    d, res = _scatter_backward_out(grad, n_src)
+    _call.run(grad.device, _lib.load().mtmc_scatter_add_backward, g2.data_ptr(), idx.data_ptr(), n_src, g2.shape[1],
+              g2.shape[0], d.data_ptr(), _call.stream(grad.device))
+    return res
+
+
+@torch.library.impl("mtmc_mpn::scatter_mean_backward", "CUDA")
+def _scatter_mean_backward(grad, index, n_src):
+    g2, idx, _ = _scatter_backward_args("scatter_mean_backward", grad, index, n_src)
+    d, res = _scatter_backward_out(grad, n_src)
+    cnt = torch.empty((max(g2.shape[0], 1),), dtype=torch.int32, device=grad.device)
+    _call.run(grad.device, _lib.load().mtmc_scatter_mean_backward, g2.data_ptr(), idx.data_ptr(), n_src, g2.shape[1],
+              g2.shape[0], cnt.data_ptr(), d.data_ptr(), _call.stream(grad.device))
+    return res
+
+
+@torch.library.impl("mtmc_mpn::scatter_max_backward", "CUDA")
+def _scatter_max_backward(grad, arg, index, n_src):
+    g2, idx, a2 = _scatter_backward_args("scatter_max_backward", grad, index, n_src, arg)
+    d, res = _scatter_backward_out(grad, n_src)
+    _call.run(grad.device, _lib.load().mtmc_scatter_max_backward, g2.data_ptr(), a2.data_ptr(), idx.data_ptr(), n_src,
+              g2.shape[1], g2.shape[0], d.data_ptr(), _call.stream(grad.device))
+    return res
+
+
+def _scatter_backward_fake(grad, index, n_src):
+    return grad.new_empty((n_src,) + tuple(grad.shape[1:]), dtype=torch.float32)
+
+
+torch.library.register_fake("mtmc_mpn::scatter_add_backward")(_scatter_backward_fake)
+torch.library.register_fake("mtmc_mpn::scatter_mean_backward")(_scatter_backward_fake)
+
+
+@torch.library.register_fake("mtmc_mpn::scatter_max_backward")
+def _scatter_max_backward_fake(grad, arg, index, n_src):
+    return _scatter_backward_fake(grad, index, n_src)
+
+
+def _scatter_setup_context(ctx, inputs, output):
+    src, index, _dim, _dim_size = inputs
+    ctx.n_src, ctx.src_dtype = src.shape[0], src.dtype
+    if isinstance(output, tuple):                      # scatter_max: (values, argmax)
+        ctx.save_for_backward(output[1], index)
+    else:
+        ctx.save_for_backward(index)
+
+
+def _scatter_autograd(backward_op):
+    """The autograd formula of one forward op: the gradient of `src` in src's shape and dtype (half-precision src was
+    converted to float by the forward: one `.to` back), None for index, dim and dim_size.  The argmax carries no gradient."""
+    def backward(ctx, grad, _d_arg=None):
+        d = backward_op(grad, *ctx.saved_tensors, ctx.n_src)         # (grad, [arg,] index, n_src)
+        return d.to(ctx.src_dtype), None, None, None
+    return backward
+
+
+torch.library.register_autograd("mtmc_mpn::scatter_add", _scatter_autograd(torch.ops.mtmc_mpn.scatter_add_backward),
+                                setup_context=_scatter_setup_context)
+torch.library.register_autograd("mtmc_mpn::scatter_mean", _scatter_autograd(torch.ops.mtmc_mpn.scatter_mean_backward),
+                                setup_context=_scatter_setup_context)
+torch.library.register_autograd("mtmc_mpn::scatter_max", _scatter_autograd(torch.ops.mtmc_mpn.scatter_max_backward),
+                                setup_context=_scatter_setup_context)

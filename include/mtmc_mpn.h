@@ -277,6 +277,24 @@ int32_t mtmc_scatter_mean(const float* src, const int64_t* index, int64_t n_src,
 int32_t mtmc_scatter_max(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols,
                          int64_t dim_size, float* out, int64_t* arg_out, void* stream);
 
+/* The backward passes of the three float scatters with respect to src: grad_src[n_src, C] from grad_out[dim_size, C], r = index[e]:
+ *   add : grad_src[e, c] = grad_out[r, c]
+ *   mean: grad_src[e, c] = grad_out[r, c] / (float)max(count[r], 1), a true division; count[r] = the rows with index r inside
+ *         [0, dim_size), as the forward counts them, recounted into count_scratch (int32 [dim_size]: one memset, one pass
+ *         of integer atomics)
+ *   max : grad_src[e, c] = grad_out[r, c] if arg[r, c] == e, else 0; arg [dim_size, C] is what the forward wrote to arg_out
+ *         (the smallest e attaining the maximum; n_src where nobody wrote, so that gradient goes nowhere)
+ * A row whose index lies outside [0, dim_size) gets zeros: the forward skips it.  Every element of grad_src is written
+ * exactly once (no memset, no atomics on floats), so the result is the same bits on every run.  n_src == 0 or n_cols == 0:
+ * success, nothing enqueued.  Rows of 16 bytes per lane when C % 4 == 0 and grad_out, grad_src (and arg) are 16-byte
+ * aligned, one column per lane otherwise.  With dim_size == 0 grad_out, arg and count_scratch are not read and may be NULL. */
+int32_t mtmc_scatter_add_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols,
+                                  int64_t dim_size, float* grad_src, void* stream);
+int32_t mtmc_scatter_mean_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols,
+                                   int64_t dim_size, int32_t* count_scratch, float* grad_src, void* stream);
+int32_t mtmc_scatter_max_backward(const float* grad_out, const int64_t* arg, const int64_t* index, int64_t n_src,
+                                  int64_t n_cols, int64_t dim_size, float* grad_src, void* stream);
+
 /* y[rows, out] = relu(batchnorm_batchstats(x[rows,in] . W^T + b)) for one Linear+BN+ReLU group
  * (gamma == NULL: bare Linear).  stats_scratch: f64[2*out], y_raw aliases y. */
 int32_t mtmc_mlp_layer_forward(const mtmc_layer* layer, const float* x, int64_t x_row_stride, int64_t rows,
