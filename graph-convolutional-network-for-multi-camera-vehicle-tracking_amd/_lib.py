@@ -96,7 +96,8 @@ EXPORTS = ["mtmc_mpn_abi_version", "mtmc_mpn_last_error", "mtmc_mpn_workspace_by
            "mtmc_edge_loss_scratch_bytes", "mtmc_edge_loss_forward", "mtmc_edge_loss_backward",
            "mtmc_cluster_scores_workspace_bytes", "mtmc_cluster_scores", "mtmc_edge_prf",
            "mtmc_pool_chunk_rows", "mtmc_pool_tracklets_workspace_bytes", "mtmc_pool_tracklets", "mtmc_pool_tracklets_backward",
-           "mtmc_scatter_add_backward", "mtmc_scatter_mean_backward", "mtmc_scatter_max_backward"]
+           "mtmc_scatter_add_backward", "mtmc_scatter_mean_backward", "mtmc_scatter_max_backward",
+           "mtmc_graph_knn_workspace_bytes", "mtmc_build_graph_knn"]
 
 _lib = None
 
@@ -135,6 +136,11 @@ def load() -> C.CDLL:
     lib.mtmc_build_graph.restype = C.c_int32
     lib.mtmc_build_graph.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
         [C.c_int32, C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
+    lib.mtmc_graph_knn_workspace_bytes.restype = C.c_size_t
+    lib.mtmc_graph_knn_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.mtmc_build_graph_knn.restype = C.c_int32
+    lib.mtmc_build_graph_knn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
+        [C.c_int32, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_int64] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
     lib.mtmc_graph_backward_workspace_bytes.restype = C.c_size_t
     lib.mtmc_graph_backward_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.mtmc_build_graph_backward.restype = C.c_int32

@@ -14,8 +14,7 @@
 //     N >= 1921           gemm_bn_bf16x6_kernel<2,2,32> (128 x 128 tiles, six bf16 products per fp32 product)
 //     F > 6144            linear_generic_kernel (one thread per element, a chain of F fmaf) up to N = 2048; refused above that
 // tests/gram_cases.py names a case for each line and tests/test_gram_cases.py pins the splits.
-#include "api_error.h"
-#include "kernels.h"
+#include "graph_build.h"
 
 namespace mtmc {
 
@@ -60,16 +59,6 @@ __global__ __launch_bounds__(256) void gb_normalize_kernel(const float* x, int64
   }
 }
 
-struct EdgeBuildParams {
-  const int* in_list; const int* in_off;        // nodes of camera c: in_list[in_off[c] .. in_off[c+1])
-  const int* out_list; const int64_t* out_off;  // nodes NOT in camera c, ascending
-  const int64_t* block_off;                     // first edge of camera c's block; block_off[n_cams] = E
-  int n_cams; int64_t n_nodes; int64_t n_edges; int f;
-  const float* G; const float* row_sq; const float* row_sum; const int64_t* node_labels;
-  int64_t* edge_index;                          // [E][2] (row, col): its .T is the [2,E] view the callers pass on
-  float* edge_attr; float* edge_labels;
-};
-
 __global__ __launch_bounds__(256) void gb_edges_kernel(EdgeBuildParams p) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < p.n_edges; e += stride) {
@@ -82,12 +71,8 @@ __global__ __launch_bounds__(256) void gb_edges_kernel(EdgeBuildParams p) {
     const int col = p.out_list[p.out_off[c] + local % n_out];
     reinterpret_cast<longlong2*>(p.edge_index)[e] = make_longlong2(row, col);
     const float g = p.G[(int64_t)row * p.n_nodes + col];
-    const float nr = p.row_sq[row], nc = p.row_sq[col];
-    const float eps = 1e-6f;                     // F.pairwise_distance eps
-    const float d2 = nr + nc - 2.f * g + 2.f * eps * (p.row_sum[row] - p.row_sum[col]) + (float)p.f * eps * eps;
-    const float dist = sqrtf(fmaxf(d2, 0.f));
-    const float cosv = g / (fmaxf(sqrtf(nr), 1e-8f) * fmaxf(sqrtf(nc), 1e-8f));   // F.cosine_similarity eps
-    reinterpret_cast<float2*>(p.edge_attr)[e] = make_float2(dist, 1.f - cosv);
+    reinterpret_cast<float2*>(p.edge_attr)[e] =
+        gb_edge_attr(g, p.row_sq[row], p.row_sq[col], p.row_sum[row], p.row_sum[col], p.f);
     if (p.edge_labels) p.edge_labels[e] = p.node_labels[row] == p.node_labels[col] ? 1.f : 0.f;
   }
 }
@@ -99,13 +84,6 @@ __global__ __launch_bounds__(256) void gb_edges_kernel(EdgeBuildParams p) {
 //     dXn     = gX + S . Xn + diag(delta) . Xn + 1e-6 kappa 1^T
 //     dX[:,k] = (dXn[:,k] - Xn[:,k] <Xn[:,k], dXn[:,k]>) / n_k                        (l2norm; dX = dXn otherwise)
 // The eps clamps of the forward (1e-8 on rho, 1e-12 on n_k) count as constants where they are active, as in autograd.
-
-template <class T>
-__device__ __forceinline__ int gb_segment_of(const T* off, int n_seg, int64_t v) {   // off[s] <= v < off[s + 1]
-  int lo = 0, hi = n_seg;
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)off[mid] <= v) lo = mid; else hi = mid; }
-  return lo;
-}
 
 // node -> (camera block, position inside it): the inverse of in_list
 __global__ __launch_bounds__(256) void gb_bwd_nodemap_kernel(const int* in_list, const int* in_off, int n_cams, int64_t n,
@@ -390,13 +368,10 @@ __global__ __launch_bounds__(256) void gb_bwd_normalize_kernel(const float* x, i
   }
 }
 
-}  // namespace mtmc
+static inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
-namespace {
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-struct GLayout { size_t colsq, row_sq, row_sum, G, zeros, slab, total; };
-GLayout graph_layout(int64_t n, int f) {
-  GLayout l;
+GraphLayout graph_layout(int64_t n, int f) {
+  GraphLayout l;
   size_t off = 0;
   auto take = [&](size_t b) { size_t o = off; off = up256(off + b); return o; };
   l.colsq = take((size_t)f * sizeof(double));
@@ -405,11 +380,60 @@ GLayout graph_layout(int64_t n, int f) {
   l.G = take((size_t)n * n * sizeof(float));
   l.zeros = take((size_t)n * sizeof(float));
   int sk = 1;
-  mtmc::gemm_plan(n, f, (int)n, &sk);
+  gemm_plan(n, f, (int)n, &sk);
   l.slab = take(sk > 1 ? (size_t)sk * n * n * sizeof(float) : 0);
   l.total = off;
   return l;
 }
+
+int graph_check_args(const char* entry, const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim,
+                     const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
+                     const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
+                     const float* x_out, const int64_t* edge_index_out, const float* edge_attr_out,
+                     const float* edge_labels_out, const void* workspace) {
+  using mtmc_api::fail;
+  if (!feats || !x_out) return fail(MTMC_E_ARG, "%s: NULL feats or x_out", entry);
+  if (n_nodes < 1 || n_nodes > 46000 || feat_dim % 32 != 0 || feat_dim < 32 || n_cams < 1)
+    return fail(MTMC_E_ARG, "%s: n_nodes must be in [1, 46000], feat_dim a multiple of 32 and n_cams >= 1", entry);
+  if (n_edges > 0 && (!in_list || !in_off || !out_list || !out_off || !block_off || !edge_index_out || !edge_attr_out))
+    return fail(MTMC_E_ARG, "%s: NULL camera table or edge output with n_edges > 0", entry);
+  if (edge_labels_out && !node_labels) return fail(MTMC_E_ARG, "%s: edge_labels_out needs node_labels", entry);
+  if (((uintptr_t)feats & 15) || (feat_row_stride & 3) || ((uintptr_t)x_out & 15) || ((uintptr_t)workspace & 255))
+    return fail(MTMC_E_ARG, "%s: feats and x_out must be 16-byte and the workspace 256-byte aligned, the row stride a "
+                            "multiple of 4", entry);
+  return MTMC_OK;
+}
+
+int graph_normalize_gram(const char* entry, const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim,
+                         int32_t l2norm, float* x_out, char* ws, const GraphLayout& l, bool gram, hipStream_t s) {
+  using mtmc_api::fail;
+  double* colsq = reinterpret_cast<double*>(ws + l.colsq);
+  float* row_sq = reinterpret_cast<float*>(ws + l.row_sq);
+  float* row_sum = reinterpret_cast<float*>(ws + l.row_sum);
+  float* zeros = reinterpret_cast<float*>(ws + l.zeros);
+  if (hipMemsetAsync(colsq, 0, (size_t)feat_dim * sizeof(double), s) != hipSuccess ||
+      hipMemsetAsync(zeros, 0, (size_t)n_nodes * sizeof(float), s) != hipSuccess)
+    return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
+  if (l2norm)
+    hipLaunchKernelGGL(gb_colnorm_kernel, dim3((feat_dim + 63) / 64, (unsigned)((n_nodes + 63) / 64)), dim3(256), 0, s,
+                       feats, feat_row_stride, n_nodes, feat_dim, colsq);
+  hipLaunchKernelGGL(gb_normalize_kernel, dim3((unsigned)n_nodes), dim3(256), 0, s, feats, feat_row_stride, n_nodes,
+                     feat_dim, colsq, l2norm, x_out, row_sq, row_sum);
+  if (gram) {
+    GemmParams g = plain_gemm(x_out, feat_dim, x_out, zeros, reinterpret_cast<float*>(ws + l.G), n_nodes, n_nodes, feat_dim,
+                              (int)n_nodes);
+    int sk = 1;
+    gemm_plan(n_nodes, feat_dim, (int)n_nodes, &sk);
+    if (sk > 1 && l.slab != l.total) g.slab = reinterpret_cast<float*>(ws + l.slab);
+    if (launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "%s: the Gram-matrix GEMM refused its shape", entry);
+  }
+  return MTMC_OK;
+}
+
+}  // namespace mtmc
+
+namespace {
+using mtmc::up256;
 struct GBLayout { size_t colsq, dot, rho, delta, kappa, node_cam, node_loc, S, total; int npad; };
 GBLayout graph_bwd_layout(int64_t n, int f) {
   GBLayout l;
@@ -436,7 +460,7 @@ using mtmc_api::launched;
 
 size_t mtmc_graph_workspace_bytes(int64_t n_nodes, int32_t feat_dim) {
   if (n_nodes < 1 || n_nodes > 46000 || feat_dim < 32) return 0;
-  return graph_layout(n_nodes, feat_dim).total;
+  return mtmc::graph_layout(n_nodes, feat_dim).total;
 }
 
 int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
@@ -444,44 +468,24 @@ int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_
                          const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
                          float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                          void* workspace, size_t workspace_bytes, void* stream) {
-  if (!feats || !x_out) return fail(MTMC_E_ARG, "build_graph: NULL feats or x_out");
-  if (n_nodes < 1 || n_nodes > 46000 || feat_dim % 32 != 0 || feat_dim < 32 || n_cams < 1)
-    return fail(MTMC_E_ARG, "build_graph: n_nodes must be in [1, 46000], feat_dim a multiple of 32 and n_cams >= 1");
-  if (n_edges > 0 && (!in_list || !in_off || !out_list || !out_off || !block_off || !edge_index_out || !edge_attr_out))
-    return fail(MTMC_E_ARG, "build_graph: NULL camera table or edge output with n_edges > 0");
-  if (edge_labels_out && !node_labels) return fail(MTMC_E_ARG, "build_graph: edge_labels_out needs node_labels");
-  if (((uintptr_t)feats & 15) || (feat_row_stride & 3) || ((uintptr_t)x_out & 15) || ((uintptr_t)workspace & 255))
-    return fail(MTMC_E_ARG, "build_graph: feats and x_out must be 16-byte and the workspace 256-byte aligned, the row stride a "
-                            "multiple of 4");
-  const GLayout l = graph_layout(n_nodes, feat_dim);
+  int rc = mtmc::graph_check_args("build_graph", feats, feat_row_stride, n_nodes, feat_dim, in_list, in_off, out_list, out_off,
+                                  block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out,
+                                  edge_labels_out, workspace);
+  if (rc != MTMC_OK) return rc;
+  const mtmc::GraphLayout l = mtmc::graph_layout(n_nodes, feat_dim);
   if (!workspace || workspace_bytes < l.total)
     return fail(MTMC_E_WORKSPACE, "build_graph: workspace has %zu bytes, %zu needed (mtmc_graph_workspace_bytes)",
                 workspace ? workspace_bytes : (size_t)0, l.total);
   char* ws = static_cast<char*>(workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  double* colsq = reinterpret_cast<double*>(ws + l.colsq);
-  float* row_sq = reinterpret_cast<float*>(ws + l.row_sq);
-  float* row_sum = reinterpret_cast<float*>(ws + l.row_sum);
-  float* G = reinterpret_cast<float*>(ws + l.G);
-  float* zeros = reinterpret_cast<float*>(ws + l.zeros);
-  if (hipMemsetAsync(colsq, 0, (size_t)feat_dim * sizeof(double), s) != hipSuccess ||
-      hipMemsetAsync(zeros, 0, (size_t)n_nodes * sizeof(float), s) != hipSuccess)
-    return fail(MTMC_E_HIP, "build_graph: hipMemsetAsync failed");
-  if (l2norm)
-    hipLaunchKernelGGL(mtmc::gb_colnorm_kernel, dim3((feat_dim + 63) / 64, (unsigned)((n_nodes + 63) / 64)), dim3(256), 0, s,
-                       feats, feat_row_stride, n_nodes, feat_dim, colsq);
-  hipLaunchKernelGGL(mtmc::gb_normalize_kernel, dim3((unsigned)n_nodes), dim3(256), 0, s, feats, feat_row_stride, n_nodes,
-                     feat_dim, colsq, l2norm, x_out, row_sq, row_sum);
+  rc = mtmc::graph_normalize_gram("build_graph", feats, feat_row_stride, n_nodes, feat_dim, l2norm, x_out, ws, l, n_edges > 0, s);
+  if (rc != MTMC_OK) return rc;
   if (n_edges > 0) {
-    mtmc::GemmParams g = mtmc::plain_gemm(x_out, feat_dim, x_out, zeros, G, n_nodes, n_nodes, feat_dim, (int)n_nodes);
-    int sk = 1;
-    mtmc::gemm_plan(n_nodes, feat_dim, (int)n_nodes, &sk);
-    if (sk > 1 && l.slab != l.total) g.slab = reinterpret_cast<float*>(ws + l.slab);
-    if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "build_graph: the Gram-matrix GEMM refused its shape");
     mtmc::EdgeBuildParams p;
     p.in_list = in_list; p.in_off = in_off; p.out_list = out_list; p.out_off = out_off; p.block_off = block_off;
     p.n_cams = n_cams; p.n_nodes = n_nodes; p.n_edges = n_edges; p.f = feat_dim;
-    p.G = G; p.row_sq = row_sq; p.row_sum = row_sum; p.node_labels = node_labels;
+    p.G = reinterpret_cast<float*>(ws + l.G); p.row_sq = reinterpret_cast<float*>(ws + l.row_sq);
+    p.row_sum = reinterpret_cast<float*>(ws + l.row_sum); p.node_labels = node_labels;
     p.edge_index = edge_index_out; p.edge_attr = edge_attr_out; p.edge_labels = edge_labels_out;
     hipLaunchKernelGGL(mtmc::gb_edges_kernel, dim3(mtmc::blocks_for(n_edges, 256, 4096)), dim3(256), 0, s, p);
   }

@@ -1,0 +1,253 @@
+// build_graph(k=...): the cross-camera list of graph_build.hip thinned to a symmetric k-nearest list (the
+// reference's authors left the same idea as a commented-out block, inference.py:415-441).
+//     key(i, j)  = the cosine distance edge_attr[e][1] that the dense builder writes for the directed edge (i, j)
+//     top_i      = the first min(k, n_out(i)) cross-camera nodes j of row i in the order (key, j) ascending
+//     keep (i,j) iff j in top_i or i in top_j            -- a union: symmetric whether or not G[i][j] == G[j][i] bitwise
+// Kept edges appear in the dense list's order with the dense list's bits (gb_edge_attr, graph_build.h) and carry their dense
+// position in edge_pos.  Only G and an N x N BIT matrix are N^2-sized; the dense edge arrays are never formed.
+//     gk_select_kernel   one workgroup per row: radix select of the k-th (key, j), then bit (i, j) and bit (j, i) per pick
+//     gk_count_kernel    one workgroup per row: kept columns of its out_list
+//     gk_scan_kernel     exclusive int64 scan of the counts in in_list position order (= the dense list's row order)
+//     gk_fill_kernel     one workgroup per row: ordered compaction of its kept columns at its row offset
+// No atomics on any output cursor and the ORs commute, so two calls on the same G give the same bits.
+#include "graph_build.h"
+
+namespace mtmc {
+
+struct KnnParams {
+  EdgeBuildParams e;          // camera tables, G, row norms, labels; the edge outputs hold `capacity` edges
+  int k; int64_t capacity;
+  unsigned* bits;             // bit i * N + j: edge (i, j) is kept
+  int64_t* row_off;           // [N] by in_list position: kept edges of the row, then (scanned in place) its first output slot
+  int64_t* edge_pos;          // [capacity]: dense position of every kept edge
+};
+
+struct KnnRow { int i; const int* ol; int n_out; int64_t e0; };   // node, its camera's out_list, its first dense edge
+
+// row of in_list position q; false where in_list names no node (such a row has no edges in any of the kernels)
+__device__ __forceinline__ bool knn_row(const EdgeBuildParams& p, int64_t q, KnnRow* r) {
+  const int c = gb_segment_of(p.in_off, p.n_cams, q);
+  const int64_t n_out = p.out_off[c + 1] - p.out_off[c];
+  r->i = p.in_list[q];
+  r->ol = p.out_list + p.out_off[c];
+  r->n_out = (int)n_out;
+  r->e0 = p.block_off[c] + (q - p.in_off[c]) * n_out;
+  return r->i >= 0 && r->i < p.n_nodes;
+}
+
+// order-preserving uint32 image of key(i, j); false where j is no node
+__device__ __forceinline__ bool knn_key(const EdgeBuildParams& p, int i, int j, uint32_t* u) {
+  if (j < 0 || j >= p.n_nodes) return false;
+  const float key = gb_edge_attr(p.G[(int64_t)i * p.n_nodes + j], p.row_sq[i], p.row_sq[j], p.row_sum[i], p.row_sum[j], p.f).y;
+  const uint32_t b = __float_as_uint(key);
+  *u = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+  return true;
+}
+
+__device__ __forceinline__ void knn_set(unsigned* bits, int64_t n, int i, int j) {
+  const int64_t b = (int64_t)i * n + j;
+  atomicOr(bits + (b >> 5), 1u << (b & 31));
+}
+__device__ __forceinline__ bool knn_get(const unsigned* bits, int64_t n, int i, int j) {
+  const int64_t b = (int64_t)i * n + j;
+  return (bits[b >> 5] >> (b & 31)) & 1u;
+}
+
+// exclusive prefix of v over the 256 threads of the workgroup in thread order, *total = the sum; smem: 4 ints.
+// Every thread must call.
+__device__ __forceinline__ int block_excl_scan(int v, int* smem, int* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
+  __syncthreads();                                // the previous call's readers are done with smem
+  if (lane == 63) smem[w] = inc;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int x = 0; x < 4; ++x) { const int s = smem[x]; if (x < w) base += s; tot += s; }
+  *total = tot;
+  return base + inc - v;
+}
+
+// Radix select over the key images, most significant byte first: after pass b, `prefix` holds the top 8 (b + 1) bits of the
+// k-th smallest image and `want` its rank among the keys that share them.  The row is read again on every pass (184 KB at
+// the most: it stays in L2).  After four passes `want` of the keys equal to the k-th are admitted with every smaller one;
+// out_list ascends, so a prefix count in sweep order admits the lowest columns first.
+__global__ __launch_bounds__(256) void gk_select_kernel(KnnParams p) {
+  __shared__ int hist[256];
+  __shared__ int scan_s[4];
+  __shared__ int pick[2];
+  KnnRow r;
+  if (!knn_row(p.e, blockIdx.x, &r)) return;
+  uint32_t prefix = 0, mask = 0;
+  int want = p.k;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (int t = threadIdx.x; t < r.n_out; t += 256) {
+      uint32_t u;
+      if (knn_key(p.e, r.i, r.ol[t], &u) && (u & mask) == prefix) atomicAdd(&hist[(u >> shift) & 255], 1);
+    }
+    __syncthreads();
+    const int h = hist[threadIdx.x];
+    int total;
+    const int excl = block_excl_scan(h, scan_s, &total);
+    if (pass == 0) {                              // total = the row's candidates
+      if (total == 0) return;
+      want = min(want, total);
+    }
+    if (excl < want && want <= excl + h) { pick[0] = threadIdx.x; pick[1] = want - excl; }   // one bin holds the k-th
+    __syncthreads();
+    prefix |= (uint32_t)pick[0] << shift;
+    mask |= 0xFFu << shift;
+    want = pick[1];
+    __syncthreads();
+  }
+  int seen = 0;                                   // keys equal to the k-th in earlier sweeps
+  for (int t0 = 0; t0 < r.n_out; t0 += 256) {
+    const int t = t0 + threadIdx.x;
+    uint32_t u = 0;
+    int j = -1;
+    bool ok = false;
+    if (t < r.n_out) { j = r.ol[t]; ok = knn_key(p.e, r.i, j, &u); }
+    const bool eq = ok && u == prefix;
+    int total;
+    const int rank = block_excl_scan(eq ? 1 : 0, scan_s, &total);
+    if (ok && (u < prefix || (eq && seen + rank < want))) {
+      knn_set(p.bits, p.e.n_nodes, r.i, j);
+      knn_set(p.bits, p.e.n_nodes, j, r.i);
+    }
+    seen += total;
+  }
+}
+
+__global__ __launch_bounds__(256) void gk_count_kernel(KnnParams p) {
+  __shared__ int scan_s[4];
+  KnnRow r;
+  int c = 0;
+  if (knn_row(p.e, blockIdx.x, &r))
+    for (int t = threadIdx.x; t < r.n_out; t += 256) {
+      const int j = r.ol[t];
+      if (j >= 0 && j < p.e.n_nodes && knn_get(p.bits, p.e.n_nodes, r.i, j)) ++c;
+    }
+  int total;
+  block_excl_scan(c, scan_s, &total);
+  if (threadIdx.x == 0) p.row_off[blockIdx.x] = total;
+}
+
+// one workgroup: counts -> first output slot of every row, the total to n_kept (a sweep's counts fit an int: 256 x 46000)
+__global__ __launch_bounds__(256) void gk_scan_kernel(int64_t* row_off, int64_t n, int64_t* n_kept) {
+  __shared__ int scan_s[4];
+  int64_t carry = 0;
+  for (int64_t q0 = 0; q0 < n; q0 += 256) {
+    const int64_t q = q0 + threadIdx.x;
+    const int v = q < n ? (int)row_off[q] : 0;
+    int total;
+    const int excl = block_excl_scan(v, scan_s, &total);
+    if (q < n) row_off[q] = carry + excl;
+    carry += total;
+  }
+  if (threadIdx.x == 0) *n_kept = carry;
+}
+
+// Slots at or beyond `capacity` are not written: a caller whose buffers are too short reads n_kept > capacity and has
+// the first `capacity` edges.
+__global__ __launch_bounds__(256) void gk_fill_kernel(KnnParams p) {
+  __shared__ int scan_s[4];
+  KnnRow r;
+  if (!knn_row(p.e, blockIdx.x, &r)) return;
+  int64_t at = p.row_off[blockIdx.x];
+  for (int t0 = 0; t0 < r.n_out; t0 += 256) {
+    const int t = t0 + threadIdx.x;
+    int j = -1;
+    bool kept = false;
+    if (t < r.n_out) { j = r.ol[t]; kept = j >= 0 && j < p.e.n_nodes && knn_get(p.bits, p.e.n_nodes, r.i, j); }
+    int total;
+    const int64_t pos = at + block_excl_scan(kept ? 1 : 0, scan_s, &total);
+    if (kept && pos < p.capacity) {
+      reinterpret_cast<longlong2*>(p.e.edge_index)[pos] = make_longlong2(r.i, j);
+      reinterpret_cast<float2*>(p.e.edge_attr)[pos] =
+          gb_edge_attr(p.e.G[(int64_t)r.i * p.e.n_nodes + j], p.e.row_sq[r.i], p.e.row_sq[j], p.e.row_sum[r.i], p.e.row_sum[j], p.e.f);
+      if (p.e.edge_labels) p.e.edge_labels[pos] = p.e.node_labels[r.i] == p.e.node_labels[j] ? 1.f : 0.f;
+      p.edge_pos[pos] = r.e0 + t;
+    }
+    at += total;
+  }
+}
+
+}  // namespace mtmc
+
+namespace {
+struct KnnLayout { mtmc::GraphLayout g; size_t bits, bits_bytes, row_off, total; };
+KnnLayout knn_layout(int64_t n, int f) {
+  KnnLayout l;
+  l.g = mtmc::graph_layout(n, f);
+  auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
+  l.bits = l.g.total;
+  l.bits_bytes = ((size_t)n * n + 31) / 32 * sizeof(unsigned);      // N^2 / 8 bytes, rounded up to a word
+  l.row_off = up256(l.bits + l.bits_bytes);
+  l.total = up256(l.row_off + (size_t)n * sizeof(int64_t));
+  return l;
+}
+}  // namespace
+
+extern "C" {
+
+using mtmc_api::fail;
+using mtmc_api::launched;
+
+size_t mtmc_graph_knn_workspace_bytes(int64_t n_nodes, int32_t feat_dim) {
+  if (n_nodes < 1 || n_nodes > 46000 || feat_dim < 32) return 0;
+  return knn_layout(n_nodes, feat_dim).total;
+}
+
+int32_t mtmc_build_graph_knn(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
+                             const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
+                             const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
+                             float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                             int32_t k, int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = mtmc::graph_check_args("build_graph_knn", feats, feat_row_stride, n_nodes, feat_dim, in_list, in_off, out_list,
+                                  out_off, block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out,
+                                  edge_labels_out, workspace);
+  if (rc != MTMC_OK) return rc;
+  if (k < 1 || edge_capacity < 0) return fail(MTMC_E_ARG, "build_graph_knn: k must be >= 1 and edge_capacity >= 0");
+  if (!n_kept_out || (n_edges > 0 && !edge_pos_out))
+    return fail(MTMC_E_ARG, "build_graph_knn: NULL n_kept_out, or NULL edge_pos_out with n_edges > 0");
+  if (((uintptr_t)edge_index_out & 15) || ((uintptr_t)edge_attr_out & 7))
+    return fail(MTMC_E_ARG, "build_graph_knn: edge_index_out must be 16-byte and edge_attr_out 8-byte aligned");
+  const KnnLayout l = knn_layout(n_nodes, feat_dim);
+  if (!workspace || workspace_bytes < l.total)
+    return fail(MTMC_E_WORKSPACE, "build_graph_knn: workspace has %zu bytes, %zu needed (mtmc_graph_knn_workspace_bytes)",
+                workspace ? workspace_bytes : (size_t)0, l.total);
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  rc = mtmc::graph_normalize_gram("build_graph_knn", feats, feat_row_stride, n_nodes, feat_dim, l2norm, x_out, ws, l.g,
+                                  n_edges > 0, s);
+  if (rc != MTMC_OK) return rc;
+  if (n_edges <= 0) {
+    if (hipMemsetAsync(n_kept_out, 0, sizeof(int64_t), s) != hipSuccess)
+      return fail(MTMC_E_HIP, "build_graph_knn: hipMemsetAsync failed");
+    return launched("build_graph_knn");
+  }
+  mtmc::KnnParams p;
+  p.e.in_list = in_list; p.e.in_off = in_off; p.e.out_list = out_list; p.e.out_off = out_off; p.e.block_off = block_off;
+  p.e.n_cams = n_cams; p.e.n_nodes = n_nodes; p.e.n_edges = n_edges; p.e.f = feat_dim;
+  p.e.G = reinterpret_cast<float*>(ws + l.g.G); p.e.row_sq = reinterpret_cast<float*>(ws + l.g.row_sq);
+  p.e.row_sum = reinterpret_cast<float*>(ws + l.g.row_sum); p.e.node_labels = node_labels;
+  p.e.edge_index = edge_index_out; p.e.edge_attr = edge_attr_out; p.e.edge_labels = edge_labels_out;
+  p.k = k; p.capacity = edge_capacity;
+  p.bits = reinterpret_cast<unsigned*>(ws + l.bits); p.row_off = reinterpret_cast<int64_t*>(ws + l.row_off);
+  p.edge_pos = edge_pos_out;
+  if (hipMemsetAsync(p.bits, 0, l.bits_bytes, s) != hipSuccess) return fail(MTMC_E_HIP, "build_graph_knn: hipMemsetAsync failed");
+  const dim3 rows((unsigned)n_nodes), wg(256);
+  hipLaunchKernelGGL(mtmc::gk_select_kernel, rows, wg, 0, s, p);
+  hipLaunchKernelGGL(mtmc::gk_count_kernel, rows, wg, 0, s, p);
+  hipLaunchKernelGGL(mtmc::gk_scan_kernel, dim3(1), wg, 0, s, p.row_off, n_nodes, n_kept_out);
+  hipLaunchKernelGGL(mtmc::gk_fill_kernel, rows, wg, 0, s, p);
+  return launched("build_graph_knn");
+}
+
+}  // extern "C"

@@ -350,6 +350,28 @@ int32_t mtmc_build_graph(const float* feats, int64_t feat_row_stride, int64_t n_
                          float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same construction thinned to a symmetric k-nearest list (the reference leaves the idea as a commented-out block
+ * between its edge list and its attributes, inference.py:407-456): with key(i, j) = the cosine distance edge_attr[e][1]
+ * that mtmc_build_graph writes for the directed edge (i, j), row i ranks its cross-camera nodes by (key, j) ascending,
+ * top_i = the first min(k, n_out(i)) of them, and edge (i, j) is kept iff j is in top_i or i is in top_j -- a union, so
+ * the list is symmetric by construction.  The kept edges come in the dense list's order and with the dense call's bits;
+ * edge_pos_out [edge_capacity] int64 receives each kept edge's index in the dense list.  Arguments as mtmc_build_graph
+ * (n_edges = the DENSE list's length, block_off[n_cams]), plus k >= 1, edge_capacity = the number of edges the four
+ * edge outputs can hold (min(n_edges, 2 k n_nodes) always suffices) and n_kept_out = one int64 in device memory that
+ * receives the number of kept edges E_k.  Status: n_kept_out[0] > edge_capacity reports a capacity error -- the outputs
+ * then hold the first edge_capacity kept edges and nothing at or past edge_capacity was written.  Only the Gram matrix and
+ * a bit matrix of n_nodes^2 / 8 bytes are N^2-sized: no dense-sized edge array is formed.  Nothing synchronises; the
+ * result is bitwise repeatable for a given Gram matrix.  MTMC_E_ARG / MTMC_E_WORKSPACE as mtmc_build_graph, and for
+ * k < 1, edge_capacity < 0 or a NULL n_kept_out.  The workspace query returns 0 outside 1 <= n_nodes <= 46000 or for
+ * feat_dim < 32, and at least mtmc_graph_workspace_bytes otherwise. */
+size_t mtmc_graph_knn_workspace_bytes(int64_t n_nodes, int32_t feat_dim);
+int32_t mtmc_build_graph_knn(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
+                             const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
+                             const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
+                             float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                             int32_t k, int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the construction to the node features (the reference's CNN_MODEL.finetune chain, train.py:304-342:
  * autograd through F.normalize(dim=0), F.pairwise_distance and 1 - F.cosine_similarity along the edge list).
  * feats, l2norm and the five camera tables as in the forward call (in_list per camera and out_list per camera
