@@ -94,6 +94,7 @@ EXPORTS = ["mtmc_mpn_abi_version", "mtmc_mpn_last_error", "mtmc_mpn_workspace_by
            "mtmc_linear_presplit_raw", "mtmc_linear_staged_raw", "mtmc_linear_few_raw", "mtmc_mpn_weight_cache_bytes",
            "mtmc_graph_backward_workspace_bytes", "mtmc_build_graph_backward",
            "mtmc_edge_loss_scratch_bytes", "mtmc_edge_loss_forward", "mtmc_edge_loss_backward",
+           "mtmc_edge_focal_forward", "mtmc_edge_focal_backward",
            "mtmc_cluster_scores_workspace_bytes", "mtmc_cluster_scores", "mtmc_edge_prf",
            "mtmc_pool_chunk_rows", "mtmc_pool_tracklets_workspace_bytes", "mtmc_pool_tracklets", "mtmc_pool_tracklets_backward",
            "mtmc_scatter_add_backward", "mtmc_scatter_mean_backward", "mtmc_scatter_max_backward",
@@ -186,6 +187,10 @@ def load() -> C.CDLL:
     lib.mtmc_edge_loss_backward.restype = C.c_int32
     lib.mtmc_edge_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+    lib.mtmc_edge_focal_forward.restype = C.c_int32              # mtmc_edge_loss_forward's arguments, then gamma and per_row
+    lib.mtmc_edge_focal_forward.argtypes = lib.mtmc_edge_loss_forward.argtypes[:-1] + [C.c_float, C.c_void_p, C.c_void_p]
+    lib.mtmc_edge_focal_backward.restype = C.c_int32             # ... then gamma and grad_per_row
+    lib.mtmc_edge_focal_backward.argtypes = lib.mtmc_edge_loss_backward.argtypes[:-1] + [C.c_float, C.c_int32, C.c_void_p]
     lib.mtmc_cluster_scores_workspace_bytes.restype = C.c_size_t
     lib.mtmc_cluster_scores_workspace_bytes.argtypes = [C.c_int64]
     lib.mtmc_cluster_scores.restype = C.c_int32

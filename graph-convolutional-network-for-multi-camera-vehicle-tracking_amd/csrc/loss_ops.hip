@@ -8,6 +8,8 @@
 #include "api_error.h"
 #include "kernels.h"
 
+#include <float.h>
+
 namespace mtmc {
 
 __device__ __forceinline__ void ce_row(const float* x, int C, float (&p)[MTMC_MAX_CLASSES], float& lse) {
@@ -221,6 +223,98 @@ __global__ __launch_bounds__(256) void el_backward_kernel(const float* logits, c
   }
 }
 
+// ---- mtmc_edge_focal_*: the same pass with the focal row loss f = q^gamma * l (include/mtmc_mpn.h) ---------------------
+// d f / d z = -q^gamma * (gamma * p * l + q): q^(gamma - 1) never appears, so q = 0 (a margin past ~ +104, where e is 0)
+// gives f = 0 and d f / d z = 0 for every gamma > 0, and nothing divides by q.  powf on the q of el_row, which has no
+// cancellation on either side of z = 0.
+__device__ __forceinline__ void el_focal_row(float z, float gamma, float& f, float& df, float& p) {
+  float l, q;
+  el_row(z, l, p, q);
+  const float m = powf(q, gamma);
+  f = m * l;
+  df = -m * (gamma * p * l + q);
+}
+
+// as el_forward_kernel, with sum f in the L0 / L1 words; same scratch, same finalize
+template <int C>
+__global__ __launch_bounds__(256) void el_focal_forward_kernel(const float* logits, const int64_t* labels, int64_t n,
+                                                               int n_steps, float gamma, double* scratch) {
+  __shared__ double red[4 * 4];
+  __shared__ unsigned int cnt[4];
+  const int64_t nthreads = (int64_t)gridDim.x * 256;
+  for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
+    const float* x = logits + (int64_t)s * n * C;
+    double acc[4] = {0, 0, 0, 0};
+    unsigned int c[4] = {0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
+      const int64_t lab = labels[i];
+      if (lab != 0 && lab != 1) continue;
+      const bool y = lab == 1;
+      bool pred;
+      const float z = el_margin<C>(x, i, y, pred);
+      float f, df, p;
+      el_focal_row(z, gamma, f, df, p);
+      if (y) { acc[1] += f; acc[3] += p; } else { acc[0] += f; acc[2] += p; }
+      ++c[confusion_slot(y, pred)];
+    }
+    double* rep = scratch + (int64_t)s * kStatRep * kElStride;
+    block_atomic_add<4>(acc, rep, kElStride, red);
+    block_count_add<4>(c, reinterpret_cast<unsigned long long*>(rep + (blockIdx.x % kStatRep) * kElStride + 4), cnt);
+  }
+}
+
+// per_row [n_steps][n] = w[y] * f, 0 on skipped rows; after the finalize, whose record holds the (possibly balanced) weights
+template <int C>
+__global__ __launch_bounds__(256) void el_focal_rows_kernel(const float* logits, const int64_t* labels, int64_t n, int n_steps,
+                                                            float gamma, const double* record, float* per_row) {
+  const float w0 = (float)record[0], w1 = (float)record[1];
+  const int64_t nthreads = (int64_t)gridDim.x * 256;
+  for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
+    const float* x = logits + (int64_t)s * n * C;
+    float* out = per_row + (int64_t)s * n;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
+      const int64_t lab = labels[i];
+      float v = 0.f;
+      if (lab == 0 || lab == 1) {
+        const bool y = lab == 1;
+        bool pred;
+        float f, df, p;
+        el_focal_row(el_margin<C>(x, i, y, pred), gamma, f, df, p);
+        v = (y ? w1 : w0) * f;
+      }
+      out[i] = v;
+    }
+  }
+}
+
+// PER_ROW: grad [n_steps][n] is the upstream gradient of per_row (no division by D); otherwise grad[0] as el_backward_kernel
+template <int C, bool PER_ROW>
+__global__ __launch_bounds__(256) void el_focal_backward_kernel(const float* logits, const int64_t* labels, int64_t n,
+                                                                int n_steps, const float* grad, const double* record,
+                                                                float gamma, float* d_logits) {
+  const double gd = PER_ROW ? 1.0 : (double)grad[0] / record[2];
+  const float g0 = (float)(gd * record[0]), g1 = (float)(gd * record[1]);
+  const int64_t nthreads = (int64_t)gridDim.x * 256;
+  for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
+    const float* x = logits + (int64_t)s * n * C;
+    float* d = d_logits + (int64_t)s * n * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
+      const int64_t lab = labels[i];
+      float dz = 0.f;
+      const bool y = lab == 1;
+      if (lab == 0 || lab == 1) {
+        bool pred;
+        float f, df, p;
+        el_focal_row(el_margin<C>(x, i, y, pred), gamma, f, df, p);
+        dz = (y ? g1 : g0) * df;
+        if (PER_ROW) dz *= grad[(int64_t)s * n + i];
+      }
+      if (C == 2) reinterpret_cast<float2*>(d)[i] = y ? make_float2(-dz, dz) : make_float2(dz, -dz);
+      else d[i] = y ? dz : -dz;
+    }
+  }
+}
+
 // x: row blocks up to `cap` workgroups in all (the forward ends in eight 64-bit atomics per workgroup: 512, as kCeBlocksFwd)
 static inline dim3 el_grid(int64_t n, int n_steps, int cap) {
   const int gy = n_steps < 1024 ? n_steps : 1024;
@@ -325,22 +419,49 @@ size_t mtmc_edge_loss_scratch_bytes(int32_t n_steps) {
   return n_steps < 1 ? 0 : (size_t)n_steps * mtmc::kStatRep * mtmc::kElStride * sizeof(double);
 }
 
+// the argument checks the plain and the focal entry points share; `entry` starts the error text
+static int el_check_forward(const char* entry, const float* logits, const int64_t* labels, int64_t n, int32_t n_classes,
+                            int32_t n_steps, int32_t weight_mode, const float* weight, const void* scratch,
+                            size_t scratch_bytes, const double* record, const float* out, const int64_t* confusion) {
+  if (!logits || !labels || !scratch || !record || !out || !confusion)
+    return fail(MTMC_E_ARG, "%s: NULL logits, labels, scratch, record, out or confusion", entry);
+  if (n < 0 || n_steps < 1 || (n_classes != 1 && n_classes != 2))
+    return fail(MTMC_E_ARG, "%s: n must be >= 0, n_steps >= 1 and n_classes 1 or 2", entry);
+  if (weight_mode < MTMC_EDGE_W_ONE || weight_mode > MTMC_EDGE_W_BALANCED || (weight_mode == MTMC_EDGE_W_GIVEN && !weight))
+    return fail(MTMC_E_ARG, "%s: weight_mode must be MTMC_EDGE_W_ONE, _GIVEN (with weight) or _BALANCED", entry);
+  if ((n_classes == 2 && ((uintptr_t)logits & 7)) || ((uintptr_t)scratch & 7))
+    return fail(MTMC_E_ARG, "%s: [n, 2] logits and scratch must be 8-byte aligned", entry);
+  const size_t need = mtmc_edge_loss_scratch_bytes(n_steps);
+  if (scratch_bytes < need)
+    return fail(MTMC_E_ARG, "%s: scratch has %zu bytes, %zu needed (mtmc_edge_loss_scratch_bytes)", entry, scratch_bytes, need);
+  return MTMC_OK;
+}
+
+static int el_check_backward(const char* entry, const float* logits, const int64_t* labels, int64_t n, int32_t n_classes,
+                             int32_t n_steps, const float* grad, const double* record, const float* d_logits) {
+  if (!logits || !labels || !grad || !record || !d_logits)
+    return fail(MTMC_E_ARG, "%s: NULL logits, labels, grad, record or d_logits", entry);
+  if (n < 0 || n_steps < 1 || (n_classes != 1 && n_classes != 2))
+    return fail(MTMC_E_ARG, "%s: n must be >= 0, n_steps >= 1 and n_classes 1 or 2", entry);
+  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7)))
+    return fail(MTMC_E_ARG, "%s: [n, 2] logits and d_logits must be 8-byte aligned", entry);
+  return MTMC_OK;
+}
+
+static int el_check_gamma(const char* entry, float gamma) {
+  if (!(gamma >= 0.f) || gamma > FLT_MAX) return fail(MTMC_E_ARG, "%s: gamma must be finite and >= 0", entry);
+  return MTMC_OK;
+}
+
 int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
                                size_t scratch_bytes, double* record, float* out, int64_t* confusion, void* stream) {
-  if (!logits || !labels || !scratch || !record || !out || !confusion)
-    return fail(MTMC_E_ARG, "edge_loss_forward: NULL logits, labels, scratch, record, out or confusion");
-  if (n < 0 || n_steps < 1 || (n_classes != 1 && n_classes != 2))
-    return fail(MTMC_E_ARG, "edge_loss_forward: n must be >= 0, n_steps >= 1 and n_classes 1 or 2");
-  if (weight_mode < MTMC_EDGE_W_ONE || weight_mode > MTMC_EDGE_W_BALANCED || (weight_mode == MTMC_EDGE_W_GIVEN && !weight))
-    return fail(MTMC_E_ARG, "edge_loss_forward: weight_mode must be MTMC_EDGE_W_ONE, _GIVEN (with weight) or _BALANCED");
-  if ((n_classes == 2 && ((uintptr_t)logits & 7)) || ((uintptr_t)scratch & 7))
-    return fail(MTMC_E_ARG, "edge_loss_forward: [n, 2] logits and scratch must be 8-byte aligned");
-  const size_t need = mtmc_edge_loss_scratch_bytes(n_steps);
-  if (scratch_bytes < need)
-    return fail(MTMC_E_ARG, "edge_loss_forward: scratch has %zu bytes, %zu needed (mtmc_edge_loss_scratch_bytes)", scratch_bytes, need);
+  if (const int rc = el_check_forward("edge_loss_forward", logits, labels, n, n_classes, n_steps, weight_mode, weight, scratch,
+                                      scratch_bytes, record, out, confusion))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, need, s) != hipSuccess) return fail(MTMC_E_HIP, "edge_loss_forward: hipMemsetAsync failed");
+  if (hipMemsetAsync(scratch, 0, mtmc_edge_loss_scratch_bytes(n_steps), s) != hipSuccess)
+    return fail(MTMC_E_HIP, "edge_loss_forward: hipMemsetAsync failed");
   double* acc = static_cast<double*>(scratch);
   if (n > 0) {
     const dim3 grid = mtmc::el_grid(n, n_steps, 512);
@@ -356,12 +477,8 @@ int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64
 
 int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                 const float* grad, const double* record, float* d_logits, void* stream) {
-  if (!logits || !labels || !grad || !record || !d_logits)
-    return fail(MTMC_E_ARG, "edge_loss_backward: NULL logits, labels, grad, record or d_logits");
-  if (n < 0 || n_steps < 1 || (n_classes != 1 && n_classes != 2))
-    return fail(MTMC_E_ARG, "edge_loss_backward: n must be >= 0, n_steps >= 1 and n_classes 1 or 2");
-  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7)))
-    return fail(MTMC_E_ARG, "edge_loss_backward: [n, 2] logits and d_logits must be 8-byte aligned");
+  if (const int rc = el_check_backward("edge_loss_backward", logits, labels, n, n_classes, n_steps, grad, record, d_logits))
+    return rc;
   if (n > 0) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
@@ -371,6 +488,56 @@ int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int6
       hipLaunchKernelGGL(mtmc::el_backward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, record, d_logits);
   }
   return launched("edge_loss_backward");
+}
+
+int32_t mtmc_edge_focal_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                                int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
+                                size_t scratch_bytes, double* record, float* out, int64_t* confusion, float gamma,
+                                float* per_row, void* stream) {
+  if (const int rc = el_check_forward("edge_focal_forward", logits, labels, n, n_classes, n_steps, weight_mode, weight, scratch,
+                                      scratch_bytes, record, out, confusion))
+    return rc;
+  if (const int rc = el_check_gamma("edge_focal_forward", gamma)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(scratch, 0, mtmc_edge_loss_scratch_bytes(n_steps), s) != hipSuccess)
+    return fail(MTMC_E_HIP, "edge_focal_forward: hipMemsetAsync failed");
+  double* acc = static_cast<double*>(scratch);
+  if (n > 0) {
+    const dim3 grid = mtmc::el_grid(n, n_steps, 512);
+    if (n_classes == 2)
+      hipLaunchKernelGGL(mtmc::el_focal_forward_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, acc);
+    else
+      hipLaunchKernelGGL(mtmc::el_focal_forward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, acc);
+  }
+  hipLaunchKernelGGL(mtmc::el_finalize_kernel, dim3(1), dim3(64), 0, s, acc, n_steps, n_classes, weight_mode, weight,
+                     fpr_alpha, record, out, reinterpret_cast<long long*>(confusion));
+  if (per_row && n > 0) {                                      // the weights are the finalize's: one more launch, after it
+    const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
+    if (n_classes == 2)
+      hipLaunchKernelGGL(mtmc::el_focal_rows_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, record, per_row);
+    else
+      hipLaunchKernelGGL(mtmc::el_focal_rows_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, record, per_row);
+  }
+  return launched("edge_focal_forward");
+}
+
+int32_t mtmc_edge_focal_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                                 const float* grad, const double* record, float* d_logits, float gamma, int32_t grad_per_row,
+                                 void* stream) {
+  if (const int rc = el_check_backward("edge_focal_backward", logits, labels, n, n_classes, n_steps, grad, record, d_logits))
+    return rc;
+  if (const int rc = el_check_gamma("edge_focal_backward", gamma)) return rc;
+  if (n > 0) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
+#define MTMC_EL_FOCAL_BWD(C, PER_ROW)                                                                                      \
+    hipLaunchKernelGGL((mtmc::el_focal_backward_kernel<C, PER_ROW>), grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, \
+                       record, gamma, d_logits)
+    if (n_classes == 2) { if (grad_per_row) MTMC_EL_FOCAL_BWD(2, true); else MTMC_EL_FOCAL_BWD(2, false); }
+    else { if (grad_per_row) MTMC_EL_FOCAL_BWD(1, true); else MTMC_EL_FOCAL_BWD(1, false); }
+#undef MTMC_EL_FOCAL_BWD
+  }
+  return launched("edge_focal_backward");
 }
 
 }  // extern "C"

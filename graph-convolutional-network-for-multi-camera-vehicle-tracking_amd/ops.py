@@ -10,7 +10,9 @@
       without the device synchronisations of boolean-mask indexing (reference train.py:98-107, inference.py:20-67)
   edge_loss                                  everything the training / validation loops' `compute_loss_acc` returns
       (reference train.py:36-245: balanced CE or one-logit BCE, FPR term, per-class losses and probabilities, confusion
-      counts) for every classified step in one pass, with a fused backward and no host read
+      counts) for every classified step in one pass, with a fused backward and no host read; `gamma` > 0: focal rows
+  focal_loss / FocalLoss                     the `Focal` loss of the reference's training config (config_training.yaml:37,
+      main_training.py:273-276, whose class is commented out) on [E, 2] or [E, 1] logits: mean, sum or per row
 
 All of them run HIP kernels through the C ABI; CPU tensors are refused.
 """
@@ -237,23 +239,56 @@ class _EdgeLoss(torch.autograd.Function):
         return (None, None, None, None) + tuple(d[i] for i in range(len(steps)))
 
 
-def edge_loss(steps, labels, weight=None, pos_weight=None, fpr_alpha: float = 0.0):
-    """The training / validation loops' `compute_loss_acc` (reference train.py:36-245) over `outputs['classified_edges']`
-    in one pass over the logits block, without a host read (it can sit inside `capture_training_step`):
+class _EdgeFocal(torch.autograd.Function):
+    """_EdgeLoss with the row loss q^gamma * l (mtmc_edge_focal_*).  `rows`: one more output, the [S, E] weighted row
+    losses (one more launch), and THEY are what is differentiable, through the per-row backward; the loss is not then."""
 
-      C = 2 (CE / CE_weighted):  loss = sum_s F.cross_entropy(step_s, labels, weight) + fpr_alpha * sum_s FPR_s
-          `weight`: None, a [2] tensor, or "balanced" = (1, n0/n1) from the label counts of this call (train.py:124-130)
-      C = 1 (BCE / BCE_weighted): loss = sum_s F.binary_cross_entropy_with_logits(step_s[:, 0], labels, pos_weight=pw)
-          + fpr_alpha * sum_s FPR_s;  `pos_weight`: None, a number, a one-element tensor, or "balanced" = n0/n1
+    @staticmethod
+    def forward(ctx, target, weight, mode, fpr_alpha, gamma, rows, *steps):
+        n, c = steps[0].shape
+        s = len(steps)
+        dev = steps[0].device
+        lib = _lib.load()
+        nbytes = lib.mtmc_edge_loss_scratch_bytes(s)
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        record = torch.empty(_lib.EDGE_LOSS_RECORD, dtype=torch.float64, device=dev)
+        out = torch.empty(3 + 5 * s, dtype=torch.float32, device=dev)
+        confusion = torch.empty((s, 4), dtype=torch.int64, device=dev)
+        per_row = torch.empty((s, n), dtype=torch.float32, device=dev) if rows else None
+        _call.run(dev, lib.mtmc_edge_focal_forward,
+                  steps[0].data_ptr(), target.data_ptr(), n, c, s, mode, weight.data_ptr() if weight is not None else None,
+                  fpr_alpha, scratch.data_ptr(), nbytes, record.data_ptr(), out.data_ptr(), confusion.data_ptr(), gamma,
+                  per_row.data_ptr() if rows else None, _call.stream(dev))
+        ctx.save_for_backward(target, record, *steps)
+        ctx.gamma, ctx.rows = gamma, rows
+        r = (out[0], out[3:3 + 2 * s].view(s, 2), out[3 + 2 * s:3 + 4 * s].view(s, 2), confusion, out[3 + 4 * s:], out[1:3])
+        if rows:
+            ctx.mark_non_differentiable(*r)
+            return r + (per_row,)
+        ctx.mark_non_differentiable(*r[1:])
+        return r
 
-    "balanced" with an empty class falls back to (1, 1) (the reference divides by zero there).  `labels` [E]: int64 or the
-    float 0/1 tensor the reference keeps; rows labelled neither 0 nor 1 count for nothing.  Returns the named tuple
-    EdgeLoss(loss, class_loss [S,2], class_prob [S,2], confusion [S,4] = TP FP TN FN, fpr [S], class_weight [2]); only
-    `loss` is differentiable (the FPR term has no gradient, as in the reference).  Steps that are the consecutive slices
-    of one block (what a forward of this package returns) are used in place; any other list is stacked first."""
+    @staticmethod
+    def backward(ctx, *grads):
+        target, record, *steps = ctx.saved_tensors
+        n, c = steps[0].shape
+        dev = steps[0].device
+        d = torch.empty((len(steps), n, c), dtype=torch.float32, device=dev)
+        g = (grads[6] if ctx.rows else grads[0]).contiguous().float()
+        _call.run(dev, _lib.load().mtmc_edge_focal_backward,
+                  steps[0].data_ptr(), target.data_ptr(), n, c, len(steps), g.data_ptr(), record.data_ptr(), d.data_ptr(),
+                  ctx.gamma, int(ctx.rows), _call.stream(dev))
+        return (None,) * 6 + tuple(d[i] for i in range(len(steps)))
+
+
+def _edge_loss(steps, labels, weight, pos_weight, fpr_alpha, gamma, rows):
+    """The checks and the call behind edge_loss and focal_loss: the six EdgeLoss fields, then the [S, E] rows if asked for."""
     steps = list(steps)
     if not steps:
         raise ValueError("edge_loss: no classified steps")
+    gamma = float(gamma)
+    if not 0.0 <= gamma < float("inf"):
+        raise ValueError(f"mtmc_mpn.edge_loss: gamma must be finite and >= 0, got {gamma}")
     s0 = steps[0]
     if s0.dim() != 2 or s0.dtype != torch.float32 or s0.shape[1] not in (1, 2) or labels.shape != s0.shape[:1] \
             or any(t.shape != s0.shape or t.dtype != s0.dtype or t.device != s0.device for t in steps):
@@ -278,4 +313,83 @@ def edge_loss(steps, labels, weight=None, pos_weight=None, fpr_alpha: float = 0.
             raise ValueError(f"mtmc_mpn.edge_loss: {name} must have {2 if c == 2 else 1} element(s)")
     if not _call.steps_block(steps):
         steps = list(torch.stack(steps).unbind(0))           # autograd reaches the pieces through the stack
-    return EdgeLoss(*_EdgeLoss.apply(labels.contiguous().long(), given, mode, float(fpr_alpha), *steps))
+    labels = labels.contiguous().long()
+    if gamma == 0.0 and not rows:
+        return _EdgeLoss.apply(labels, given, mode, float(fpr_alpha), *steps)
+    return _EdgeFocal.apply(labels, given, mode, float(fpr_alpha), gamma, rows, *steps)
+
+
+def edge_loss(steps, labels, weight=None, pos_weight=None, fpr_alpha: float = 0.0, gamma: float = 0.0):
+    """The training / validation loops' `compute_loss_acc` (reference train.py:36-245) over `outputs['classified_edges']`
+    in one pass over the logits block, without a host read (it can sit inside `capture_training_step`):
+
+      C = 2 (CE / CE_weighted):  loss = sum_s F.cross_entropy(step_s, labels, weight) + fpr_alpha * sum_s FPR_s
+          `weight`: None, a [2] tensor, or "balanced" = (1, n0/n1) from the label counts of this call (train.py:124-130)
+      C = 1 (BCE / BCE_weighted): loss = sum_s F.binary_cross_entropy_with_logits(step_s[:, 0], labels, pos_weight=pw)
+          + fpr_alpha * sum_s FPR_s;  `pos_weight`: None, a number, a one-element tensor, or "balanced" = n0/n1
+      gamma > 0 (the config's `Focal`): every row loss l above becomes (1 - p_t)^gamma * l, p_t the probability of the
+          true class; weights, the denominator of the mean and every other field are formed as before, and `class_loss`
+          is the per-class mean of the focal rows.  gamma = 0 is the loss above, through the same kernels.
+
+    "balanced" with an empty class falls back to (1, 1) (the reference divides by zero there).  `labels` [E]: int64 or the
+    float 0/1 tensor the reference keeps; rows labelled neither 0 nor 1 count for nothing.  Returns the named tuple
+    EdgeLoss(loss, class_loss [S,2], class_prob [S,2], confusion [S,4] = TP FP TN FN, fpr [S], class_weight [2]); only
+    `loss` is differentiable (the FPR term has no gradient, as in the reference).  Steps that are the consecutive slices
+    of one block (what a forward of this package returns) are used in place; any other list is stacked first."""
+    return EdgeLoss(*_edge_loss(steps, labels, weight, pos_weight, fpr_alpha, gamma, False))
+
+
+def focal_loss(input, target, gamma: float = 2.0, weight=None, pos_weight=None, reduction: str = "mean"):
+    """Focal loss (Lin et al. 2017) of [E, 2] or [E, 1] float32 logits against 0/1 targets: what the `criterion` /
+    `criterion_no_reduction` of the reference's `Focal` setting were meant to be (main_training.py:273-276; the class they
+    name is commented out).  Row loss f = (1 - p_t)^gamma * CE resp. BCE-with-logits; w = `weight` ([E, 2]) or
+    (1, `pos_weight`) ([E, 1]), each None, numbers or "balanced" as in `edge_loss`; rows labelled neither 0 nor 1 are skipped.
+
+      "mean": `edge_loss([input], target, weight, pos_weight, gamma=gamma).loss`
+      "sum" : sum_i w[y_i] f_i
+      "none": the [E] tensor w[y_i] f_i, 0 on skipped rows
+
+    With one logit, `0.9 * focal_loss(x, t, 5.0, reduction="none")` is the reference's `FocalLoss_binary(5, 0.9, 'none')`
+    (utils.py:695-724).  Its `reduction='mean'` modulates the mean BCE, one scalar, instead of the rows; that form is not a
+    focal loss and is not offered."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"{reduction} is not a valid value for reduction")
+    r = _edge_loss([input], target, weight, pos_weight, 0.0, gamma, reduction != "mean")
+    if reduction == "mean":
+        return r[0]
+    return r[6][0] if reduction == "none" else r[6].sum()
+
+
+class FocalLoss(torch.nn.Module):
+    """`focal_loss` as a module, for the `utils.FocalLoss(reduction=..., alpha=...)` calls of reference
+    main_training.py:275-276.  `alpha`: None; "balanced"; a [2] tensor of class weights; or a number a, the class weights
+    (1 - a, a) of Lin et al.  One-logit input has a single `pos_weight`, so weights (w0, w1) are passed there as
+    pos_weight = w1 / w0 with the result scaled by w0 -- for a number a: pos_weight = a / (1 - a), times (1 - a), a < 1.
+    (The reduction "mean" of one-logit input divides by the row count, as BCEWithLogitsLoss does, that of two-logit input
+    by the sum of the rows' weights, as CrossEntropyLoss does.)"""
+
+    def __init__(self, gamma: float = 2.0, alpha=None, reduction: str = "mean"):
+        super().__init__()
+        if not isinstance(alpha, (str, torch.Tensor)) and alpha is not None and not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"FocalLoss: alpha must lie in [0, 1], got {alpha}")
+        self.gamma, self.alpha, self.reduction = float(gamma), alpha, reduction
+
+    def forward(self, input, target):
+        a, one = self.alpha, input.dim() == 2 and input.shape[1] == 1
+        if a is None or isinstance(a, str):
+            return focal_loss(input, target, self.gamma, **{"pos_weight" if one else "weight": a}, reduction=self.reduction)
+        if isinstance(a, torch.Tensor):
+            w = a.detach().to(input.device, torch.float32).view(2)
+            if one:
+                return w[0] * focal_loss(input, target, self.gamma, pos_weight=w[1:] / w[:1], reduction=self.reduction)
+            return focal_loss(input, target, self.gamma, weight=w, reduction=self.reduction)
+        a = float(a)
+        if one:
+            if a >= 1.0:
+                raise ValueError("FocalLoss: one-logit input needs alpha < 1 (pos_weight = alpha / (1 - alpha))")
+            return (1.0 - a) * focal_loss(input, target, self.gamma, pos_weight=a / (1.0 - a), reduction=self.reduction)
+        w = torch.full((2,), a, dtype=torch.float32, device=input.device)           # (fills: capture-safe)
+        w[:1].fill_(1.0 - a)
+        return focal_loss(input, target, self.gamma, weight=w, reduction=self.reduction)
+
+

@@ -455,6 +455,30 @@ int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64
 int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                 const float* grad, const double* record, float* d_logits, void* stream);
 
+/* ---- focal loss (Lin et al., "Focal Loss for Dense Object Detection") for both classifier forms: the fourth entry of
+ * the reference's `loss_name: CE_weighted # CE_weighted Focal BCE_weighted BCE` (config/config_training.yaml:37), whose
+ * callers (main_training.py:273-276, train.py:144-181) name a class that is commented out; only the one-logit
+ * utils.FocalLoss_binary (utils.py:695-724) is live there.  Everything of mtmc_edge_loss_* holds (arguments, scratch size,
+ * record and out layout, weights, D, FPR term, class_prob, confusion, refusals) with one change: with z, l, p = sigmoid(z),
+ * q = 1 - p as above, the row loss is
+ *   f = q^gamma * l,          loss = sum_s (w0 F0_s + w1 F1_s) / D + fpr_alpha * sum_s fpr_s,   class_loss = F_c / n_c
+ *   d f / d z = -q^gamma * (gamma * p * l + q)
+ * (F_c = the sum of f over the rows of class c; D as above, not modulated).  q^(gamma - 1) is never formed: the factored
+ * gradient is finite for every gamma >= 0 at q = 0 (loss 0, gradient 0 there for gamma > 0) and is -q at gamma = 0, which
+ * is mtmc_edge_loss_*.  On softmax outputs f = (1 - p_t)^gamma * CE; balance * f is FocalLoss_binary(reduction='none').
+ * (FocalLoss_binary with reduction='mean' modulates the mean BCE, one scalar, not the rows: it is not reproduced.)
+ * forward: per_row, if not NULL, receives [n_steps][n] f32 = w[y] * f (0 on skipped rows) from one more launch after the
+ * finalize.  backward: grad_per_row == 0: grad[0] is the gradient of the loss, as above; != 0: grad [n_steps][n] is the
+ * gradient of per_row, d_logits = grad[s][i] * w[y] * d f / d x (no division by D).
+ * MTMC_E_ARG as mtmc_edge_loss_*, and for a gamma that is negative, NaN or infinite. */
+int32_t mtmc_edge_focal_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                                int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
+                                size_t scratch_bytes, double* record, float* out, int64_t* confusion, float gamma,
+                                float* per_row, void* stream);
+int32_t mtmc_edge_focal_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                                 const float* grad, const double* record, float* d_logits, float gamma, int32_t grad_per_row,
+                                 void* stream);
+
 /* ---- post-processing of the last logits (replaces reference inference.py:475-489, post_processing
  * inference.py:70-169 and utils.py compute_SCC_and_Clusters :30-52, splitting :54-123, remove_edges_single_direction
  * :125-142, pruning :144-339) ----
