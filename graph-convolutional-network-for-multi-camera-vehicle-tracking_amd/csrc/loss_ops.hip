@@ -112,6 +112,19 @@ __device__ __forceinline__ void el_row(float z, float& l, float& p, float& q) { 
   p = z >= 0.f ? inv : e * inv;
   q = z >= 0.f ? e * inv : inv;
 }
+// The row loss f and d f / d z of both forms (mtmc_edge_loss_* / mtmc_edge_focal_*).  Plain: f = l, d f / d z = -q.
+// FOCAL: f = q^gamma * l and d f / d z = -q^gamma * (gamma * p * l + q): q^(gamma - 1) never appears, so q = 0 (a margin
+// past ~ +104, where e is 0) gives f = 0 and d f / d z = 0 for every gamma > 0, and nothing divides by q.  powf on the q of
+// el_row, which has no cancellation on either side of z = 0.
+template <bool FOCAL>
+__device__ __forceinline__ void el_loss_row(float z, float gamma, float& f, float& df, float& p) {
+  float l, q;
+  el_row(z, l, p, q);
+  if (!FOCAL) { f = l; df = -q; return; }
+  const float m = powf(q, gamma);
+  f = m * l;
+  df = -m * (gamma * p * l + q);
+}
 template <int C>
 __device__ __forceinline__ float el_margin(const float* x, int64_t i, bool y, bool& pred) {
   if (C == 2) {
@@ -127,10 +140,11 @@ __device__ __forceinline__ float el_margin(const float* x, int64_t i, bool y, bo
 // scratch: per step kStatRep replicas of kElStride 64-bit words (128 bytes): L0 L1 P0 P1 (f64) | TP FP TN FN (u64) | padding
 constexpr int kElStride = 16;
 
-// grid (x: row blocks, y: steps); both dimensions are strided over, so any n and any n_steps run
-template <int C>
+// grid (x: row blocks, y: steps); both dimensions are strided over, so any n and any n_steps run.  The L0 / L1 words hold
+// sum f, so both forms share the scratch and the finalize; gamma is read with FOCAL only
+template <int C, bool FOCAL>
 __global__ __launch_bounds__(256) void el_forward_kernel(const float* logits, const int64_t* labels, int64_t n, int n_steps,
-                                                         double* scratch) {
+                                                         float gamma, double* scratch) {
   __shared__ double red[4 * 4];
   __shared__ unsigned int cnt[4];
   const int64_t nthreads = (int64_t)gridDim.x * 256;
@@ -144,9 +158,9 @@ __global__ __launch_bounds__(256) void el_forward_kernel(const float* logits, co
       const bool y = lab == 1;
       bool pred;
       const float z = el_margin<C>(x, i, y, pred);
-      float l, p, q;
-      el_row(z, l, p, q);
-      if (y) { acc[1] += l; acc[3] += p; } else { acc[0] += l; acc[2] += p; }
+      float f, df, p;
+      el_loss_row<FOCAL>(z, gamma, f, df, p);
+      if (y) { acc[1] += f; acc[3] += p; } else { acc[0] += f; acc[2] += p; }
       ++c[confusion_slot(y, pred)];
     }
     double* rep = scratch + (int64_t)s * kStatRep * kElStride;
@@ -198,71 +212,6 @@ __global__ __launch_bounds__(64) void el_finalize_kernel(const double* scratch, 
   }
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void el_backward_kernel(const float* logits, const int64_t* labels, int64_t n, int n_steps,
-                                                          const float* grad, const double* record, float* d_logits) {
-  const double gd = (double)grad[0] / record[2];
-  const float g0 = (float)(gd * record[0]), g1 = (float)(gd * record[1]);
-  const int64_t nthreads = (int64_t)gridDim.x * 256;
-  for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
-    const float* x = logits + (int64_t)s * n * C;
-    float* d = d_logits + (int64_t)s * n * C;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
-      const int64_t lab = labels[i];
-      float dz = 0.f;                                        // d loss / d z; skipped rows: 0
-      const bool y = lab == 1;
-      if (lab == 0 || lab == 1) {
-        bool pred;
-        float l, p, q;
-        el_row(el_margin<C>(x, i, y, pred), l, p, q);
-        dz = -(y ? g1 : g0) * q;
-      }
-      if (C == 2) reinterpret_cast<float2*>(d)[i] = y ? make_float2(-dz, dz) : make_float2(dz, -dz);
-      else d[i] = y ? dz : -dz;
-    }
-  }
-}
-
-// ---- mtmc_edge_focal_*: the same pass with the focal row loss f = q^gamma * l (include/mtmc_mpn.h) ---------------------
-// d f / d z = -q^gamma * (gamma * p * l + q): q^(gamma - 1) never appears, so q = 0 (a margin past ~ +104, where e is 0)
-// gives f = 0 and d f / d z = 0 for every gamma > 0, and nothing divides by q.  powf on the q of el_row, which has no
-// cancellation on either side of z = 0.
-__device__ __forceinline__ void el_focal_row(float z, float gamma, float& f, float& df, float& p) {
-  float l, q;
-  el_row(z, l, p, q);
-  const float m = powf(q, gamma);
-  f = m * l;
-  df = -m * (gamma * p * l + q);
-}
-
-// as el_forward_kernel, with sum f in the L0 / L1 words; same scratch, same finalize
-template <int C>
-__global__ __launch_bounds__(256) void el_focal_forward_kernel(const float* logits, const int64_t* labels, int64_t n,
-                                                               int n_steps, float gamma, double* scratch) {
-  __shared__ double red[4 * 4];
-  __shared__ unsigned int cnt[4];
-  const int64_t nthreads = (int64_t)gridDim.x * 256;
-  for (int s = blockIdx.y; s < n_steps; s += gridDim.y) {
-    const float* x = logits + (int64_t)s * n * C;
-    double acc[4] = {0, 0, 0, 0};
-    unsigned int c[4] = {0, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
-      const int64_t lab = labels[i];
-      if (lab != 0 && lab != 1) continue;
-      const bool y = lab == 1;
-      bool pred;
-      const float z = el_margin<C>(x, i, y, pred);
-      float f, df, p;
-      el_focal_row(z, gamma, f, df, p);
-      if (y) { acc[1] += f; acc[3] += p; } else { acc[0] += f; acc[2] += p; }
-      ++c[confusion_slot(y, pred)];
-    }
-    double* rep = scratch + (int64_t)s * kStatRep * kElStride;
-    block_atomic_add<4>(acc, rep, kElStride, red);
-    block_count_add<4>(c, reinterpret_cast<unsigned long long*>(rep + (blockIdx.x % kStatRep) * kElStride + 4), cnt);
-  }
-}
-
 // per_row [n_steps][n] = w[y] * f, 0 on skipped rows; after the finalize, whose record holds the (possibly balanced) weights
 template <int C>
 __global__ __launch_bounds__(256) void el_focal_rows_kernel(const float* logits, const int64_t* labels, int64_t n, int n_steps,
@@ -279,7 +228,7 @@ __global__ __launch_bounds__(256) void el_focal_rows_kernel(const float* logits,
         const bool y = lab == 1;
         bool pred;
         float f, df, p;
-        el_focal_row(el_margin<C>(x, i, y, pred), gamma, f, df, p);
+        el_loss_row<true>(el_margin<C>(x, i, y, pred), gamma, f, df, p);
         v = (y ? w1 : w0) * f;
       }
       out[i] = v;
@@ -287,11 +236,12 @@ __global__ __launch_bounds__(256) void el_focal_rows_kernel(const float* logits,
   }
 }
 
-// PER_ROW: grad [n_steps][n] is the upstream gradient of per_row (no division by D); otherwise grad[0] as el_backward_kernel
-template <int C, bool PER_ROW>
-__global__ __launch_bounds__(256) void el_focal_backward_kernel(const float* logits, const int64_t* labels, int64_t n,
-                                                                int n_steps, const float* grad, const double* record,
-                                                                float gamma, float* d_logits) {
+// d_logits of the loss: grad[0] / D times the class weight times d f / d z.  PER_ROW (FOCAL only): grad [n_steps][n] is the
+// upstream gradient of per_row, one value per row and no division by D
+template <int C, bool FOCAL, bool PER_ROW>
+__global__ __launch_bounds__(256) void el_backward_kernel(const float* logits, const int64_t* labels, int64_t n, int n_steps,
+                                                          const float* grad, const double* record, float gamma,
+                                                          float* d_logits) {
   const double gd = PER_ROW ? 1.0 : (double)grad[0] / record[2];
   const float g0 = (float)(gd * record[0]), g1 = (float)(gd * record[1]);
   const int64_t nthreads = (int64_t)gridDim.x * 256;
@@ -300,12 +250,12 @@ __global__ __launch_bounds__(256) void el_focal_backward_kernel(const float* log
     float* d = d_logits + (int64_t)s * n * C;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += nthreads) {
       const int64_t lab = labels[i];
-      float dz = 0.f;
+      float dz = 0.f;                                        // d loss / d z; skipped rows: 0
       const bool y = lab == 1;
       if (lab == 0 || lab == 1) {
         bool pred;
         float f, df, p;
-        el_focal_row(el_margin<C>(x, i, y, pred), gamma, f, df, p);
+        el_loss_row<FOCAL>(el_margin<C>(x, i, y, pred), gamma, f, df, p);
         dz = (y ? g1 : g0) * df;
         if (PER_ROW) dz *= grad[(int64_t)s * n + i];
       }
@@ -328,78 +278,83 @@ extern "C" {
 using mtmc_api::fail;
 using mtmc_api::launched;
 
-int32_t mtmc_cross_entropy_forward(const float* logits, const int64_t* labels, const float* weight, int64_t n, int32_t n_classes,
-                                   int64_t ignore_index, int32_t mode, float* per_sample, double* sums, float* loss_out,
-                                   void* stream) {
-  if (!logits || !labels || !sums) return fail(MTMC_E_ARG, "cross_entropy_forward: NULL logits, labels or sums");
-  if (n < 0 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
-    return fail(MTMC_E_ARG, "cross_entropy_forward: n must be >= 0 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
-  if (n_classes == 2 && ((uintptr_t)logits & 7)) return fail(MTMC_E_ARG, "cross_entropy_forward: [n, 2] logits must be 8-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * mtmc::kStatRep, s) != hipSuccess)
-    return fail(MTMC_E_HIP, "cross_entropy_forward: hipMemsetAsync failed");
-  if (n > 0)
-    hipLaunchKernelGGL(mtmc::ce_forward_kernel, dim3(mtmc::blocks_for(n, 256, mtmc::kCeBlocksFwd)), dim3(256), 0, s, logits,
-                       labels, weight, n, n_classes, ignore_index, per_sample, sums, (int64_t)0);
-  hipLaunchKernelGGL(mtmc::ce_finalize_kernel, dim3(1), dim3(1), 0, s, sums, mode, loss_out, 1.0);
-  return launched("cross_entropy_forward");
+// The argument checks of the four cross-entropy entry points; `entry` starts the error text.  `steps`: n_steps is an
+// argument and the reduction is mean or sum; `backward`: grad and d_logits as well, and the sums wherever the mode reads them
+// (the plain forward takes any mode: 0 is the mean, everything else the sum, next to the per-sample losses)
+static int ce_check(const char* entry, bool steps, bool backward, const float* logits, const int64_t* labels, int64_t n,
+                    int32_t n_classes, int32_t n_steps, int32_t mode, const float* grad, const double* sums,
+                    const float* d_logits) {
+  if (!logits || !labels || (backward ? !grad || !d_logits || (steps && !sums) : !sums))
+    return fail(MTMC_E_ARG, "%s: NULL logits, labels%s", entry,
+                !backward ? " or sums" : steps ? ", grad, sums or d_logits" : ", grad or d_logits");
+  if (n < 0 || n_steps < 1 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
+    return fail(MTMC_E_ARG, "%s: n must be >= 0%s and n_classes in [1, %d]", entry, steps ? ", n_steps >= 1" : "", MTMC_MAX_CLASSES);
+  if (steps && (mode < 0 || mode > 1)) return fail(MTMC_E_ARG, "%s: mode must be 0 (mean) or 1 (sum)", entry);
+  if (!steps && backward && (mode < 0 || mode > 2 || (mode == 0 && !sums)))
+    return fail(MTMC_E_ARG, "%s: mode must be 0 (mean, with the forward's sums), 1 (sum) or 2 (none)", entry);
+  if (n_classes == 2 && (((uintptr_t)logits & 7) || (backward && ((uintptr_t)d_logits & 7))))
+    return fail(MTMC_E_ARG, "%s: [n, 2] logits%s must be 8-byte aligned", entry, backward ? " and d_logits" : "");
+  return MTMC_OK;
 }
 
 // The training loop's `sum(criterion(step, labels) for step in outputs['classified_edges'])` (reference train.py:118-138:
-// every classified step against the SAME labels) in one pass over the [n_steps][n][C] logits block the forward emits:
-// with equal labels the weight sums of the steps are equal, so sum_s mean_s = n_steps * (sum of all terms / sum of all
-// weights).  mode 0 = mean per step (then summed), 1 = sum.
-int32_t mtmc_cross_entropy_steps_forward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
-                                         int32_t n_classes, int32_t n_steps, int64_t ignore_index, int32_t mode,
-                                         double* sums, float* loss_out, void* stream) {
-  if (!logits || !labels || !sums) return fail(MTMC_E_ARG, "cross_entropy_steps_forward: NULL logits, labels or sums");
-  if (n < 0 || n_steps < 1 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
-    return fail(MTMC_E_ARG, "cross_entropy_steps_forward: n must be >= 0, n_steps >= 1 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
-  if (mode < 0 || mode > 1) return fail(MTMC_E_ARG, "cross_entropy_steps_forward: mode must be 0 (mean) or 1 (sum)");
-  if (n_classes == 2 && ((uintptr_t)logits & 7))
-    return fail(MTMC_E_ARG, "cross_entropy_steps_forward: [n, 2] logits must be 8-byte aligned");
+// every classified step against the SAME labels) is one pass over the [n_steps][n][C] logits block the forward emits, as
+// n * n_steps rows whose labels repeat with period n: with equal labels the weight sums of the steps are equal, so
+// sum_s mean_s = n_steps * (sum of all terms / sum of all weights).  The plain entry points: n_steps = 1, period = 0.
+static int ce_forward(const char* entry, const float* logits, const int64_t* labels, const float* weight, int64_t n,
+                      int32_t n_classes, int32_t n_steps, int64_t period, int64_t ignore_index, int32_t mode, float* per_sample,
+                      double* sums, float* loss_out, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * mtmc::kStatRep, s) != hipSuccess)
-    return fail(MTMC_E_HIP, "cross_entropy_steps_forward: hipMemsetAsync failed");
+    return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
   if (n > 0)
     hipLaunchKernelGGL(mtmc::ce_forward_kernel, dim3(mtmc::blocks_for(n * n_steps, 256, mtmc::kCeBlocksFwd)), dim3(256), 0, s,
-                       logits, labels, weight, n * n_steps, n_classes, ignore_index, (float*)nullptr, sums, n);
+                       logits, labels, weight, n * n_steps, n_classes, ignore_index, per_sample, sums, period);
   hipLaunchKernelGGL(mtmc::ce_finalize_kernel, dim3(1), dim3(1), 0, s, sums, mode, loss_out, (double)n_steps);
-  return launched("cross_entropy_steps_forward");
+  return launched(entry);
 }
 
-int32_t mtmc_cross_entropy_steps_backward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
-                                          int32_t n_classes, int32_t n_steps, int64_t ignore_index, int32_t mode,
-                                          const float* grad, const double* sums, float* d_logits, void* stream) {
-  if (!logits || !labels || !grad || !sums || !d_logits)
-    return fail(MTMC_E_ARG, "cross_entropy_steps_backward: NULL logits, labels, grad, sums or d_logits");
-  if (n < 0 || n_steps < 1 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
-    return fail(MTMC_E_ARG, "cross_entropy_steps_backward: n must be >= 0, n_steps >= 1 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
-  if (mode < 0 || mode > 1) return fail(MTMC_E_ARG, "cross_entropy_steps_backward: mode must be 0 (mean) or 1 (sum)");
-  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7)))
-    return fail(MTMC_E_ARG, "cross_entropy_steps_backward: [n, 2] logits and d_logits must be 8-byte aligned");
+static int ce_backward(const char* entry, const float* logits, const int64_t* labels, const float* weight, int64_t n,
+                       int32_t n_classes, int32_t n_steps, int64_t period, int64_t ignore_index, int32_t mode,
+                       const float* grad, const double* sums, float* d_logits, void* stream) {
   if (n > 0)
     hipLaunchKernelGGL(mtmc::ce_backward_kernel, dim3(mtmc::blocks_for(n * n_steps, 256, mtmc::kCeBlocks)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), logits, labels, weight, n * n_steps, n_classes, ignore_index, mode,
-                       grad, sums, d_logits, n, (double)n_steps);
-  return launched("cross_entropy_steps_backward");
+                       grad, sums, d_logits, period, (double)n_steps);
+  return launched(entry);
+}
+
+int32_t mtmc_cross_entropy_forward(const float* logits, const int64_t* labels, const float* weight, int64_t n, int32_t n_classes,
+                                   int64_t ignore_index, int32_t mode, float* per_sample, double* sums, float* loss_out,
+                                   void* stream) {
+  const char* entry = "cross_entropy_forward";
+  if (const int rc = ce_check(entry, false, false, logits, labels, n, n_classes, 1, mode, nullptr, sums, nullptr)) return rc;
+  return ce_forward(entry, logits, labels, weight, n, n_classes, 1, 0, ignore_index, mode, per_sample, sums, loss_out, stream);
 }
 
 int32_t mtmc_cross_entropy_backward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
                                     int32_t n_classes, int64_t ignore_index, int32_t mode, const float* grad,
                                     const double* sums, float* d_logits, void* stream) {
-  if (!logits || !labels || !grad || !d_logits) return fail(MTMC_E_ARG, "cross_entropy_backward: NULL logits, labels, grad or d_logits");
-  if (n < 0 || n_classes < 1 || n_classes > MTMC_MAX_CLASSES)
-    return fail(MTMC_E_ARG, "cross_entropy_backward: n must be >= 0 and n_classes in [1, %d]", MTMC_MAX_CLASSES);
-  if (mode < 0 || mode > 2 || (mode == 0 && !sums))
-    return fail(MTMC_E_ARG, "cross_entropy_backward: mode must be 0 (mean, with the forward's sums), 1 (sum) or 2 (none)");
-  if (n_classes == 2 && (((uintptr_t)logits & 7) || ((uintptr_t)d_logits & 7)))
-    return fail(MTMC_E_ARG, "cross_entropy_backward: [n, 2] logits and d_logits must be 8-byte aligned");
-  if (n > 0)
-    hipLaunchKernelGGL(mtmc::ce_backward_kernel, dim3(mtmc::blocks_for(n, 256, mtmc::kCeBlocks)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), logits, labels, weight, n, n_classes, ignore_index, mode, grad, sums,
-                       d_logits, (int64_t)0, 1.0);
-  return launched("cross_entropy_backward");
+  const char* entry = "cross_entropy_backward";
+  if (const int rc = ce_check(entry, false, true, logits, labels, n, n_classes, 1, mode, grad, sums, d_logits)) return rc;
+  return ce_backward(entry, logits, labels, weight, n, n_classes, 1, 0, ignore_index, mode, grad, sums, d_logits, stream);
+}
+
+// mode 0 = mean per step (then summed), 1 = sum
+int32_t mtmc_cross_entropy_steps_forward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
+                                         int32_t n_classes, int32_t n_steps, int64_t ignore_index, int32_t mode,
+                                         double* sums, float* loss_out, void* stream) {
+  const char* entry = "cross_entropy_steps_forward";
+  if (const int rc = ce_check(entry, true, false, logits, labels, n, n_classes, n_steps, mode, nullptr, sums, nullptr)) return rc;
+  return ce_forward(entry, logits, labels, weight, n, n_classes, n_steps, n, ignore_index, mode, nullptr, sums, loss_out, stream);
+}
+
+int32_t mtmc_cross_entropy_steps_backward(const float* logits, const int64_t* labels, const float* weight, int64_t n,
+                                          int32_t n_classes, int32_t n_steps, int64_t ignore_index, int32_t mode,
+                                          const float* grad, const double* sums, float* d_logits, void* stream) {
+  const char* entry = "cross_entropy_steps_backward";
+  if (const int rc = ce_check(entry, true, true, logits, labels, n, n_classes, n_steps, mode, grad, sums, d_logits)) return rc;
+  return ce_backward(entry, logits, labels, weight, n, n_classes, n_steps, n, ignore_index, mode, grad, sums, d_logits, stream);
 }
 
 int32_t mtmc_edge_confusion(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int64_t* counts,
@@ -453,91 +408,78 @@ static int el_check_gamma(const char* entry, float gamma) {
   return MTMC_OK;
 }
 
-int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
-                               int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
-                               size_t scratch_bytes, double* record, float* out, int64_t* confusion, void* stream) {
-  if (const int rc = el_check_forward("edge_loss_forward", logits, labels, n, n_classes, n_steps, weight_mode, weight, scratch,
-                                      scratch_bytes, record, out, confusion))
+// Both forward entry points: check, memset, row pass, finalize; with per_row one more launch after the finalize, whose
+// record holds the weights.  The plain one passes gamma = 0 and no per_row
+static int el_forward(const char* entry, bool focal, const float* logits, const int64_t* labels, int64_t n, int32_t n_classes,
+                      int32_t n_steps, int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
+                      size_t scratch_bytes, double* record, float* out, int64_t* confusion, float gamma, float* per_row,
+                      void* stream) {
+  if (const int rc = el_check_forward(entry, logits, labels, n, n_classes, n_steps, weight_mode, weight, scratch, scratch_bytes,
+                                      record, out, confusion))
     return rc;
+  if (const int rc = el_check_gamma(entry, gamma)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(scratch, 0, mtmc_edge_loss_scratch_bytes(n_steps), s) != hipSuccess)
-    return fail(MTMC_E_HIP, "edge_loss_forward: hipMemsetAsync failed");
+    return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
   double* acc = static_cast<double*>(scratch);
+  const bool two = n_classes == 2;
   if (n > 0) {
-    const dim3 grid = mtmc::el_grid(n, n_steps, 512);
-    if (n_classes == 2)
-      hipLaunchKernelGGL(mtmc::el_forward_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, acc);
-    else
-      hipLaunchKernelGGL(mtmc::el_forward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, acc);
+    const auto pass = focal ? (two ? mtmc::el_forward_kernel<2, true> : mtmc::el_forward_kernel<1, true>)
+                            : (two ? mtmc::el_forward_kernel<2, false> : mtmc::el_forward_kernel<1, false>);
+    hipLaunchKernelGGL(pass, mtmc::el_grid(n, n_steps, 512), dim3(256), 0, s, logits, labels, n, n_steps, gamma, acc);
   }
   hipLaunchKernelGGL(mtmc::el_finalize_kernel, dim3(1), dim3(64), 0, s, acc, n_steps, n_classes, weight_mode, weight,
                      fpr_alpha, record, out, reinterpret_cast<long long*>(confusion));
-  return launched("edge_loss_forward");
+  if (per_row && n > 0) {
+    const auto rows = two ? mtmc::el_focal_rows_kernel<2> : mtmc::el_focal_rows_kernel<1>;
+    hipLaunchKernelGGL(rows, mtmc::el_grid(n, n_steps, 2048), dim3(256), 0, s, logits, labels, n, n_steps, gamma, record, per_row);
+  }
+  return launched(entry);
+}
+
+// Both backward entry points: check, then the instantiation (per-row gradients exist in the focal form only)
+static int el_backward(const char* entry, bool focal, const float* logits, const int64_t* labels, int64_t n, int32_t n_classes,
+                       int32_t n_steps, const float* grad, const double* record, float* d_logits, float gamma, bool per_row,
+                       void* stream) {
+  if (const int rc = el_check_backward(entry, logits, labels, n, n_classes, n_steps, grad, record, d_logits)) return rc;
+  if (const int rc = el_check_gamma(entry, gamma)) return rc;
+  if (n > 0) {
+    const bool two = n_classes == 2;
+    const auto pass = !focal    ? (two ? mtmc::el_backward_kernel<2, false, false> : mtmc::el_backward_kernel<1, false, false>)
+                      : per_row ? (two ? mtmc::el_backward_kernel<2, true, true> : mtmc::el_backward_kernel<1, true, true>)
+                                : (two ? mtmc::el_backward_kernel<2, true, false> : mtmc::el_backward_kernel<1, true, false>);
+    hipLaunchKernelGGL(pass, mtmc::el_grid(n, n_steps, 2048), dim3(256), 0, static_cast<hipStream_t>(stream), logits, labels, n,
+                       n_steps, grad, record, gamma, d_logits);
+  }
+  return launched(entry);
+}
+
+int32_t mtmc_edge_loss_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
+                               int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
+                               size_t scratch_bytes, double* record, float* out, int64_t* confusion, void* stream) {
+  return el_forward("edge_loss_forward", false, logits, labels, n, n_classes, n_steps, weight_mode, weight, fpr_alpha, scratch,
+                    scratch_bytes, record, out, confusion, 0.f, nullptr, stream);
 }
 
 int32_t mtmc_edge_loss_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                 const float* grad, const double* record, float* d_logits, void* stream) {
-  if (const int rc = el_check_backward("edge_loss_backward", logits, labels, n, n_classes, n_steps, grad, record, d_logits))
-    return rc;
-  if (n > 0) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
-    if (n_classes == 2)
-      hipLaunchKernelGGL(mtmc::el_backward_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, record, d_logits);
-    else
-      hipLaunchKernelGGL(mtmc::el_backward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, record, d_logits);
-  }
-  return launched("edge_loss_backward");
+  return el_backward("edge_loss_backward", false, logits, labels, n, n_classes, n_steps, grad, record, d_logits, 0.f, false,
+                     stream);
 }
 
 int32_t mtmc_edge_focal_forward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                 int32_t weight_mode, const float* weight, float fpr_alpha, void* scratch,
                                 size_t scratch_bytes, double* record, float* out, int64_t* confusion, float gamma,
                                 float* per_row, void* stream) {
-  if (const int rc = el_check_forward("edge_focal_forward", logits, labels, n, n_classes, n_steps, weight_mode, weight, scratch,
-                                      scratch_bytes, record, out, confusion))
-    return rc;
-  if (const int rc = el_check_gamma("edge_focal_forward", gamma)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(scratch, 0, mtmc_edge_loss_scratch_bytes(n_steps), s) != hipSuccess)
-    return fail(MTMC_E_HIP, "edge_focal_forward: hipMemsetAsync failed");
-  double* acc = static_cast<double*>(scratch);
-  if (n > 0) {
-    const dim3 grid = mtmc::el_grid(n, n_steps, 512);
-    if (n_classes == 2)
-      hipLaunchKernelGGL(mtmc::el_focal_forward_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, acc);
-    else
-      hipLaunchKernelGGL(mtmc::el_focal_forward_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, acc);
-  }
-  hipLaunchKernelGGL(mtmc::el_finalize_kernel, dim3(1), dim3(64), 0, s, acc, n_steps, n_classes, weight_mode, weight,
-                     fpr_alpha, record, out, reinterpret_cast<long long*>(confusion));
-  if (per_row && n > 0) {                                      // the weights are the finalize's: one more launch, after it
-    const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
-    if (n_classes == 2)
-      hipLaunchKernelGGL(mtmc::el_focal_rows_kernel<2>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, record, per_row);
-    else
-      hipLaunchKernelGGL(mtmc::el_focal_rows_kernel<1>, grid, dim3(256), 0, s, logits, labels, n, n_steps, gamma, record, per_row);
-  }
-  return launched("edge_focal_forward");
+  return el_forward("edge_focal_forward", true, logits, labels, n, n_classes, n_steps, weight_mode, weight, fpr_alpha, scratch,
+                    scratch_bytes, record, out, confusion, gamma, per_row, stream);
 }
 
 int32_t mtmc_edge_focal_backward(const float* logits, const int64_t* labels, int64_t n, int32_t n_classes, int32_t n_steps,
                                  const float* grad, const double* record, float* d_logits, float gamma, int32_t grad_per_row,
                                  void* stream) {
-  if (const int rc = el_check_backward("edge_focal_backward", logits, labels, n, n_classes, n_steps, grad, record, d_logits))
-    return rc;
-  if (const int rc = el_check_gamma("edge_focal_backward", gamma)) return rc;
-  if (n > 0) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid = mtmc::el_grid(n, n_steps, 2048);
-#define MTMC_EL_FOCAL_BWD(C, PER_ROW)                                                                                      \
-    hipLaunchKernelGGL((mtmc::el_focal_backward_kernel<C, PER_ROW>), grid, dim3(256), 0, s, logits, labels, n, n_steps, grad, \
-                       record, gamma, d_logits)
-    if (n_classes == 2) { if (grad_per_row) MTMC_EL_FOCAL_BWD(2, true); else MTMC_EL_FOCAL_BWD(2, false); }
-    else { if (grad_per_row) MTMC_EL_FOCAL_BWD(1, true); else MTMC_EL_FOCAL_BWD(1, false); }
-#undef MTMC_EL_FOCAL_BWD
-  }
-  return launched("edge_focal_backward");
+  return el_backward("edge_focal_backward", true, logits, labels, n, n_classes, n_steps, grad, record, d_logits, gamma,
+                     grad_per_row != 0, stream);
 }
 
 }  // extern "C"

@@ -99,33 +99,45 @@ _REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
 
 
 class _CrossEntropy(torch.autograd.Function):
+    """One [E, C] tensor (any reduction: mtmc_cross_entropy_*), or the classified steps of one forward, consecutive [E, C]
+    slices of one block (mean or sum: mtmc_cross_entropy_steps_*, one pass over all of them)."""
+
     @staticmethod
-    def forward(ctx, logits, target, weight, mode, ignore_index):
-        n, c = logits.shape
-        dev = logits.device
-        x = logits.contiguous()
+    def forward(ctx, target, weight, mode, ignore_index, *steps):
+        s = len(steps)
+        x = steps[0].contiguous() if s == 1 else steps[0]
+        n, c = x.shape
+        dev = x.device
+        lib = _lib.load()
         sums = torch.empty(2 * _lib.STAT_REPLICAS, dtype=torch.float64, device=dev)
-        per = torch.empty(n, dtype=torch.float32, device=dev) if mode == 2 else None
-        loss = torch.empty((), dtype=torch.float32, device=dev) if mode != 2 else None
-        _call.run(dev, _lib.load().mtmc_cross_entropy_forward,
-                  x.data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c, ignore_index,
-                  mode, per.data_ptr() if per is not None else None, sums.data_ptr(),
-                  loss.data_ptr() if loss is not None else None, _call.stream(dev))
-        ctx.save_for_backward(x, target, weight, sums)
+        out = torch.empty(n if mode == 2 else (), dtype=torch.float32, device=dev)
+        head = (x.data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c)
+        if s == 1:
+            per, loss = (out.data_ptr(), None) if mode == 2 else (None, out.data_ptr())
+            _call.run(dev, lib.mtmc_cross_entropy_forward, *head, ignore_index, mode, per, sums.data_ptr(), loss, _call.stream(dev))
+        else:
+            _call.run(dev, lib.mtmc_cross_entropy_steps_forward, *head, s, ignore_index, mode, sums.data_ptr(), out.data_ptr(),
+                      _call.stream(dev))
+        ctx.save_for_backward(target, weight, sums, x, *steps[1:])
         ctx.mode, ctx.ignore_index = mode, ignore_index
-        return per if mode == 2 else loss
+        return out
 
     @staticmethod
     def backward(ctx, grad):
-        x, target, weight, sums = ctx.saved_tensors
-        n, c = x.shape
-        dev = x.device
-        d = torch.empty_like(x)
+        target, weight, sums, *steps = ctx.saved_tensors
+        s = len(steps)
+        n, c = steps[0].shape
+        dev = steps[0].device
+        lib = _lib.load()
+        d = torch.empty((s, n, c), dtype=torch.float32, device=dev)
         g = grad.contiguous().float()
-        _call.run(dev, _lib.load().mtmc_cross_entropy_backward,
-                  x.data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
-                  ctx.ignore_index, ctx.mode, g.data_ptr(), sums.data_ptr(), d.data_ptr(), _call.stream(dev))
-        return d, None, None, None, None
+        head = (steps[0].data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c)
+        tail = (ctx.ignore_index, ctx.mode, g.data_ptr(), sums.data_ptr(), d.data_ptr(), _call.stream(dev))
+        if s == 1:
+            _call.run(dev, lib.mtmc_cross_entropy_backward, *head, *tail)
+        else:
+            _call.run(dev, lib.mtmc_cross_entropy_steps_backward, *head, s, *tail)
+        return (None, None, None, None) + d.unbind(0)
 
 
 def cross_entropy(input, target, weight=None, reduction: str = "mean", ignore_index: int = -100):
@@ -137,36 +149,7 @@ def cross_entropy(input, target, weight=None, reduction: str = "mean", ignore_in
     if reduction not in _REDUCTIONS:
         raise ValueError(f"{reduction} is not a valid value for reduction")
     weight = _call.class_weight(weight, input.device, input.shape[1], "cross_entropy")
-    return _CrossEntropy.apply(input, target.contiguous().long(), weight, _REDUCTIONS[reduction], int(ignore_index))
-
-
-class _CrossEntropySteps(torch.autograd.Function):
-    """The classified steps of one forward are consecutive [E, C] slices of one block: one pass over all of them."""
-
-    @staticmethod
-    def forward(ctx, target, weight, mode, ignore_index, *steps):
-        n, c = steps[0].shape
-        dev = steps[0].device
-        sums = torch.empty(2 * _lib.STAT_REPLICAS, dtype=torch.float64, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        _call.run(dev, _lib.load().mtmc_cross_entropy_steps_forward,
-                  steps[0].data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
-                  len(steps), ignore_index, mode, sums.data_ptr(), loss.data_ptr(), _call.stream(dev))
-        ctx.save_for_backward(target, weight, sums, *steps)
-        ctx.mode, ctx.ignore_index = mode, ignore_index
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad):
-        target, weight, sums, *steps = ctx.saved_tensors
-        n, c = steps[0].shape
-        dev = steps[0].device
-        d = torch.empty((len(steps), n, c), dtype=torch.float32, device=dev)
-        g = grad.contiguous().float()
-        _call.run(dev, _lib.load().mtmc_cross_entropy_steps_backward,
-                  steps[0].data_ptr(), target.data_ptr(), weight.data_ptr() if weight is not None else None, n, c,
-                  len(steps), ctx.ignore_index, ctx.mode, g.data_ptr(), sums.data_ptr(), d.data_ptr(), _call.stream(dev))
-        return (None, None, None, None) + tuple(d[i] for i in range(len(steps)))
+    return _CrossEntropy.apply(target.contiguous().long(), weight, _REDUCTIONS[reduction], int(ignore_index), input)
 
 
 def cross_entropy_steps(steps, target, weight=None, reduction: str = "mean", ignore_index: int = -100):
@@ -185,7 +168,7 @@ def cross_entropy_steps(steps, target, weight=None, reduction: str = "mean", ign
     if not block or len(steps) == 1:
         return sum(cross_entropy(t, target, weight=weight, reduction=reduction, ignore_index=ignore_index) for t in steps)
     weight = _call.class_weight(weight, s0.device, s0.shape[1], "cross_entropy_steps")
-    return _CrossEntropySteps.apply(target.contiguous().long(), weight, _REDUCTIONS[reduction], int(ignore_index), *steps)
+    return _CrossEntropy.apply(target.contiguous().long(), weight, _REDUCTIONS[reduction], int(ignore_index), *steps)
 
 
 def edge_confusion(logits, labels):
@@ -205,43 +188,10 @@ EdgeLoss = collections.namedtuple("EdgeLoss", ["loss", "class_loss", "class_prob
 
 
 class _EdgeLoss(torch.autograd.Function):
-    """Consecutive [E, C] slices of one logits block, C in {1, 2}: 3 launches forward (memset, pass, finalize), 1 backward."""
-
-    @staticmethod
-    def forward(ctx, target, weight, mode, fpr_alpha, *steps):
-        n, c = steps[0].shape
-        s = len(steps)
-        dev = steps[0].device
-        lib = _lib.load()
-        nbytes = lib.mtmc_edge_loss_scratch_bytes(s)
-        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        record = torch.empty(_lib.EDGE_LOSS_RECORD, dtype=torch.float64, device=dev)
-        out = torch.empty(3 + 5 * s, dtype=torch.float32, device=dev)
-        confusion = torch.empty((s, 4), dtype=torch.int64, device=dev)
-        _call.run(dev, lib.mtmc_edge_loss_forward,
-                  steps[0].data_ptr(), target.data_ptr(), n, c, s, mode, weight.data_ptr() if weight is not None else None,
-                  fpr_alpha, scratch.data_ptr(), nbytes, record.data_ptr(), out.data_ptr(), confusion.data_ptr(), _call.stream(dev))
-        ctx.save_for_backward(target, record, *steps)
-        r = (out[0], out[3:3 + 2 * s].view(s, 2), out[3 + 2 * s:3 + 4 * s].view(s, 2), confusion, out[3 + 4 * s:], out[1:3])
-        ctx.mark_non_differentiable(*r[1:])
-        return r
-
-    @staticmethod
-    def backward(ctx, grad, *_unused):
-        target, record, *steps = ctx.saved_tensors
-        n, c = steps[0].shape
-        dev = steps[0].device
-        d = torch.empty((len(steps), n, c), dtype=torch.float32, device=dev)
-        g = grad.contiguous().float()
-        _call.run(dev, _lib.load().mtmc_edge_loss_backward,
-                  steps[0].data_ptr(), target.data_ptr(), n, c, len(steps), g.data_ptr(), record.data_ptr(), d.data_ptr(),
-                  _call.stream(dev))
-        return (None, None, None, None) + tuple(d[i] for i in range(len(steps)))
-
-
-class _EdgeFocal(torch.autograd.Function):
-    """_EdgeLoss with the row loss q^gamma * l (mtmc_edge_focal_*).  `rows`: one more output, the [S, E] weighted row
-    losses (one more launch), and THEY are what is differentiable, through the per-row backward; the loss is not then."""
+    """Consecutive [E, C] slices of one logits block, C in {1, 2}: 3 launches forward (memset, pass, finalize), 1 backward.
+    gamma = 0 without `rows` is mtmc_edge_loss_*; anything else mtmc_edge_focal_*, the row loss q^gamma * l.  `rows`: one
+    more output, the [S, E] weighted row losses (one more launch), and THEY are what is differentiable, through the per-row
+    backward; the loss is not then."""
 
     @staticmethod
     def forward(ctx, target, weight, mode, fpr_alpha, gamma, rows, *steps):
@@ -255,10 +205,13 @@ class _EdgeFocal(torch.autograd.Function):
         out = torch.empty(3 + 5 * s, dtype=torch.float32, device=dev)
         confusion = torch.empty((s, 4), dtype=torch.int64, device=dev)
         per_row = torch.empty((s, n), dtype=torch.float32, device=dev) if rows else None
-        _call.run(dev, lib.mtmc_edge_focal_forward,
-                  steps[0].data_ptr(), target.data_ptr(), n, c, s, mode, weight.data_ptr() if weight is not None else None,
-                  fpr_alpha, scratch.data_ptr(), nbytes, record.data_ptr(), out.data_ptr(), confusion.data_ptr(), gamma,
-                  per_row.data_ptr() if rows else None, _call.stream(dev))
+        args = (steps[0].data_ptr(), target.data_ptr(), n, c, s, mode, weight.data_ptr() if weight is not None else None,
+                fpr_alpha, scratch.data_ptr(), nbytes, record.data_ptr(), out.data_ptr(), confusion.data_ptr())
+        ctx.plain = gamma == 0.0 and not rows
+        if ctx.plain:
+            _call.run(dev, lib.mtmc_edge_loss_forward, *args, _call.stream(dev))
+        else:
+            _call.run(dev, lib.mtmc_edge_focal_forward, *args, gamma, per_row.data_ptr() if rows else None, _call.stream(dev))
         ctx.save_for_backward(target, record, *steps)
         ctx.gamma, ctx.rows = gamma, rows
         r = (out[0], out[3:3 + 2 * s].view(s, 2), out[3 + 2 * s:3 + 4 * s].view(s, 2), confusion, out[3 + 4 * s:], out[1:3])
@@ -273,12 +226,15 @@ class _EdgeFocal(torch.autograd.Function):
         target, record, *steps = ctx.saved_tensors
         n, c = steps[0].shape
         dev = steps[0].device
+        lib = _lib.load()
         d = torch.empty((len(steps), n, c), dtype=torch.float32, device=dev)
         g = (grads[6] if ctx.rows else grads[0]).contiguous().float()
-        _call.run(dev, _lib.load().mtmc_edge_focal_backward,
-                  steps[0].data_ptr(), target.data_ptr(), n, c, len(steps), g.data_ptr(), record.data_ptr(), d.data_ptr(),
-                  ctx.gamma, int(ctx.rows), _call.stream(dev))
-        return (None,) * 6 + tuple(d[i] for i in range(len(steps)))
+        args = (steps[0].data_ptr(), target.data_ptr(), n, c, len(steps), g.data_ptr(), record.data_ptr(), d.data_ptr())
+        if ctx.plain:
+            _call.run(dev, lib.mtmc_edge_loss_backward, *args, _call.stream(dev))
+        else:
+            _call.run(dev, lib.mtmc_edge_focal_backward, *args, ctx.gamma, int(ctx.rows), _call.stream(dev))
+        return (None,) * 6 + d.unbind(0)
 
 
 def _edge_loss(steps, labels, weight, pos_weight, fpr_alpha, gamma, rows):
@@ -313,10 +269,7 @@ def _edge_loss(steps, labels, weight, pos_weight, fpr_alpha, gamma, rows):
             raise ValueError(f"mtmc_mpn.edge_loss: {name} must have {2 if c == 2 else 1} element(s)")
     if not _call.steps_block(steps):
         steps = list(torch.stack(steps).unbind(0))           # autograd reaches the pieces through the stack
-    labels = labels.contiguous().long()
-    if gamma == 0.0 and not rows:
-        return _EdgeLoss.apply(labels, given, mode, float(fpr_alpha), *steps)
-    return _EdgeFocal.apply(labels, given, mode, float(fpr_alpha), gamma, rows, *steps)
+    return _EdgeLoss.apply(labels.contiguous().long(), given, mode, float(fpr_alpha), gamma, rows, *steps)
 
 
 def edge_loss(steps, labels, weight=None, pos_weight=None, fpr_alpha: float = 0.0, gamma: float = 0.0):

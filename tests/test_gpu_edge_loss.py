@@ -4,45 +4,19 @@ fused backward) against edge_loss_ref: torch's own losses in fp64 on the same in
 Bars: loss, class_loss, class_prob, fpr <= 2e-6 * max(1, |ref|); gradients <= 2e-6 * max|grad_ref| (the bars test_gpu_loss.py
 holds the same fp32 row arithmetic with fp64 sums to); confusion counts exactly."""
 import copy
-import types
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 import mtmc_mpn
+from edge_loss_cases import DEV, make_inputs, nodrop, one_logit_params, to_gpu, weight_modes
 from edge_loss_ref import edge_loss_ref
 from golden_util import ARCH
 from mtmc_mpn import graphs
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 BAR = 2e-6
-
-
-def make_inputs(e, s, c, seed, labels="mixed"):
-    """randn * 3 logits with exact ties (x0 == x1; x == 0) and rows at +-80 planted, nothing else within 1e-5 of a tie;
-    about 2 % positives with -100 rows interleaved, or one class only."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(s, e, c, generator=g) * 3
-    if c == 2:
-        d = x[..., 1] - x[..., 0]
-        x[..., 1] = torch.where((d.abs() < 1e-5), x[..., 0] + 1.0, x[..., 1])
-        x[:, 5::29] = torch.tensor([80.0, -80.0])
-        x[:, 7::31] = torch.tensor([-80.0, 80.0])
-        x[:, ::17, 1] = x[:, ::17, 0]
-    else:
-        x[x.abs() < 1e-5] = 1.0
-        x[:, 5::29] = 80.0
-        x[:, 7::31] = -80.0
-        x[:, ::17] = 0.0
-    if labels == "mixed":
-        y = (torch.rand(e, generator=g) < 0.02).long()
-        y[[i for i in (0, 5, 7) if i < e]] = 1              # positives on a tie, on a +80 and on a -80 row as well
-        y[3::41] = -100
-    else:
-        y = torch.full((e,), int(labels), dtype=torch.long)
-    return x, y
 
 
 def run_ours(x, y, up=1.7, separate=False, **kw):
@@ -83,12 +57,6 @@ def compare(r, grad, ref, ref_grad, tag):
     assert torch.isfinite(grad).all().item(), tag
     gerr = (grad.cpu().double() - ref_grad).abs().max().item()
     assert gerr <= BAR * ref_grad.abs().max().item(), f"{tag} grad: {gerr:.3e} vs max|grad| {ref_grad.abs().max().item():.3e}"
-
-
-def weight_modes(c):
-    if c == 2:
-        return [dict(), dict(weight=torch.tensor([0.7, 4.2], device=DEV)), dict(weight="balanced")]
-    return [dict(), dict(pos_weight=torch.tensor([4.2], device=DEV)), dict(pos_weight="balanced")]
 
 
 def check_all_modes(x, y, tag):
@@ -202,18 +170,6 @@ def test_refusals_on_device_tensors():
 
 
 # ---- on a model ------------------------------------------------------------------------------------------------------
-def to_gpu(d):
-    return types.SimpleNamespace(x=d.x.cuda(), edge_index=d.edge_index.cuda(), edge_attr=d.edge_attr.cuda())
-
-
-def nodrop(params):
-    p = copy.deepcopy(params)
-    p["encoder_feats_dict"]["nodes"][ARCH]["dropout_p"] = 0.0
-    p["edge_model_feats_dict"]["dropout_p"] = 0.0
-    p["node_model_feats_dict"]["dropout_p"] = 0.0
-    return p
-
-
 def test_balanced_loss_on_the_outputs_of_a_training_forward():
     """Parameter gradients through edge_loss(weight="balanced") == through cross_entropy(weight=w), w from the label counts
     read on the host (what a caller had to do before); same Dropout masks."""
@@ -238,12 +194,6 @@ def test_balanced_loss_on_the_outputs_of_a_training_forward():
     for k in grads[0][1]:
         a, b = grads[0][1][k], grads[1][1][k]
         assert (a - b).abs().max().item() <= 1e-5 * b.abs().max().item() + 1e-6, k
-
-
-def one_logit_params():
-    p = nodrop(mtmc_mpn.default_params(num_enc_steps=3, num_class_steps=3))
-    p["classifier_feats_dict"]["edge_out_dim"] = 1
-    return p
 
 
 def test_one_logit_model_eval_logits_against_the_oracle():

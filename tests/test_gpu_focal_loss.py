@@ -13,13 +13,12 @@ import pytest
 import torch
 
 import mtmc_mpn
+from edge_loss_cases import DEV, make_inputs, nodrop, one_logit_params, to_gpu, weight_modes
 from focal_ref import class_weights, focal_ref, focal_weighted_rows
 from golden_util import ARCH
 from mtmc_mpn import graphs
-from test_gpu_edge_loss import make_inputs, nodrop, one_logit_params, to_gpu, weight_modes
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 FLOOR = 2e-6
 FIELDS = ("loss", "class_loss", "class_prob", "fpr", "class_weight")
 GAMMAS = (0.5, 1.0, 2.0, 5.0)
@@ -226,11 +225,8 @@ def bar_rows(x, y, gamma, want, **kw):
     return max(FLOOR, 4 * ((rows.double() - want).abs() / want.abs().clamp(min=1.0)).max().item())
 
 
-@pytest.mark.parametrize("c", [2, 1])
-@pytest.mark.parametrize("gamma", [2.0, 5.0])
-def test_focal_loss_reductions(gamma, c):
-    x, y = make_inputs(20011, 1, c, seed=71 + c)
-    x = x[0]
+def check_reductions(x, y, gamma, c):
+    """focal_loss "mean" against edge_loss, "none" and "sum" with their gradients (the per-row backward) against focal_ref."""
     xd, yd = x.to(DEV), y.to(DEV)
     for kw in weight_modes(c):
         cpu_kw = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in kw.items()}
@@ -259,6 +255,21 @@ def test_focal_loss_reductions(gamma, c):
         xr2 = x.double().requires_grad_(True)
         focal_weighted_rows(xr2, y, gamma, **cpu_kw).sum().backward()
         assert (xs.grad.cpu().double() - xr2.grad).abs().max().item() <= bar * xr2.grad.abs().max().item()
+
+
+@pytest.mark.parametrize("c", [2, 1])
+@pytest.mark.parametrize("gamma", [2.0, 5.0])
+def test_focal_loss_reductions(gamma, c):
+    x, y = make_inputs(20011, 1, c, seed=71 + c)
+    check_reductions(x[0], y, gamma, c)
+
+
+@pytest.mark.parametrize("c", [2, 1])
+@pytest.mark.parametrize("e", [1, 63, 257])
+def test_focal_loss_reductions_at_wave_and_workgroup_edges(e, c):
+    """The rows kernel and the per-row backward on one row, just under one wave, and one row past a workgroup."""
+    x, y = make_inputs(e, 1, c, seed=71 + 10 * e + c)
+    check_reductions(x[0], y, 2.0, c)
 
 
 def test_focal_loss_module():
