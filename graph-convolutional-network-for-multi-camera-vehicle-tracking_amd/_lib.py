@@ -2,12 +2,15 @@
 
 The library is built in-tree (`python -m mtmc_mpn.build`, or `__graft_entry__.build()`).  If it is
 missing, loading fails loudly: there is no other implementation behind the module.
+Everything here mirrors the header by hand; tests/test_abi_exports.py parses the header and compares the
+constants and every entry of SIGNATURES with it.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 
+ABI_VERSION = 6
 MAX_ENC_LAYERS = 8
 NODE_DIM, EDGE_DIM, MAX_CLASSES = 32, 4, 4
 AGG = {"sum": 0, "mean": 1, "max": 2}
@@ -85,20 +88,66 @@ POOL_INFO = 4                                             # mtmc_pool_tracklets:
 
 # MTMC_MPN_LIB: another build of the same ABI (same-box A/B of two library versions, tools/lib_ab.sh); default: the in-tree build
 LIB_PATH = os.environ.get("MTMC_MPN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmtmc_mpn.so")
-EXPORTS = ["mtmc_mpn_abi_version", "mtmc_mpn_last_error", "mtmc_mpn_workspace_bytes", "mtmc_mpn_workspace_layout",
-           "mtmc_mpn_forward", "mtmc_mpn_run_phase", "mtmc_mpn_run_phases", "mtmc_mpn_plan_call", "mtmc_scatter_add", "mtmc_scatter_add_i64", "mtmc_scatter_mean", "mtmc_scatter_max",
-           "mtmc_mlp_layer_forward", "mtmc_mpn_train_workspace_bytes", "mtmc_mpn_backward", "mtmc_graph_workspace_bytes",
-           "mtmc_build_graph", "mtmc_postprocess_workspace_bytes", "mtmc_postprocess",
-           "mtmc_cross_entropy_forward", "mtmc_cross_entropy_backward",
-           "mtmc_cross_entropy_steps_forward", "mtmc_cross_entropy_steps_backward", "mtmc_mpn_backward_steps", "mtmc_mpn_backward_flat", "mtmc_mpn_grad_layout", "mtmc_linear_raw", "mtmc_edge_confusion",
-           "mtmc_linear_presplit_raw", "mtmc_linear_staged_raw", "mtmc_linear_few_raw", "mtmc_mpn_weight_cache_bytes",
-           "mtmc_graph_backward_workspace_bytes", "mtmc_build_graph_backward",
-           "mtmc_edge_loss_scratch_bytes", "mtmc_edge_loss_forward", "mtmc_edge_loss_backward",
-           "mtmc_edge_focal_forward", "mtmc_edge_focal_backward",
-           "mtmc_cluster_scores_workspace_bytes", "mtmc_cluster_scores", "mtmc_edge_prf",
-           "mtmc_pool_chunk_rows", "mtmc_pool_tracklets_workspace_bytes", "mtmc_pool_tracklets", "mtmc_pool_tracklets_backward",
-           "mtmc_scatter_add_backward", "mtmc_scatter_mean_backward", "mtmc_scatter_max_backward",
-           "mtmc_graph_knn_workspace_bytes", "mtmc_build_graph_knn"]
+
+# Every entry point of the header: name -> (return type, argument types), in the header's order.  A pointer to one of the
+# structs above is typed as such; every other pointer (device or host memory, a stream) is a c_void_p.
+_p, _i32, _i64, _sz, _u64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_uint64, C.c_float, C.c_double
+_Layer, _Model, _Call, _WsLayout, _Plan = (C.POINTER(s) for s in (Layer, Model, Call, WsLayout, Plan))
+_graph_head = [_p, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _i32, _i64]     # feats ... max_edges of the build_graph family
+SIGNATURES = {
+    "mtmc_mpn_abi_version": (_i32, []),
+    "mtmc_mpn_last_error": (C.c_char_p, []),
+    "mtmc_mpn_workspace_bytes": (_sz, [_Model, _i64, _i64]),
+    "mtmc_mpn_weight_cache_bytes": (_sz, [_Model]),
+    "mtmc_mpn_workspace_layout": (_i32, [_Model, _i64, _i64, _WsLayout]),
+    "mtmc_mpn_forward": (_i32, [_Model, _Call]),
+    "mtmc_mpn_train_workspace_bytes": (_sz, [_Model, _i64, _i64]),
+    "mtmc_mpn_backward": (_i32, [_Model, _Call, _p, _p, _Model, _p, _p]),
+    "mtmc_mpn_backward_steps": (_i32, [_Model, _Call, _p, _p, _Model, _p, _sz, _p, _p]),
+    "mtmc_mpn_grad_layout": (_i64, [_Model, _p, _i32]),
+    "mtmc_mpn_backward_flat": (_i32, [_Model, _Call, _p, _p, _p, _i64, _p, _p]),
+    "mtmc_mpn_run_phase": (_i32, [_Model, _Call, _i32, _i32]),
+    "mtmc_mpn_run_phases": (_i32, [_Model, _Call, _p, _i32]),
+    "mtmc_mpn_plan_call": (_i32, [_Model, _Call, _Plan]),
+    "mtmc_scatter_add": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p]),
+    "mtmc_scatter_add_i64": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p]),
+    "mtmc_scatter_mean": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "mtmc_scatter_max": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "mtmc_scatter_add_backward": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p]),
+    "mtmc_scatter_mean_backward": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "mtmc_scatter_max_backward": (_i32, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "mtmc_mlp_layer_forward": (_i32, [_Layer, _p, _i64, _i64, _p, _p, _p]),
+    "mtmc_linear_raw": (_i32, [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
+    "mtmc_linear_few_raw": (_i32, [_p, _i64, _p, _p, _p, _f64, _p, _p, _p, _i64, _i32, _i32, _p, _u64, _p, _p]),
+    "mtmc_linear_staged_raw": (_i32, [_p, _i64, _p, _p, _p, _f64, _p, _p, _p, _i64, _i32, _i32, _p, _u64, _p, _p, _p]),
+    "mtmc_linear_presplit_raw": (_i32, [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _u64, _p, _p, _i32, _p]),
+    "mtmc_graph_workspace_bytes": (_sz, [_i64, _i32]),
+    "mtmc_build_graph": (_i32, _graph_head + [_p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mtmc_graph_knn_workspace_bytes": (_sz, [_i64, _i32]),
+    "mtmc_build_graph_knn": (_i32, _graph_head + [_p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _sz, _p]),
+    "mtmc_graph_backward_workspace_bytes": (_sz, [_i64, _i32]),
+    "mtmc_build_graph_backward": (_i32, _graph_head + [_p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mtmc_cross_entropy_forward": (_i32, [_p, _p, _p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
+    "mtmc_cross_entropy_backward": (_i32, [_p, _p, _p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
+    "mtmc_cross_entropy_steps_forward": (_i32, [_p, _p, _p, _i64, _i32, _i32, _i64, _i32, _p, _p, _p]),
+    "mtmc_cross_entropy_steps_backward": (_i32, [_p, _p, _p, _i64, _i32, _i32, _i64, _i32, _p, _p, _p, _p]),
+    "mtmc_edge_confusion": (_i32, [_p, _p, _i64, _i32, _p, _p]),
+    "mtmc_edge_loss_scratch_bytes": (_sz, [_i32]),
+    "mtmc_edge_loss_forward": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _f32, _p, _sz, _p, _p, _p, _p]),
+    "mtmc_edge_loss_backward": (_i32, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
+    "mtmc_edge_focal_forward": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _f32, _p, _sz, _p, _p, _p, _f32, _p, _p]),
+    "mtmc_edge_focal_backward": (_i32, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _f32, _i32, _p]),
+    "mtmc_postprocess_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "mtmc_postprocess": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "mtmc_cluster_scores_workspace_bytes": (_sz, [_i64]),
+    "mtmc_cluster_scores": (_i32, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "mtmc_edge_prf": (_i32, [_p, _i64, _p, _i64, _i64, _p, _p, _p]),
+    "mtmc_pool_chunk_rows": (_i32, []),
+    "mtmc_pool_tracklets_workspace_bytes": (_sz, [_i64, _i32]),
+    "mtmc_pool_tracklets": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _sz, _p]),
+    "mtmc_pool_tracklets_backward": (_i32, [_p, _i64, _i32, _p, _i64, _p, _i64, _p]),
+}
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
@@ -113,134 +162,10 @@ def load() -> C.CDLL:
                            "-- there is no fallback implementation")
     import torch  # noqa: F401  (loads the ROCm runtime the library links against)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    lib.mtmc_mpn_abi_version.restype = C.c_int32
-    lib.mtmc_mpn_last_error.restype = C.c_char_p
-    lib.mtmc_mpn_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_mpn_workspace_bytes.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64]
-    lib.mtmc_mpn_weight_cache_bytes.restype = C.c_size_t
-    lib.mtmc_mpn_weight_cache_bytes.argtypes = [C.POINTER(Model)]
-    lib.mtmc_linear_few_raw.restype = C.c_int32
-    lib.mtmc_linear_few_raw.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64,
-                                        C.c_void_p, C.c_void_p]
-    lib.mtmc_mpn_workspace_layout.restype = C.c_int32
-    lib.mtmc_mpn_workspace_layout.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64, C.POINTER(WsLayout)]
-    lib.mtmc_mpn_forward.restype = C.c_int32
-    lib.mtmc_mpn_forward.argtypes = [C.POINTER(Model), C.POINTER(Call)]
-    lib.mtmc_mpn_train_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_mpn_train_workspace_bytes.argtypes = [C.POINTER(Model), C.c_int64, C.c_int64]
-    lib.mtmc_mpn_backward.restype = C.c_int32
-    lib.mtmc_mpn_backward.argtypes = [C.POINTER(Model), C.POINTER(Call), C.c_void_p, C.c_void_p, C.POINTER(Model),
-                                      C.c_void_p, C.c_void_p]
-    lib.mtmc_graph_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_graph_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-    lib.mtmc_build_graph.restype = C.c_int32
-    lib.mtmc_build_graph.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
-        [C.c_int32, C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
-    lib.mtmc_graph_knn_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_graph_knn_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-    lib.mtmc_build_graph_knn.restype = C.c_int32
-    lib.mtmc_build_graph_knn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
-        [C.c_int32, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_int64] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
-    lib.mtmc_graph_backward_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_graph_backward_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-    lib.mtmc_build_graph_backward.restype = C.c_int32
-    lib.mtmc_build_graph_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
-        [C.c_int32, C.c_int64] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
-    lib.mtmc_mpn_backward_steps.restype = C.c_int32
-    lib.mtmc_mpn_backward_steps.argtypes = [C.POINTER(Model), C.POINTER(Call), C.POINTER(C.c_void_p), C.c_void_p,
-                                            C.POINTER(Model), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.mtmc_mpn_backward_flat.restype = C.c_int32
-    lib.mtmc_mpn_backward_flat.argtypes = [C.POINTER(Model), C.POINTER(Call), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
-                                           C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mtmc_mpn_grad_layout.restype = C.c_int64
-    lib.mtmc_mpn_grad_layout.argtypes = [C.POINTER(Model), C.POINTER(C.c_int64), C.c_int32]
-    lib.mtmc_edge_confusion.restype = C.c_int32
-    lib.mtmc_edge_confusion.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.mtmc_linear_presplit_raw.restype = C.c_int32
-    lib.mtmc_linear_presplit_raw.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                             C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mtmc_linear_staged_raw.restype = C.c_int32
-    lib.mtmc_linear_staged_raw.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_linear_raw.restype = C.c_int32
-    lib.mtmc_linear_raw.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_cross_entropy_forward.restype = C.c_int32
-    lib.mtmc_cross_entropy_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
-                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_cross_entropy_backward.restype = C.c_int32
-    lib.mtmc_cross_entropy_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
-                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_cross_entropy_steps_forward.restype = C.c_int32
-    lib.mtmc_cross_entropy_steps_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
-                                                     C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_cross_entropy_steps_backward.restype = C.c_int32
-    lib.mtmc_cross_entropy_steps_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
-                                                      C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_edge_loss_scratch_bytes.restype = C.c_size_t
-    lib.mtmc_edge_loss_scratch_bytes.argtypes = [C.c_int32]
-    lib.mtmc_edge_loss_forward.restype = C.c_int32
-    lib.mtmc_edge_loss_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                           C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_edge_loss_backward.restype = C.c_int32
-    lib.mtmc_edge_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p]
-    lib.mtmc_edge_focal_forward.restype = C.c_int32              # mtmc_edge_loss_forward's arguments, then gamma and per_row
-    lib.mtmc_edge_focal_forward.argtypes = lib.mtmc_edge_loss_forward.argtypes[:-1] + [C.c_float, C.c_void_p, C.c_void_p]
-    lib.mtmc_edge_focal_backward.restype = C.c_int32             # ... then gamma and grad_per_row
-    lib.mtmc_edge_focal_backward.argtypes = lib.mtmc_edge_loss_backward.argtypes[:-1] + [C.c_float, C.c_int32, C.c_void_p]
-    lib.mtmc_cluster_scores_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_cluster_scores_workspace_bytes.argtypes = [C.c_int64]
-    lib.mtmc_cluster_scores.restype = C.c_int32
-    lib.mtmc_cluster_scores.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.mtmc_edge_prf.restype = C.c_int32
-    lib.mtmc_edge_prf.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mtmc_pool_chunk_rows.restype = C.c_int32
-    lib.mtmc_pool_chunk_rows.argtypes = []
-    lib.mtmc_pool_tracklets_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_pool_tracklets_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-    lib.mtmc_pool_tracklets.restype = C.c_int32
-    lib.mtmc_pool_tracklets.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.mtmc_pool_tracklets_backward.restype = C.c_int32
-    lib.mtmc_pool_tracklets_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                                 C.c_int64, C.c_void_p]
-    lib.mtmc_postprocess_workspace_bytes.restype = C.c_size_t
-    lib.mtmc_postprocess_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
-    lib.mtmc_postprocess.restype = C.c_int32
-    lib.mtmc_postprocess.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
-                                     C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_size_t, C.c_void_p]
-    lib.mtmc_mpn_plan_call.restype = C.c_int32
-    lib.mtmc_mpn_plan_call.argtypes = [C.POINTER(Model), C.POINTER(Call), C.POINTER(Plan)]
-    lib.mtmc_mpn_run_phase.restype = C.c_int32
-    lib.mtmc_mpn_run_phase.argtypes = [C.POINTER(Model), C.POINTER(Call), C.c_int32, C.c_int32]
-    lib.mtmc_mpn_run_phases.restype = C.c_int32
-    lib.mtmc_mpn_run_phases.argtypes = [C.POINTER(Model), C.POINTER(Call), C.POINTER(C.c_int32), C.c_int32]
-    for name in ("mtmc_scatter_add", "mtmc_scatter_add_i64"):
-        getattr(lib, name).restype = C.c_int32
-        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mtmc_scatter_mean.restype = C.c_int32
-    lib.mtmc_scatter_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                      C.c_void_p]
-    lib.mtmc_scatter_max.restype = C.c_int32
-    lib.mtmc_scatter_max.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                     C.c_void_p]
-    lib.mtmc_scatter_add_backward.restype = C.c_int32
-    lib.mtmc_scatter_add_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.mtmc_scatter_mean_backward.restype = C.c_int32
-    lib.mtmc_scatter_mean_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                               C.c_void_p]
-    lib.mtmc_scatter_max_backward.restype = C.c_int32
-    lib.mtmc_scatter_max_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                              C.c_void_p]
-    lib.mtmc_mlp_layer_forward.restype = C.c_int32
-    lib.mtmc_mlp_layer_forward.argtypes = [C.POINTER(Layer), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                           C.c_void_p]
-    if lib.mtmc_mpn_abi_version() != 6:
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if lib.mtmc_mpn_abi_version() != ABI_VERSION:
         raise RuntimeError("mtmc_mpn: ABI version mismatch between _lib.py and libmtmc_mpn.so")
     _lib = lib
     return lib

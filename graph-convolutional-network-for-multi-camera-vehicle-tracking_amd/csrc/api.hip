@@ -1,7 +1,14 @@
-// C-ABI layer (include/mtmc_mpn.h): argument checking, workspace carving and the phase sequence of one
-// MOTMPNet.forward (reference models/mpn.py:250-299).  Launch-only: nothing here allocates or synchronises,
-// so a caller may capture a forward into a hipGraph.
+// C-ABI layer (include/mtmc_mpn.h), the forward: the sizing and layout queries, the per-phase parameter blocks and launches,
+// and the phase sequence of one MOTMPNet.forward (reference models/mpn.py:250-299).  Launch-only: nothing here allocates or
+// synchronises, so a caller may capture a forward into a hipGraph.
 #include "api_internal.h"
+
+#include <mutex>
+
+namespace mtmc_api {
+// Side stream + events of the pipelined layer 0 (Ctx::pipe; pipe_for below)
+struct SidePipe { hipStream_t stream = nullptr; hipEvent_t fork = nullptr; hipEvent_t ready[kMaxPanels] = {}; };
+}  // namespace mtmc_api
 
 using namespace mtmc_api;
 
@@ -58,6 +65,303 @@ SidePipe* pipe_for(hipStream_t caller) {
     if (hipEventCreateWithFlags(&sp.ready[i], hipEventDisableTiming) != hipSuccess) { destroy_pipe(sp, i); return nullptr; }
   slots[n_slots] = {dev, caller, sp};
   return &slots[n_slots++].pipe;
+}
+
+// Diagnostics (bench.py): HIP events around every layer-0 GEMM launch of a many-row forward -- in the pipelined forward the
+// layer is several panel launches beside the operand split on a side stream, and the figure a bench line reports must be
+// that of the forward it sits beside.  Off by default; mtmc_dbg_panel_timing / mtmc_dbg_panel_times below.
+struct PanelTiming { bool on = false, created = false; hipEvent_t ev[2 * kMaxPanels]; int n = 0; };
+PanelTiming& panel_timing() { static PanelTiming t; return t; }
+
+enum { kPhMemset = -1, kPhPrep = -2 };   // the two halves of MTMC_PH_BEGIN, for the forked forward
+
+// the edge part of prep_kernel for this call
+void fill_prep_edge(const Ctx& x, mtmc::PrepEdge* p) {
+  const mtmc_mpn_call* c = x.c;
+  p->row = c->row; p->col = c->col; p->idx_stride = c->idx_stride; p->attr = c->edge_attr; p->fe = x.m->enc_edge[0].in_dim;
+  p->n_edges = c->n_edges; p->n_nodes = c->n_nodes;
+  p->row32 = x.at<int>(x.lo.row32); p->col32 = x.at<int>(x.lo.col32); p->deg = x.at<int>(x.lo.pub.deg_off);
+  p->flags = x.at<int>(x.lo.pub.flags_off); p->stat_attr = x.at<double>(x.lo.pub.stat_attr_off);
+  p->row_start = x.at<int>(x.lo.row_start);
+}
+
+const int* scale_deg(const Ctx& x) {   // the degree mean aggregation divides by
+  return x.at<int>((x.c->flags & MTMC_F_GLOBAL_DEG) ? x.lo.pub.deg_global_off : x.lo.pub.deg_off);
+}
+
+// The parts of node-encoder layer l's parameter block (kernels.h), each filled from the call in one place.
+// Input: x for layer 0, else the previous layer's raw Y with its statistics, BatchNorm and Dropout
+void fill_in(const Ctx& x, int l, mtmc::ActIn* q) {
+  if (l == 0) {
+    q->A = x.c->x; q->lda = x.c->x_row_stride;
+  } else {
+    const mtmc_layer& Pv = x.m->enc_node[l - 1];
+    q->A = x.at<float>(x.lo.Y[l - 1]); q->lda = Pv.out_dim;
+    q->stats_in = x.at<double>(x.lo.pub.stat_enc_layer_off[l - 1]); q->gamma_in = Pv.gamma; q->beta_in = Pv.beta;
+  }
+  q->count = (double)x.c->n_nodes;
+  q->drop_in = make_drop(x, x.m->dropout_enc); q->drop_stream = mtmc::kDropEncNode + l - 1;
+}
+void fill_out(const Ctx& x, int l, mtmc::LayerOut* q) {
+  const mtmc_layer& Lr = x.m->enc_node[l];
+  q->bias = Lr.bias; q->Y = x.at<float>(x.lo.Y[l]); q->ldy = Lr.out_dim;
+  q->stats_out = x.at<double>(x.lo.pub.stat_enc_layer_off[l]); q->amax_y = amax_y(x, l);
+  q->M = x.plan.rows; q->K = Lr.in_dim; q->Nout = Lr.out_dim;
+}
+void fill_w(const Ctx& x, int l, mtmc::PlanesW* q) { q->Wh = w_planes(x, l); q->inv_w = w_inv(x, l); }
+void fill_x(const Ctx& x, mtmc::PlanesA* q) { q->Ah = x.at<_Float16>(x.lo.xh); q->inv_a = x.at<float>(x.lo.inv_a); }
+// MTMC_PH_EDGE_ENC's work as passenger workgroups of the last encoder layer's launch
+void ride_enc2(const Ctx& x, mtmc::Enc2Ride* q) {
+  const int64_t blocks = (x.c->n_edges + 255) / 256;
+  q->pass_blocks = (int)(blocks > 2048 ? 2048 : blocks);
+  q->pass_enc = enc_params(x); q->pass_attr = x.c->edge_attr; q->pass_edges = x.c->n_edges;
+  q->pass_e_total = (double)x.c->n_edges_total; q->pass_stat = x.at<double>(x.lo.pub.stat_enc2_off);
+}
+
+// The node-encoder layer launches of MTMC_PH_NODE_ENC, one per form of CallPlan::enc_kernel.  A launcher's refusal
+// (kernels.h: MTMC_E_ARG or MTMC_E_HIP) is the phase's code.
+// Few-row graphs (gemm_few.hip): one launch per layer, never split along K.
+int launch_enc_few(const Ctx& x, int l) {
+  int rc;
+  if (l == 0) {
+    mtmc::FewL0Params q;
+    fill_x(x, &q); fill_w(x, 0, &q); fill_out(x, 0, &q);
+    rc = mtmc::launch_few_l0(q, x.stream);
+  } else {
+    mtmc::FewWaveParams q;
+    fill_in(x, l, &q); fill_w(x, l, &q); fill_out(x, l, &q);
+    if (x.enc2_rides && l == x.m->n_enc_layers - 1) ride_enc2(x, &q);
+    rc = mtmc::launch_few_wave(q, x.stream);
+  }
+  if (rc) return fail(rc, "encoder layer %d: few-row kernel refused the shape or the launch", l);
+  return MTMC_OK;
+}
+
+// Many-row graphs, layer 0 on the operand planes made in MTMC_PH_BEGIN -- or, in the pipelined forward (x.pipe), in row panels.
+int launch_enc_presplit0(const Ctx& x) {
+  const mtmc_mpn_call* c = x.c;
+  const mtmc_layer& Lr = x.m->enc_node[0];
+  const int64_t rows = x.plan.rows;
+  hipStream_t s = x.stream;
+  mtmc::SplitGemmParams q;
+  fill_x(x, &q); fill_w(x, 0, &q); fill_out(x, 0, &q);
+  PanelTiming& pt = panel_timing();
+  if (x.pipe) {
+    // Row panels: the side stream splits panel after panel (HBM-bound), the main stream multiplies panel i as soon as
+    // its planes are there (matrix-bound): the split pass leaves the critical path except for the first panel.
+    // Panel = whole rounds of workgroups of the tile height the whole matrix would get, so no round is paid twice.
+    const int np = x.plan.l0_panels;
+    const int64_t* cuts = x.plan.l0_cuts;
+    q.bm = x.plan.l0_bm;
+    q.M_rows = rows;
+    if (hipEventRecord(x.pipe->fork, s) != hipSuccess || hipStreamWaitEvent(x.pipe->stream, x.pipe->fork, 0) != hipSuccess)
+      return fail(MTMC_E_HIP, "encoder layer 0: fork onto the side stream failed");
+    // from here on the side stream is forked off `s` (inside a capture: part of it): every way out joins it again
+    auto join_and = [&](int code, const char* what) {
+      if (hipEventRecord(x.pipe->ready[0], x.pipe->stream) == hipSuccess) (void)hipStreamWaitEvent(s, x.pipe->ready[0], 0);
+      return fail(code, "%s", what);
+    };
+    for (int i = 0; i < np; ++i) {
+      mtmc::launch_split_rows_range(c->x, c->x_row_stride, rows, Lr.in_dim, x.at<void>(x.lo.xh), x.at<float>(x.lo.inv_a),
+                                    cuts[i], cuts[i + 1], x.pipe->stream);
+      if (hipEventRecord(x.pipe->ready[i], x.pipe->stream) != hipSuccess) return join_and(MTMC_E_HIP, "hipEventRecord failed");
+    }
+    if (pt.on) pt.n = 0;
+    for (int i = 0; i < np; ++i) {               // (the wait on the last panel's event also joins the side stream)
+      if (hipStreamWaitEvent(s, x.pipe->ready[i], 0) != hipSuccess) return join_and(MTMC_E_HIP, "hipStreamWaitEvent failed");
+      q.m_lo = cuts[i]; q.M = cuts[i + 1];
+      if (pt.on) (void)hipEventRecord(pt.ev[2 * i], s);
+      const int rc = mtmc::launch_gemm_presplit(q, s);
+      if (pt.on) { (void)hipEventRecord(pt.ev[2 * i + 1], s); pt.n = i + 1; }
+      if (rc) return join_and(rc, "encoder layer 0: pre-split GEMM refused a panel");
+    }
+    return MTMC_OK;
+  }
+  if (pt.on) { pt.n = 0; (void)hipEventRecord(pt.ev[0], s); }
+  const int rc = mtmc::launch_gemm_presplit(q, s);
+  if (pt.on) { (void)hipEventRecord(pt.ev[1], s); pt.n = 1; }
+  if (rc) return fail(rc, "encoder layer 0: pre-split GEMM refused the shape or the launch");
+  return MTMC_OK;
+}
+
+// Many-row graphs, layers >= 1 on the role-split kernel (gemm_staged.hip).
+int launch_enc_staged(const Ctx& x, int l) {
+  mtmc::StagedGemmParams q;
+  fill_in(x, l, &q); fill_w(x, l, &q); fill_out(x, l, &q);
+  q.amax_a = amax_in(x, l);
+  if (int rc = mtmc::launch_gemm_staged(q, x.stream))
+    return fail(rc, "encoder layer %d: role-split GEMM refused the shape or the launch", l);
+  return MTMC_OK;
+}
+
+// The in-loop operand split (gemm_bn.hip; MTMC_PH_NODE_COMBINE adds up the slab's K slices), or the row-streaming kernel
+// (gemm_rows.hip) of the narrow last layers of many-row graphs.
+int launch_enc_gemm(const Ctx& x, int l, int phase) {
+  mtmc::GemmParams g;
+  fill_in(x, l, &g); fill_out(x, l, &g);
+  g.W = x.m->enc_node[l].weight; g.amax_a = amax_in(x, l); g.amax_w = amax_w(x, l);
+  if (x.enc2_rides && phase == MTMC_PH_NODE_ENC && l == x.m->n_enc_layers - 1) ride_enc2(x, &g);
+  if (x.plan.enc_kernel[l] == MTMC_GEMM_ROWS_16) {
+    if (int rc = mtmc::launch_gemm_rows(g, x.stream)) return fail(rc, "encoder layer %d: row-streaming GEMM refused the shape", l);
+    return MTMC_OK;
+  }
+  if (x.plan.enc_split_k[l] > 1) g.slab = x.at<float>(x.lo.slab);
+  if (int rc = mtmc::launch_gemm_bn(g, x.stream, phase == MTMC_PH_NODE_ENC ? 1 : 2))
+    return fail(rc, "encoder layer %d: unsupported GEMM shape", l);
+  return MTMC_OK;
+}
+
+int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
+  const mtmc_mpn_model* m = x.m;
+  const mtmc_mpn_call* c = x.c;
+  const int L = m->num_enc_steps;
+  hipStream_t s = x.stream;
+  switch (phase) {
+    case MTMC_PH_BEGIN:
+    case kPhMemset:
+    case kPhPrep: {
+      // What depends on the WEIGHTS alone -- the fp16 planes + row scales of the layers that run on pre-split weights -- lives in
+      // the call's weight-plane cache when it has one and is VERIFIED here on every call, chunk by chunk, by passenger
+      // workgroups of prep_kernel (split_body.h); without a cache it is made per call in the workspace.
+      if (phase != kPhPrep && hipMemsetAsync(x.ws, 0, x.lo.pub.zero_bytes, s) != hipSuccess)
+        return fail(MTMC_E_HIP, "hipMemsetAsync failed");
+      if (phase != kPhPrep && c->training && (c->flags & MTMC_F_SEED_ON_DEVICE))      // seed word <- counter++ (one thread)
+        mtmc::launch_seed_tick(reinterpret_cast<unsigned long long*>((uintptr_t)c->seed), x.at<unsigned long long>(x.lo.seed_word), s);
+      if (phase != kPhMemset) {
+        const CallPlan& pl = x.plan;
+        const int64_t rows = pl.rows;
+        mtmc::PrepParams p;
+        fill_prep_edge(x, &p);
+        // passenger jobs: operand |.|max values / operand splits of the node encoder (this rank's rows of x; the weights)
+        p.n_jobs = 0;
+        // (training forwards: the jobs also publish the tensors' |.|max -- the backward's GEMMs scale by |x|max and |W_l|max)
+        if (rows > 0) {
+          if (pl.enc_kernel[0] == MTMC_GEMM_FEW_L0)     // the planes of x, 8 rows per passenger workgroup (no |x|max: one scale per row)
+            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, c->training ? amax_x(x) : nullptr, 0, 0, mtmc::kJobSplit,
+                                  x.at<_Float16>(x.lo.xh), x.at<float>(x.lo.inv_a), nullptr};
+          else if (pl.enc_kernel[0] != MTMC_GEMM_PRESPLIT_256)
+            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, amax_x(x), 0, 0, mtmc::kJobAmax, nullptr, nullptr, nullptr};
+          for (int l = 0; l < m->n_enc_layers; ++l) {
+            const mtmc_layer& Ll = m->enc_node[l];
+            if (pl.w_cached[l])         // layer l's planes in the cache: verify every 8-row chunk, split the ones that changed
+              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, c->training ? amax_w(x, l) : nullptr, 0, 0,
+                                    mtmc::kJobSplit, x.wc_at<_Float16>(x.cl.planes[l]), x.wc_at<float>(x.cl.inv[l]),
+                                    x.wc_at<unsigned long long>(x.cl.fp[l])};
+            else if (in_loop_kernel(pl.enc_kernel[l]))   // |W_l|max (row-streaming: in the kernel; planes without a cache: below)
+              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, amax_w(x, l), 0, 0, mtmc::kJobAmax,
+                                    nullptr, nullptr, nullptr};
+          }
+        }
+        mtmc::launch_prep(p, s);
+        if (pl.col_blocks > 0) {        // sub-run boundaries of the column-blocked pass A, once per forward
+          const mtmc::RoundParams rp = round_params(x, 0);
+          mtmc::launch_colblock_index(rp, x.at<int>(x.lo.col_sub), rp.col_blocks, rp.cb_row_lo, rp.cb_row_hi, s);
+        }
+        // instead of the |.|max of x and W0: their fp16 planes and row scales
+        // (pipelined layer 0: the x planes are made panel by panel in MTMC_PH_NODE_ENC 0)
+        if (pl.enc_kernel[0] == MTMC_GEMM_PRESPLIT_256 && !x.pipe)
+          mtmc::launch_split_rows(c->x, c->x_row_stride, rows, m->enc_node[0].in_dim, x.at<void>(x.lo.xh),
+                                  x.at<float>(x.lo.inv_a), s);
+        for (int l = 0; l < m->n_enc_layers; ++l) {     // the weight planes of the layers whose kernels want them, unless cached
+          const mtmc_layer& Ll = m->enc_node[l];
+          if ((pl.enc_kernel[l] == MTMC_GEMM_PRESPLIT_256 || pl.enc_kernel[l] == MTMC_GEMM_STAGED_128) && !pl.w_cached[l])
+            mtmc::launch_split_rows(Ll.weight, Ll.in_dim, Ll.out_dim, Ll.in_dim, w_planes(x, l), w_inv(x, l), s);
+        }
+      }
+      break;
+    }
+    case MTMC_PH_EDGE_ENC:
+      if (c->n_edges > 0)
+        mtmc::launch_enc2(enc_params(x), c->edge_attr, c->n_edges, (double)c->n_edges_total, x.at<double>(x.lo.pub.stat_enc2_off), s);
+      break;
+    case MTMC_PH_NODE_ENC:
+    case MTMC_PH_NODE_COMBINE: {
+      if (arg < 0 || arg >= m->n_enc_layers) return fail(MTMC_E_ARG, "encoder layer %d out of range", arg);
+      if (x.plan.rows == 0) break;
+      const int k = x.plan.enc_kernel[arg];
+      if (phase == MTMC_PH_NODE_COMBINE && !in_loop_kernel(k)) break;   // only the in-loop kernel splits along K
+      int rc;
+      if (k == MTMC_GEMM_FEW_L0 || k == MTMC_GEMM_FEW_WAVE) rc = launch_enc_few(x, arg);
+      else if (k == MTMC_GEMM_PRESPLIT_256) rc = launch_enc_presplit0(x);
+      else if (k == MTMC_GEMM_STAGED_128) rc = launch_enc_staged(x, arg);
+      else rc = launch_enc_gemm(x, arg, phase);
+      if (rc) return rc;
+      break;
+    }
+    case MTMC_PH_NODE_H0: {
+      const int last = m->n_enc_layers - 1;
+      const int64_t rows = c->node_hi - c->node_lo;
+      if (rows > 0)
+        mtmc::launch_bn_relu_rows({x.at<float>(x.lo.Y[last]), MTMC_NODE_DIM, rows, MTMC_NODE_DIM,
+                                   x.at<double>(x.lo.pub.stat_enc_layer_off[last]), m->enc_node[last].gamma, m->enc_node[last].beta,
+                                   (double)c->n_nodes, x.at<float>(x.lo.pub.h0_off) + (size_t)c->node_lo * MTMC_NODE_DIM,
+                                   make_drop(x, m->dropout_enc), mtmc::kDropEncNode + last, c->node_lo}, s);
+      break;
+    }
+    case MTMC_PH_ROUND_PROJ: {
+      if (arg < 0 || arg >= L) return fail(MTMC_E_ARG, "round %d out of range", arg);
+      mtmc::NodeProjParams p;
+      const int last = m->n_enc_layers - 1;
+      p.y_last = (arg == 0 && fused_h0) ? x.at<float>(x.lo.Y[last]) : nullptr;
+      p.y_stats = x.at<double>(x.lo.pub.stat_enc_layer_off[last]); p.y_gamma = m->enc_node[last].gamma;
+      p.y_beta = m->enc_node[last].beta; p.y_count = (double)c->n_nodes; p.h0_out = x.at<float>(x.lo.pub.h0_off);
+      p.finalize_enc = arg == 0; p.enc = enc_params(x); p.e_total = (double)c->n_edges_total;
+      p.h_src = round_h_src(x, arg);
+      p.drop = make_drop(x, m->dropout_enc); p.drop_stream = mtmc::kDropEncNode + last;
+      p.h0 = m->reattach_nodes ? x.at<float>(x.lo.pub.h0_off) : nullptr;
+      p.deg = (m->agg == MTMC_AGG_MEAN && arg > 0) ? scale_deg(x) : nullptr;
+      p.ue_w = m->upd_edge.weight; p.ue_ld = m->upd_edge.in_dim;
+      p.un_w = m->upd_node.weight; p.un_ld = m->upd_node.in_dim;
+      p.hn = node_in_width(m);
+      p.P = round_P(x, arg); p.Q = round_Q(x, arg);
+      p.zero_buf = agg_target(x, arg);
+      p.n_nodes = c->n_nodes;
+      p.node_begin = proj_lo(c); p.node_end = proj_hi(c);
+      p.edge_deg = x.at<int>(x.lo.pub.deg_off); p.un_b = m->upd_node.bias;
+      p.z2_stats = x.plan.fold_node_stat
+                       ? x.at<double>(x.lo.pub.stat_round_off) + (size_t)arg * mtmc::kRoundBlock + mtmc::kRoundZ2Off : nullptr;
+      mtmc::launch_node_proj(p, s);
+      break;
+    }
+    case MTMC_PH_ROUND_A:
+    case MTMC_PH_ROUND_B:
+    case MTMC_PH_ROUND_C: {
+      if (arg < 0 || arg >= L) return fail(MTMC_E_ARG, "round %d out of range", arg);
+      if (c->n_edges == 0) break;
+      const mtmc::RoundParams p = round_params(x, arg);
+      if (phase == MTMC_PH_ROUND_A) mtmc::launch_pass_a(p, s);
+      else if (phase == MTMC_PH_ROUND_B) mtmc::launch_pass_b(p, s);
+      else mtmc::launch_pass_c(p, s);
+      break;
+    }
+    case MTMC_PH_ROUND_STAT: {     // few-edge lists: nothing (the statistics came out of MTMC_PH_ROUND_PROJ + MTMC_PH_ROUND_B)
+      if (arg < 0 || arg >= L) return fail(MTMC_E_ARG, "round %d out of range", arg);
+      if (x.plan.fold_node_stat) break;
+      mtmc::NodeStatParams p;
+      p.Q = round_Q(x, arg); p.deg = x.at<int>(x.lo.pub.deg_off); p.seg = x.at<double>(x.lo.pub.seg_off);
+      p.un_w = m->upd_node.weight; p.un_b = m->upd_node.bias; p.un_ld = m->upd_node.in_dim;
+      p.un_eoff = node_in_width(m);
+      p.stats = x.at<double>(x.lo.pub.stat_round_off) + (size_t)arg * mtmc::kRoundBlock;
+      p.n_nodes = c->n_nodes;
+      p.node_begin = proj_lo(c); p.node_end = proj_hi(c);
+      mtmc::launch_node_stat(p, s);
+      break;
+    }
+    case MTMC_PH_END: {
+      const float* src = round_h_src(x, L);
+      if (L == 0 || m->agg == MTMC_AGG_MEAN || x.lo.training)   // otherwise the last round aggregated into h_out
+        mtmc::launch_h_final(src, scale_deg(x), (m->agg == MTMC_AGG_MEAN && L > 0) ? 1 : 0, c->n_nodes, c->h_out, s);
+      if (L == 0 && c->n_edges > 0)
+        mtmc::launch_classify_e0(enc_params(x), c->edge_attr, c->n_edges, (double)c->n_edges_total, m->cls.weight,
+                                 m->cls.bias, m->cls.out_dim, c->logits, s);
+      break;
+    }
+    default:
+      return fail(MTMC_E_ARG, "unknown phase %d", phase);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MTMC_E_HIP, "kernel launch failed in phase %d: %s", phase, hipGetErrorString(e));
+  return MTMC_OK;
 }
 
 }  // namespace
@@ -201,199 +505,6 @@ int32_t mtmc_mpn_forward(const mtmc_mpn_model* model, const mtmc_mpn_call* call)
     if ((rc = run_phase(x, MTMC_PH_ROUND_C, r))) return rc;
   }
   return run_phase(x, MTMC_PH_END, 0);
-}
-
-static int scatter_common(const char* entry, const float* src, const int64_t* index, int64_t n_src, int64_t n_cols,
-                          int64_t dim_size, float* out, float* count, int64_t* arg_out, int mode, void* stream) {
-  if (n_src < 0 || n_cols < 1 || dim_size < 0 || !out || (n_src > 0 && (!src || !index)))
-    return fail(MTMC_E_ARG, "%s: n_src and dim_size must be >= 0, n_cols >= 1, and out (with rows: src and index) not NULL", entry);
-  if (mode == 1 && !count) return fail(MTMC_E_ARG, "%s: needs count_scratch[dim_size]", entry);
-  if (dim_size == 0) return MTMC_OK;
-  mtmc::launch_scatter(src, index, n_src, n_cols, dim_size, out, count, arg_out, mode, static_cast<hipStream_t>(stream));
-  return launched(entry);
-}
-int32_t mtmc_scatter_add(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                         float* out, void* stream) {
-  return scatter_common("scatter_add", src, index, n_src, n_cols, dim_size, out, nullptr, nullptr, 0, stream);
-}
-int32_t mtmc_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                             int64_t* out, void* stream) {
-  if (n_src < 0 || n_cols < 1 || dim_size < 0 || !out || (n_src > 0 && (!src || !index)))
-    return fail(MTMC_E_ARG, "scatter_add_i64: n_src and dim_size must be >= 0, n_cols >= 1, and out (with rows: src and index) not NULL");
-  if (dim_size == 0) return MTMC_OK;
-  mtmc::launch_scatter_add_i64(src, index, n_src, n_cols, dim_size, out, static_cast<hipStream_t>(stream));
-  return launched("scatter_add_i64");
-}
-int32_t mtmc_scatter_mean(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                          float* out, float* count_scratch, void* stream) {
-  return scatter_common("scatter_mean", src, index, n_src, n_cols, dim_size, out, count_scratch, nullptr, 1, stream);
-}
-int32_t mtmc_scatter_max(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                         float* out, int64_t* arg_out, void* stream) {
-  return scatter_common("scatter_max", src, index, n_src, n_cols, dim_size, out, nullptr, arg_out, 2, stream);
-}
-
-static int scatter_backward_common(const char* entry, const float* grad_out, const int64_t* arg, const int64_t* index,
-                                   int64_t n_src, int64_t n_cols, int64_t dim_size, int32_t* count, float* grad_src, int mode,
-                                   void* stream) {
-  if (n_src < 0 || n_cols < 0 || dim_size < 0) return fail(MTMC_E_ARG, "%s: n_src, n_cols and dim_size must be >= 0", entry);
-  if (n_src == 0 || n_cols == 0) return MTMC_OK;
-  // (without destination rows there is no gradient to read: every row of grad_src is zero)
-  if (!index || !grad_src || (dim_size > 0 && !grad_out)) return fail(MTMC_E_ARG, "%s: NULL grad_out, index or grad_src", entry);
-  if (mode == 2 && dim_size > 0 && !arg) return fail(MTMC_E_ARG, "%s: NULL arg", entry);
-  if (mode == 1 && dim_size > 0 && !count) return fail(MTMC_E_ARG, "%s: needs count_scratch[dim_size]", entry);
-  if ((((uintptr_t)grad_out | (uintptr_t)grad_src | (uintptr_t)count) & 3) || (((uintptr_t)index | (uintptr_t)arg) & 7))
-    return fail(MTMC_E_ARG, "%s: grad_out, grad_src and count_scratch must be 4-byte, index and arg 8-byte aligned", entry);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == 1 && dim_size > 0 && hipMemsetAsync(count, 0, (size_t)dim_size * sizeof(int32_t), s) != hipSuccess)
-    return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
-  mtmc::launch_scatter_backward(grad_out, arg, index, n_src, n_cols, dim_size, count, grad_src, mode, s);
-  return launched(entry);
-}
-int32_t mtmc_scatter_add_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                                  float* grad_src, void* stream) {
-  return scatter_backward_common("scatter_add_backward", grad_out, nullptr, index, n_src, n_cols, dim_size, nullptr, grad_src, 0,
-                                 stream);
-}
-int32_t mtmc_scatter_mean_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                                   int32_t* count_scratch, float* grad_src, void* stream) {
-  return scatter_backward_common("scatter_mean_backward", grad_out, nullptr, index, n_src, n_cols, dim_size, count_scratch,
-                                 grad_src, 1, stream);
-}
-int32_t mtmc_scatter_max_backward(const float* grad_out, const int64_t* arg, const int64_t* index, int64_t n_src, int64_t n_cols,
-                                  int64_t dim_size, float* grad_src, void* stream) {
-  return scatter_backward_common("scatter_max_backward", grad_out, arg, index, n_src, n_cols, dim_size, nullptr, grad_src, 2,
-                                 stream);
-}
-
-int32_t mtmc_mlp_layer_forward(const mtmc_layer* layer, const float* x, int64_t x_row_stride, int64_t rows, float* y,
-                               double* stats_scratch, void* stream) {
-  if (!layer || !layer->weight || !layer->bias || !x || !y || rows < 1) return fail(MTMC_E_ARG, "bad mlp layer arguments");
-  const bool bn = layer->gamma != nullptr;
-  if (bn && (!layer->beta || !stats_scratch)) return fail(MTMC_E_ARG, "BatchNorm layer needs beta and stats_scratch[2*out]");
-  if (bn && rows < 2) return fail(MTMC_E_ROWS, "Expected more than 1 value per channel when training");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (bn && hipMemsetAsync(stats_scratch, 0, 2 * (size_t)layer->out_dim * sizeof(double), s) != hipSuccess)
-    return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-  mtmc::GemmParams g =
-      mtmc::plain_gemm(x, x_row_stride, layer->weight, layer->bias, y, layer->out_dim, rows, layer->in_dim, layer->out_dim);
-  if (bn) g.stats_out = stats_scratch;
-  if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "unsupported layer shape");
-  if (bn)
-    mtmc::launch_bn_relu_rows({y, layer->out_dim, rows, layer->out_dim, stats_scratch, layer->gamma, layer->beta, (double)rows, y,
-                               mtmc::kNoDrop, 0}, s);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "mlp layer launch failed: %s", hipGetErrorString(e));
-}
-
-// ---- Diagnostics / unit tests: one encoder layer on the kernel the forward would run it on.  In all four, scratch: u32[48] =
-// the |A|max, |W|max, |Y|max words; stats: f64[2*N] column sum / sumsq of Y, or NULL; work: kernels.h raw_work unless said.
-static int raw_begin(uint32_t* scratch, double* stats, int N, hipStream_t s) {
-  return mtmc::clear_raw(scratch, stats, N, s) ? MTMC_OK : fail(MTMC_E_HIP, "hipMemsetAsync failed");
-}
-static int raw_end(int rc) {       // rc: the launcher's answer (0 ok, MTMC_E_HIP, anything else: shape refused)
-  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "unsupported shape or launch refused");
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MTMC_OK : fail(MTMC_E_HIP, "launch failed: %s", hipGetErrorString(e));
-}
-// |A|max -> scratch[0] and (W given) |W|max -> scratch[1], by prep_kernel's passenger workgroups as in the forward
-static void raw_amax(const float* A, int64_t lda, int64_t M, const float* W, int K, int N, uint32_t* scratch, hipStream_t s) {
-  mtmc::PrepParams p = {};
-  p.jobs[p.n_jobs++] = {A, M, K, lda, scratch, 0, 0};
-  if (W) p.jobs[p.n_jobs++] = {W, N, K, K, scratch + mtmc::kAmaxRep, 0, 0};
-  mtmc::launch_prep(p, s);
-}
-
-// Y[M][N] = A[M][K] . W[N][K]^T + bias through the node encoder's GEMM dispatch exactly as the forward uses it for layer 0
-// (fp16 two-piece kernel where it applies).
-int32_t mtmc_linear_raw(const float* A, int64_t lda, const float* W, const float* bias, float* Y, int64_t M, int32_t K,
-                        int32_t N, uint32_t* scratch, double* stats, void* stream) {
-  if (!A || !W || !bias || !Y || !scratch || M < 1 || K < 32 || K % 32 || N < 1) return fail(MTMC_E_ARG, "bad arguments");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = raw_begin(scratch, stats, N, s)) return rc;
-  raw_amax(A, lda, M, W, K, N, scratch, s);
-  mtmc::GemmParams g = mtmc::plain_gemm(A, lda, W, bias, Y, N, M, K, N, scratch, scratch + mtmc::kAmaxRep, scratch + 2 * mtmc::kAmaxRep);
-  g.stats_out = stats;
-  return raw_end(mtmc::launch_gemm_bn(g, s));
-}
-
-// A layer >= 1 of a many-row graph: Y[M][N] = relu(bn(A))[M][K] . W[N][K]^T + bias, bn = BatchNorm with the given column
-// statistics (f64 sum[K] | sumsq[K] over `count` rows) and gamma / beta -- on the role-split kernel (gemm_staged.hip:
-// N % 256 == 0, or N = 128) or, for the narrow last layer (K = 128, N = 32), the row-streaming kernel (gemm_rows.hip).
-// work: >= 4*N*K + 4*N + 256 bytes (the role-split kernel's weight planes, their row scales on the next 256-byte boundary).
-int32_t mtmc_linear_staged_raw(const float* A, int64_t lda, const double* stats_in, const float* gamma_in, const float* beta_in,
-                               double count, const float* W, const float* bias, float* Y, int64_t M, int32_t K, int32_t N,
-                               void* work, uint64_t work_bytes, uint32_t* scratch, double* stats, void* stream) {
-  const bool narrow = K == 128 && N == 32;
-  if (!A || !stats_in || !gamma_in || !beta_in || !W || !bias || !Y || !work || !scratch || M < 1 || K < 64 || K % 32 || K > 2048 ||
-      (!narrow && N != 128 && (N < 256 || N % 256)) || lda < K || (lda & 3) || ((uintptr_t)A & 15))
-    return fail(MTMC_E_ARG, "bad arguments");
-  const uint64_t iw_off = ((uint64_t)N * K * 4 + 255) / 256 * 256;
-  if (work_bytes < iw_off + (uint64_t)N * 4) return fail(MTMC_E_ARG, "work buffer too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = raw_begin(scratch, stats, N, s)) return rc;
-  raw_amax(A, lda, M, nullptr, K, N, scratch, s);
-  if (narrow) {
-    mtmc::GemmParams g = mtmc::plain_gemm(A, lda, W, bias, Y, N, M, K, N, scratch, nullptr, scratch + 2 * mtmc::kAmaxRep);
-    g.stats_in = stats_in; g.gamma_in = gamma_in; g.beta_in = beta_in; g.count = count; g.stats_out = stats;
-    return raw_end(mtmc::launch_gemm_rows(g, s));
-  }
-  mtmc::StagedGemmParams g;
-  mtmc::set_in(&g, A, lda, stats_in, gamma_in, beta_in, count);
-  g.amax_a = scratch;
-  float* inv_w = reinterpret_cast<float*>(static_cast<char*>(work) + iw_off);
-  mtmc::launch_split_rows(W, K, N, K, work, inv_w, s);
-  g.Wh = static_cast<_Float16*>(work); g.inv_w = inv_w;
-  mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
-  return raw_end(mtmc::launch_gemm_staged(g, s));
-}
-
-// A layer of a few-row graph (gemm_few.hip): layer 0 (stats_in == NULL: x is split into planes too) or a layer >= 1.
-int32_t mtmc_linear_few_raw(const float* A, int64_t lda, const double* stats_in, const float* gamma_in, const float* beta_in,
-                            double count, const float* W, const float* bias, float* Y, int64_t M, int32_t K, int32_t N,
-                            void* work, uint64_t work_bytes, double* stats, void* stream) {
-  const bool l0 = stats_in == nullptr;
-  if (!A || !W || !bias || !Y || !work || M < 1 || K < 32 || K > 2048 || N < 1 || lda < K || (lda & 3) || ((uintptr_t)A & 15) ||
-      (l0 ? !mtmc::few_l0_shape(K, N) : (!mtmc::few_wave_shape(K, N) || !gamma_in || !beta_in)))
-    return fail(MTMC_E_ARG, "bad arguments");
-  const mtmc::RawWork wk = mtmc::raw_work(work, M, K, N, l0);
-  if (work_bytes < wk.bytes) return fail(MTMC_E_ARG, "work buffer too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = raw_begin(nullptr, stats, N, s)) return rc;
-  mtmc::launch_split_rows(W, K, N, K, wk.Wh, wk.inv_w, s);
-  if (l0) {
-    mtmc::launch_split_rows(A, lda, M, K, wk.Ah, wk.inv_a, s);
-    mtmc::FewL0Params g;
-    g.Ah = wk.Ah; g.inv_a = wk.inv_a; g.Wh = wk.Wh; g.inv_w = wk.inv_w;
-    mtmc::set_out(&g, bias, Y, N, M, K, N, stats);
-    return raw_end(mtmc::launch_few_l0(g, s));
-  }
-  mtmc::FewWaveParams g;
-  mtmc::set_in(&g, A, lda, stats_in, gamma_in, beta_in, count);
-  g.Wh = wk.Wh; g.inv_w = wk.inv_w;
-  mtmc::set_out(&g, bias, Y, N, M, K, N, stats);
-  return raw_end(mtmc::launch_few_wave(g, s));
-}
-
-// Layer 0 of a many-row graph on pre-split operands (gemm_presplit.hip); reuse_planes: the planes in `work` are those of the
-// call before (times the GEMM alone).
-int32_t mtmc_linear_presplit_raw(const float* A, int64_t lda, const float* W, const float* bias, float* Y, int64_t M,
-                                 int32_t K, int32_t N, void* work, uint64_t work_bytes, uint32_t* scratch, double* stats,
-                                 int32_t reuse_planes, void* stream) {
-  if (!A || !W || !bias || !Y || !work || !scratch || M < 1 || K < 64 || K % 64 || K > 2048 || N < 1)
-    return fail(MTMC_E_ARG, "bad arguments");
-  const mtmc::RawWork wk = mtmc::raw_work(work, M, K, N, true);
-  if (work_bytes < wk.bytes) return fail(MTMC_E_ARG, "work buffer too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = raw_begin(scratch, stats, N, s)) return rc;
-  if (!reuse_planes) {
-    mtmc::launch_split_rows(A, lda, M, K, wk.Ah, wk.inv_a, s);
-    mtmc::launch_split_rows(W, K, N, K, wk.Wh, wk.inv_w, s);
-  }
-  mtmc::SplitGemmParams g;
-  g.Ah = wk.Ah; g.inv_a = wk.inv_a; g.Wh = wk.Wh; g.inv_w = wk.inv_w;
-  mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
-  return raw_end(mtmc::launch_gemm_presplit(g, s));
 }
 
 }  // extern "C"

@@ -1,11 +1,10 @@
 // Internals shared by the C-ABI translation units (api.hip: forward + phases, api_train.hip: backward):
-// error text, workspace carving, per-phase parameter blocks and the phase launcher.
+// model and call checks, workspace carving, the call's plan and context, and the parameter blocks both directions fill.
 #pragma once
 #include "api_error.h"
 #include "kernels.h"
 #include "train_kernels.h"
 
-#include <mutex>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -17,12 +16,11 @@ inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 struct Layout {
   mtmc_ws_layout pub;
-  size_t row32, col32, e_buf[2], P, Q, slab, enc_aff, row_start, carry;
+  size_t row32, col32, e_buf[2], Q, slab, enc_aff, row_start, carry;
   size_t col_sub; int col_blocks;              // column-blocked pass A: int[N][col_blocks + 1] sub-run boundaries (0 blocks: none)
   size_t amax;                                 // u32[1 + 2*MTMC_MAX_ENC_LAYERS][kAmaxRep]: |x|max, -, |Y_l|max (zeroed)
   size_t amax_w;                               // u32[MTMC_MAX_ENC_LAYERS][kAmaxRep]: |W_l|max of the in-loop layers
   size_t Y[MTMC_MAX_ENC_LAYERS];
-  size_t stat_enc_layer[MTMC_MAX_ENC_LAYERS];
   // training: every round keeps its own buffers (the workspace is the backward tape) + backward scratch
   bool training;
   std::vector<size_t> z_tr, e_tr, h_tr;       // per round: z1 [E][4], e' [E][4], aggregated h [N][32]
@@ -109,10 +107,9 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
   // the edge branch's two statistics blocks sit right in front of node-encoder layer 0's / layer 1's column statistics: a
   // multi-GPU host all-reduces each pair as ONE message (mtmc_ws_layout, distributed.py)
   lo->pub.stat_attr_off = take((size_t)mtmc::kStatRep * mtmc::kAttrStride * sizeof(double));
-  lo->stat_enc_layer[0] = take(2 * (size_t)m->enc_node[0].out_dim * sizeof(double));
+  lo->pub.stat_enc_layer_off[0] = take(2 * (size_t)m->enc_node[0].out_dim * sizeof(double));
   lo->pub.stat_enc2_off = take((size_t)mtmc::kStatRep * mtmc::kEnc2Stride * sizeof(double));
-  for (int l = 1; l < m->n_enc_layers; ++l) lo->stat_enc_layer[l] = take(2 * (size_t)m->enc_node[l].out_dim * sizeof(double));
-  for (int l = 0; l < m->n_enc_layers; ++l) lo->pub.stat_enc_layer_off[l] = lo->stat_enc_layer[l];
+  for (int l = 1; l < m->n_enc_layers; ++l) lo->pub.stat_enc_layer_off[l] = take(2 * (size_t)m->enc_node[l].out_dim * sizeof(double));
   lo->pub.stat_round_off = take((size_t)(L > 0 ? L : 1) * mtmc::kRoundBlock * sizeof(double));
   lo->pub.deg_off = take((size_t)N * sizeof(int32_t));
   lo->pub.seg_off = take(mtmc::fold_node_stat(E) ? 0 : (size_t)N * 4 * sizeof(double));   // (few-edge lists: none)
@@ -129,8 +126,7 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
   lo->carry = take((size_t)((E + 31) / 32) * 2 * 32 * sizeof(float));
   lo->col_blocks = mtmc::plan_col_blocks(N, E, 1e30, training);      // by table size and edge count alone (the call adds the degree)
   lo->col_sub = take(lo->col_blocks > 0 ? (size_t)N * (lo->col_blocks + 1) * sizeof(int32_t) : 0);
-  lo->P = take((size_t)N * 8 * sizeof(float));
-  lo->pub.P_off = lo->P;
+  lo->pub.P_off = take((size_t)N * 8 * sizeof(float));
   lo->Q = take((size_t)N * 32 * sizeof(float));
   lo->row32 = take((size_t)E * sizeof(int32_t));
   lo->col32 = take((size_t)E * sizeof(int32_t));
@@ -166,8 +162,8 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
       lo->z_tr.push_back(take((size_t)E * 4 * sizeof(float)));
       lo->e_tr.push_back(take((size_t)E * 4 * sizeof(float)));
       lo->h_tr.push_back(take((size_t)N * 32 * sizeof(float)));
-      lo->P_tr.push_back(r == 0 ? lo->P : take((size_t)N * 8 * sizeof(float)));     // the round's projections stay on the
-      lo->Q_tr.push_back(r == 0 ? lo->Q : take((size_t)N * 32 * sizeof(float)));    // tape: the backward reads them as is
+      lo->P_tr.push_back(r == 0 ? lo->pub.P_off : take((size_t)N * 8 * sizeof(float)));   // the round's projections stay on
+      lo->Q_tr.push_back(r == 0 ? lo->Q : take((size_t)N * 32 * sizeof(float)));          // the tape: the backward reads them as is
     }
     // everything the backward accumulates into, contiguous: ONE memset clears it (api_train.hip)
     size_t maxd = 0, bn_stats = 0;
@@ -206,15 +202,8 @@ inline void make_layout(const mtmc_mpn_model* m, int64_t N, int64_t E, Layout* l
   lo->pub.total_bytes = off;
 }
 
-// Side stream + events of the pipelined layer 0 (api.hip: one set per device, created on first use)
 constexpr int kMaxPanels = 16;
-struct SidePipe { hipStream_t stream = nullptr; hipEvent_t fork = nullptr; hipEvent_t ready[kMaxPanels] = {}; };
-
-// Diagnostics (bench.py): HIP events around every layer-0 GEMM launch of a many-row forward -- in the pipelined forward the
-// layer is several panel launches beside the operand split on a side stream, and the figure a bench line reports must be
-// that of the forward it sits beside.  Off by default; mtmc_dbg_panel_timing / mtmc_dbg_panel_times (api.hip).
-struct PanelTiming { bool on = false, created = false; hipEvent_t ev[2 * kMaxPanels]; int n = 0; };
-inline PanelTiming& panel_timing() { static PanelTiming t; return t; }
+struct SidePipe;                 // side stream + events of the pipelined layer 0 (api.hip)
 
 // Row panels of the pipelined layer 0: cuts[0..np] (multiples of the tile height), np <= kMaxPanels; *bm = the tile height
 // of every panel (what the whole matrix would pick).  One round = 256 workgroups = 256 / tiles_n row tiles.
@@ -425,7 +414,7 @@ inline float* round_h_src(const Ctx& x, int r) {
   if (r == 0) return x.at<float>(x.lo.pub.h0_off);
   return x.lo.training ? x.at<float>(x.lo.h_tr[r - 1]) : x.at<float>(x.lo.pub.h_acc_off[(r - 1) & 1]);
 }
-inline float* round_P(const Ctx& x, int r) { return x.at<float>(x.lo.training ? x.lo.P_tr[r] : x.lo.P); }
+inline float* round_P(const Ctx& x, int r) { return x.at<float>(x.lo.training ? x.lo.P_tr[r] : x.lo.pub.P_off); }
 inline float* round_Q(const Ctx& x, int r) { return x.at<float>(x.lo.training ? x.lo.Q_tr[r] : x.lo.Q); }
 inline float* round_z(const Ctx& x, int r) { return x.at<float>(x.lo.training ? x.lo.z_tr[r] : x.lo.e_buf[r & 1]); }
 inline float* round_e(const Ctx& x, int r) { return x.at<float>(x.lo.training ? x.lo.e_tr[r] : x.lo.e_buf[r & 1]); }
@@ -476,300 +465,10 @@ inline float* w_inv(const Ctx& x, int l) {
   return x.at<float>(x.lo.inv_w[l]);
 }
 
-enum { kPhMemset = -1, kPhPrep = -2 };   // the two halves of MTMC_PH_BEGIN, for the forked forward
-
-// the edge part of prep_kernel for this call
-inline void fill_prep_edge(const Ctx& x, mtmc::PrepEdge* p) {
-  const mtmc_mpn_call* c = x.c;
-  p->row = c->row; p->col = c->col; p->idx_stride = c->idx_stride; p->attr = c->edge_attr; p->fe = x.m->enc_edge[0].in_dim;
-  p->n_edges = c->n_edges; p->n_nodes = c->n_nodes;
-  p->row32 = x.at<int>(x.lo.row32); p->col32 = x.at<int>(x.lo.col32); p->deg = x.at<int>(x.lo.pub.deg_off);
-  p->flags = x.at<int>(x.lo.pub.flags_off); p->stat_attr = x.at<double>(x.lo.pub.stat_attr_off);
-  p->row_start = x.at<int>(x.lo.row_start);
-}
-
-inline const int* scale_deg(const Ctx& x) {   // the degree mean aggregation divides by
-  return x.at<int>((x.c->flags & MTMC_F_GLOBAL_DEG) ? x.lo.pub.deg_global_off : x.lo.pub.deg_off);
-}
-
 // The |.|max words (u32[kAmaxRep] each) of x, of layer l's raw output Y_l and of W_l (Layout::amax, amax_w)
 inline unsigned* amax_x(const Ctx& x) { return x.at<unsigned>(x.lo.amax); }
 inline unsigned* amax_y(const Ctx& x, int l) { return amax_x(x) + (1 + MTMC_MAX_ENC_LAYERS + l) * mtmc::kAmaxRep; }
 inline unsigned* amax_w(const Ctx& x, int l) { return x.at<unsigned>(x.lo.amax_w) + l * mtmc::kAmaxRep; }
 inline unsigned* amax_in(const Ctx& x, int l) { return l == 0 ? amax_x(x) : amax_y(x, l - 1); }   // of layer l's input
-
-// The parts of node-encoder layer l's parameter block (kernels.h), each filled from the call in one place.
-// Input: x for layer 0, else the previous layer's raw Y with its statistics, BatchNorm and Dropout
-inline void fill_in(const Ctx& x, int l, mtmc::ActIn* q) {
-  if (l == 0) {
-    q->A = x.c->x; q->lda = x.c->x_row_stride;
-  } else {
-    const mtmc_layer& Pv = x.m->enc_node[l - 1];
-    q->A = x.at<float>(x.lo.Y[l - 1]); q->lda = Pv.out_dim;
-    q->stats_in = x.at<double>(x.lo.stat_enc_layer[l - 1]); q->gamma_in = Pv.gamma; q->beta_in = Pv.beta;
-  }
-  q->count = (double)x.c->n_nodes;
-  q->drop_in = make_drop(x, x.m->dropout_enc); q->drop_stream = mtmc::kDropEncNode + l - 1;
-}
-inline void fill_out(const Ctx& x, int l, mtmc::LayerOut* q) {
-  const mtmc_layer& Lr = x.m->enc_node[l];
-  q->bias = Lr.bias; q->Y = x.at<float>(x.lo.Y[l]); q->ldy = Lr.out_dim;
-  q->stats_out = x.at<double>(x.lo.stat_enc_layer[l]); q->amax_y = amax_y(x, l);
-  q->M = x.plan.rows; q->K = Lr.in_dim; q->Nout = Lr.out_dim;
-}
-inline void fill_w(const Ctx& x, int l, mtmc::PlanesW* q) { q->Wh = w_planes(x, l); q->inv_w = w_inv(x, l); }
-inline void fill_x(const Ctx& x, mtmc::PlanesA* q) { q->Ah = x.at<_Float16>(x.lo.xh); q->inv_a = x.at<float>(x.lo.inv_a); }
-// MTMC_PH_EDGE_ENC's work as passenger workgroups of the last encoder layer's launch
-inline void ride_enc2(const Ctx& x, mtmc::Enc2Ride* q) {
-  const int64_t blocks = (x.c->n_edges + 255) / 256;
-  q->pass_blocks = (int)(blocks > 2048 ? 2048 : blocks);
-  q->pass_enc = enc_params(x); q->pass_attr = x.c->edge_attr; q->pass_edges = x.c->n_edges;
-  q->pass_e_total = (double)x.c->n_edges_total; q->pass_stat = x.at<double>(x.lo.pub.stat_enc2_off);
-}
-
-// The node-encoder layer launches of MTMC_PH_NODE_ENC, one per form of CallPlan::enc_kernel.
-// Few-row graphs (gemm_few.hip): one launch per layer, never split along K.
-inline int launch_enc_few(const Ctx& x, int l) {
-  int rc;
-  if (l == 0) {
-    mtmc::FewL0Params q;
-    fill_x(x, &q); fill_w(x, 0, &q); fill_out(x, 0, &q);
-    rc = mtmc::launch_few_l0(q, x.stream);
-  } else {
-    mtmc::FewWaveParams q;
-    fill_in(x, l, &q); fill_w(x, l, &q); fill_out(x, l, &q);
-    if (x.enc2_rides && l == x.m->n_enc_layers - 1) ride_enc2(x, &q);
-    rc = mtmc::launch_few_wave(q, x.stream);
-  }
-  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: few-row kernel refused the shape or the launch", l);
-  return MTMC_OK;
-}
-
-// Many-row graphs, layer 0 on the operand planes made in MTMC_PH_BEGIN -- or, in the pipelined forward (x.pipe), in row panels.
-inline int launch_enc_presplit0(const Ctx& x) {
-  const mtmc_mpn_call* c = x.c;
-  const mtmc_layer& Lr = x.m->enc_node[0];
-  const int64_t rows = x.plan.rows;
-  hipStream_t s = x.stream;
-  mtmc::SplitGemmParams q;
-  fill_x(x, &q); fill_w(x, 0, &q); fill_out(x, 0, &q);
-  PanelTiming& pt = panel_timing();
-  if (x.pipe) {
-    // Row panels: the side stream splits panel after panel (HBM-bound), the main stream multiplies panel i as soon as
-    // its planes are there (matrix-bound): the split pass leaves the critical path except for the first panel.
-    // Panel = whole rounds of workgroups of the tile height the whole matrix would get, so no round is paid twice.
-    const int np = x.plan.l0_panels;
-    const int64_t* cuts = x.plan.l0_cuts;
-    q.bm = x.plan.l0_bm;
-    q.M_rows = rows;
-    if (hipEventRecord(x.pipe->fork, s) != hipSuccess || hipStreamWaitEvent(x.pipe->stream, x.pipe->fork, 0) != hipSuccess)
-      return fail(MTMC_E_HIP, "encoder layer 0: fork onto the side stream failed");
-    // from here on the side stream is forked off `s` (inside a capture: part of it): every way out joins it again
-    auto join_and = [&](int code, const char* what) {
-      if (hipEventRecord(x.pipe->ready[0], x.pipe->stream) == hipSuccess) (void)hipStreamWaitEvent(s, x.pipe->ready[0], 0);
-      return fail(code, "%s", what);
-    };
-    for (int i = 0; i < np; ++i) {
-      mtmc::launch_split_rows_range(c->x, c->x_row_stride, rows, Lr.in_dim, x.at<void>(x.lo.xh), x.at<float>(x.lo.inv_a),
-                                    cuts[i], cuts[i + 1], x.pipe->stream);
-      if (hipEventRecord(x.pipe->ready[i], x.pipe->stream) != hipSuccess) return join_and(MTMC_E_HIP, "hipEventRecord failed");
-    }
-    if (pt.on) pt.n = 0;
-    for (int i = 0; i < np; ++i) {               // (the wait on the last panel's event also joins the side stream)
-      if (hipStreamWaitEvent(s, x.pipe->ready[i], 0) != hipSuccess) return join_and(MTMC_E_HIP, "hipStreamWaitEvent failed");
-      q.m_lo = cuts[i]; q.M = cuts[i + 1];
-      if (pt.on) (void)hipEventRecord(pt.ev[2 * i], s);
-      const int rc = mtmc::launch_gemm_presplit(q, s);
-      if (pt.on) { (void)hipEventRecord(pt.ev[2 * i + 1], s); pt.n = i + 1; }
-      if (rc != 0) return join_and(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer 0: pre-split GEMM refused a panel");
-    }
-    return MTMC_OK;
-  }
-  if (pt.on) { pt.n = 0; (void)hipEventRecord(pt.ev[0], s); }
-  const int rc = mtmc::launch_gemm_presplit(q, s);
-  if (pt.on) { (void)hipEventRecord(pt.ev[1], s); pt.n = 1; }
-  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer 0: pre-split GEMM refused the shape or the launch");
-  return MTMC_OK;
-}
-
-// Many-row graphs, layers >= 1 on the role-split kernel (gemm_staged.hip).
-inline int launch_enc_staged(const Ctx& x, int l) {
-  mtmc::StagedGemmParams q;
-  fill_in(x, l, &q); fill_w(x, l, &q); fill_out(x, l, &q);
-  q.amax_a = amax_in(x, l);
-  const int rc = mtmc::launch_gemm_staged(q, x.stream);
-  if (rc != 0) return fail(rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG, "encoder layer %d: role-split GEMM refused the shape or the launch", l);
-  return MTMC_OK;
-}
-
-// The in-loop operand split (gemm_bn.hip; MTMC_PH_NODE_COMBINE adds up the slab's K slices), or the row-streaming kernel
-// (gemm_rows.hip) of the narrow last layers of many-row graphs.
-inline int launch_enc_gemm(const Ctx& x, int l, int phase) {
-  mtmc::GemmParams g;
-  fill_in(x, l, &g); fill_out(x, l, &g);
-  g.W = x.m->enc_node[l].weight; g.amax_a = amax_in(x, l); g.amax_w = amax_w(x, l);
-  if (x.enc2_rides && phase == MTMC_PH_NODE_ENC && l == x.m->n_enc_layers - 1) ride_enc2(x, &g);
-  if (x.plan.enc_kernel[l] == MTMC_GEMM_ROWS_16) {
-    if (mtmc::launch_gemm_rows(g, x.stream) != 0) return fail(MTMC_E_ARG, "encoder layer %d: row-streaming GEMM refused the shape", l);
-    return MTMC_OK;
-  }
-  if (x.plan.enc_split_k[l] > 1) g.slab = x.at<float>(x.lo.slab);
-  if (mtmc::launch_gemm_bn(g, x.stream, phase == MTMC_PH_NODE_ENC ? 1 : 2) != MTMC_OK)
-    return fail(MTMC_E_ARG, "encoder layer %d: unsupported GEMM shape", l);
-  return MTMC_OK;
-}
-
-inline int run_phase(const Ctx& x, int phase, int arg, bool fused_h0 = false) {
-  const mtmc_mpn_model* m = x.m;
-  const mtmc_mpn_call* c = x.c;
-  const int L = m->num_enc_steps;
-  hipStream_t s = x.stream;
-  switch (phase) {
-    case MTMC_PH_BEGIN:
-    case kPhMemset:
-    case kPhPrep: {
-      // What depends on the WEIGHTS alone -- the fp16 planes + row scales of the layers that run on pre-split weights -- lives in
-      // the call's weight-plane cache when it has one and is VERIFIED here on every call, chunk by chunk, by passenger
-      // workgroups of prep_kernel (split_body.h); without a cache it is made per call in the workspace.
-      if (phase != kPhPrep && hipMemsetAsync(x.ws, 0, x.lo.pub.zero_bytes, s) != hipSuccess)
-        return fail(MTMC_E_HIP, "hipMemsetAsync failed");
-      if (phase != kPhPrep && c->training && (c->flags & MTMC_F_SEED_ON_DEVICE))      // seed word <- counter++ (one thread)
-        mtmc::launch_seed_tick(reinterpret_cast<unsigned long long*>((uintptr_t)c->seed), x.at<unsigned long long>(x.lo.seed_word), s);
-      if (phase != kPhMemset) {
-        const CallPlan& pl = x.plan;
-        const int64_t rows = pl.rows;
-        mtmc::PrepParams p;
-        fill_prep_edge(x, &p);
-        // passenger jobs: operand |.|max values / operand splits of the node encoder (this rank's rows of x; the weights)
-        p.n_jobs = 0;
-        // (training forwards: the jobs also publish the tensors' |.|max -- the backward's GEMMs scale by |x|max and |W_l|max)
-        if (rows > 0) {
-          if (pl.enc_kernel[0] == MTMC_GEMM_FEW_L0)     // the planes of x, 8 rows per passenger workgroup (no |x|max: one scale per row)
-            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, c->training ? amax_x(x) : nullptr, 0, 0, mtmc::kJobSplit,
-                                  x.at<_Float16>(x.lo.xh), x.at<float>(x.lo.inv_a), nullptr};
-          else if (pl.enc_kernel[0] != MTMC_GEMM_PRESPLIT_256)
-            p.jobs[p.n_jobs++] = {c->x, rows, m->enc_node[0].in_dim, c->x_row_stride, amax_x(x), 0, 0, mtmc::kJobAmax, nullptr, nullptr, nullptr};
-          for (int l = 0; l < m->n_enc_layers; ++l) {
-            const mtmc_layer& Ll = m->enc_node[l];
-            if (pl.w_cached[l])         // layer l's planes in the cache: verify every 8-row chunk, split the ones that changed
-              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, c->training ? amax_w(x, l) : nullptr, 0, 0,
-                                    mtmc::kJobSplit, x.wc_at<_Float16>(x.cl.planes[l]), x.wc_at<float>(x.cl.inv[l]),
-                                    x.wc_at<unsigned long long>(x.cl.fp[l])};
-            else if (in_loop_kernel(pl.enc_kernel[l]))   // |W_l|max (row-streaming: in the kernel; planes without a cache: below)
-              p.jobs[p.n_jobs++] = {Ll.weight, Ll.out_dim, Ll.in_dim, Ll.in_dim, amax_w(x, l), 0, 0, mtmc::kJobAmax,
-                                    nullptr, nullptr, nullptr};
-          }
-        }
-        mtmc::launch_prep(p, s);
-        if (pl.col_blocks > 0) {        // sub-run boundaries of the column-blocked pass A, once per forward
-          const mtmc::RoundParams rp = round_params(x, 0);
-          mtmc::launch_colblock_index(rp, x.at<int>(x.lo.col_sub), rp.col_blocks, rp.cb_row_lo, rp.cb_row_hi, s);
-        }
-        // instead of the |.|max of x and W0: their fp16 planes and row scales
-        // (pipelined layer 0: the x planes are made panel by panel in MTMC_PH_NODE_ENC 0)
-        if (pl.enc_kernel[0] == MTMC_GEMM_PRESPLIT_256 && !x.pipe)
-          mtmc::launch_split_rows(c->x, c->x_row_stride, rows, m->enc_node[0].in_dim, x.at<void>(x.lo.xh),
-                                  x.at<float>(x.lo.inv_a), s);
-        for (int l = 0; l < m->n_enc_layers; ++l) {     // the weight planes of the layers whose kernels want them, unless cached
-          const mtmc_layer& Ll = m->enc_node[l];
-          if ((pl.enc_kernel[l] == MTMC_GEMM_PRESPLIT_256 || pl.enc_kernel[l] == MTMC_GEMM_STAGED_128) && !pl.w_cached[l])
-            mtmc::launch_split_rows(Ll.weight, Ll.in_dim, Ll.out_dim, Ll.in_dim, w_planes(x, l), w_inv(x, l), s);
-        }
-      }
-      break;
-    }
-    case MTMC_PH_EDGE_ENC:
-      if (c->n_edges > 0)
-        mtmc::launch_enc2(enc_params(x), c->edge_attr, c->n_edges, (double)c->n_edges_total, x.at<double>(x.lo.pub.stat_enc2_off), s);
-      break;
-    case MTMC_PH_NODE_ENC:
-    case MTMC_PH_NODE_COMBINE: {
-      if (arg < 0 || arg >= m->n_enc_layers) return fail(MTMC_E_ARG, "encoder layer %d out of range", arg);
-      if (x.plan.rows == 0) break;
-      const int k = x.plan.enc_kernel[arg];
-      if (phase == MTMC_PH_NODE_COMBINE && !in_loop_kernel(k)) break;   // only the in-loop kernel splits along K
-      int rc;
-      if (k == MTMC_GEMM_FEW_L0 || k == MTMC_GEMM_FEW_WAVE) rc = launch_enc_few(x, arg);
-      else if (k == MTMC_GEMM_PRESPLIT_256) rc = launch_enc_presplit0(x);
-      else if (k == MTMC_GEMM_STAGED_128) rc = launch_enc_staged(x, arg);
-      else rc = launch_enc_gemm(x, arg, phase);
-      if (rc) return rc;
-      break;
-    }
-    case MTMC_PH_NODE_H0: {
-      const int last = m->n_enc_layers - 1;
-      const int64_t rows = c->node_hi - c->node_lo;
-      if (rows > 0)
-        mtmc::launch_bn_relu_rows({x.at<float>(x.lo.Y[last]), MTMC_NODE_DIM, rows, MTMC_NODE_DIM,
-                                   x.at<double>(x.lo.stat_enc_layer[last]), m->enc_node[last].gamma, m->enc_node[last].beta,
-                                   (double)c->n_nodes, x.at<float>(x.lo.pub.h0_off) + (size_t)c->node_lo * MTMC_NODE_DIM,
-                                   make_drop(x, m->dropout_enc), mtmc::kDropEncNode + last, c->node_lo}, s);
-      break;
-    }
-    case MTMC_PH_ROUND_PROJ: {
-      if (arg < 0 || arg >= L) return fail(MTMC_E_ARG, "round %d out of range", arg);
-      mtmc::NodeProjParams p;
-      const int last = m->n_enc_layers - 1;
-      p.y_last = (arg == 0 && fused_h0) ? x.at<float>(x.lo.Y[last]) : nullptr;
-      p.y_stats = x.at<double>(x.lo.stat_enc_layer[last]); p.y_gamma = m->enc_node[last].gamma;
-      p.y_beta = m->enc_node[last].beta; p.y_count = (double)c->n_nodes; p.h0_out = x.at<float>(x.lo.pub.h0_off);
-      p.finalize_enc = arg == 0; p.enc = enc_params(x); p.e_total = (double)c->n_edges_total;
-      p.h_src = round_h_src(x, arg);
-      p.drop = make_drop(x, m->dropout_enc); p.drop_stream = mtmc::kDropEncNode + last;
-      p.h0 = m->reattach_nodes ? x.at<float>(x.lo.pub.h0_off) : nullptr;
-      p.deg = (m->agg == MTMC_AGG_MEAN && arg > 0) ? scale_deg(x) : nullptr;
-      p.ue_w = m->upd_edge.weight; p.ue_ld = m->upd_edge.in_dim;
-      p.un_w = m->upd_node.weight; p.un_ld = m->upd_node.in_dim;
-      p.hn = node_in_width(m);
-      p.P = round_P(x, arg); p.Q = round_Q(x, arg);
-      p.zero_buf = agg_target(x, arg);
-      p.n_nodes = c->n_nodes;
-      p.node_begin = proj_lo(c); p.node_end = proj_hi(c);
-      p.edge_deg = x.at<int>(x.lo.pub.deg_off); p.un_b = m->upd_node.bias;
-      p.z2_stats = x.plan.fold_node_stat
-                       ? x.at<double>(x.lo.pub.stat_round_off) + (size_t)arg * mtmc::kRoundBlock + mtmc::kRoundZ2Off : nullptr;
-      mtmc::launch_node_proj(p, s);
-      break;
-    }
-    case MTMC_PH_ROUND_A:
-    case MTMC_PH_ROUND_B:
-    case MTMC_PH_ROUND_C: {
-      if (arg < 0 || arg >= L) return fail(MTMC_E_ARG, "round %d out of range", arg);
-      if (c->n_edges == 0) break;
-      const mtmc::RoundParams p = round_params(x, arg);
-      if (phase == MTMC_PH_ROUND_A) mtmc::launch_pass_a(p, s);
-      else if (phase == MTMC_PH_ROUND_B) mtmc::launch_pass_b(p, s);
-      else mtmc::launch_pass_c(p, s);
-      break;
-    }
-    case MTMC_PH_ROUND_STAT: {     // few-edge lists: nothing (the statistics came out of MTMC_PH_ROUND_PROJ + MTMC_PH_ROUND_B)
-      if (arg < 0 || arg >= L) return fail(MTMC_E_ARG, "round %d out of range", arg);
-      if (x.plan.fold_node_stat) break;
-      mtmc::NodeStatParams p;
-      p.Q = round_Q(x, arg); p.deg = x.at<int>(x.lo.pub.deg_off); p.seg = x.at<double>(x.lo.pub.seg_off);
-      p.un_w = m->upd_node.weight; p.un_b = m->upd_node.bias; p.un_ld = m->upd_node.in_dim;
-      p.un_eoff = node_in_width(m);
-      p.stats = x.at<double>(x.lo.pub.stat_round_off) + (size_t)arg * mtmc::kRoundBlock;
-      p.n_nodes = c->n_nodes;
-      p.node_begin = proj_lo(c); p.node_end = proj_hi(c);
-      mtmc::launch_node_stat(p, s);
-      break;
-    }
-    case MTMC_PH_END: {
-      const float* src = round_h_src(x, L);
-      if (L == 0 || m->agg == MTMC_AGG_MEAN || x.lo.training)   // otherwise the last round aggregated into h_out
-        mtmc::launch_h_final(src, scale_deg(x), (m->agg == MTMC_AGG_MEAN && L > 0) ? 1 : 0, c->n_nodes, c->h_out, s);
-      if (L == 0 && c->n_edges > 0)
-        mtmc::launch_classify_e0(enc_params(x), c->edge_attr, c->n_edges, (double)c->n_edges_total, m->cls.weight,
-                                 m->cls.bias, m->cls.out_dim, c->logits, s);
-      break;
-    }
-    default:
-      return fail(MTMC_E_ARG, "unknown phase %d", phase);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MTMC_E_HIP, "kernel launch failed in phase %d: %s", phase, hipGetErrorString(e));
-  return MTMC_OK;
-}
 
 }  // namespace mtmc_api

@@ -2,7 +2,6 @@
 // Order: rounds L-1..0 (node-update MLP, edge-update MLP + classifier, node projections), then the edge encoder,
 // then the node encoder (BatchNorm backward + two fp32-MFMA GEMMs per layer on transposed operands).
 #include "api_internal.h"
-#include "train_kernels.h"
 
 using namespace mtmc_api;
 
@@ -214,7 +213,7 @@ int bwd_node_encoder_layer(Bwd& b, int l) {
   for (int j = 0; j < l; ++j) sb_off += 2 * (size_t)m->enc_node[j].out_dim;
   mtmc::BnBwdParams bb;
   bb.Y = x.at<float>(lo.Y[l]); bb.dA = dY; bb.rows = N; bb.dim = d;
-  bb.stats_fwd = x.at<double>(lo.stat_enc_layer[l]); bb.stats_bwd = x.at<double>(lo.bst_n) + sb_off; bb.count = (double)N;
+  bb.stats_fwd = x.at<double>(lo.pub.stat_enc_layer_off[l]); bb.stats_bwd = x.at<double>(lo.bst_n) + sb_off; bb.count = (double)N;
   bb.gamma = Lr.gamma; bb.beta = Lr.beta; bb.drop = make_drop(x, m->dropout_enc); bb.drop_stream = mtmc::kDropEncNode + l;
   bb.gr = b.gr.enc_node[l];
   // |.|max of the three GEMM operands of this layer: dY_l (written by bn_bwd's apply pass), a_{l-1} (x: the forward's
@@ -229,7 +228,7 @@ int bwd_node_encoder_layer(Bwd& b, int l) {
   const float* aT = b.tX;                                          // a_{l-1}^T [in][npad]
   if (l > 0) {
     const mtmc_layer& Pv = m->enc_node[l - 1];
-    bb.rc = {x.at<float>(lo.Y[l - 1]), Pv.out_dim, N, Pv.out_dim, x.at<double>(lo.stat_enc_layer[l - 1]), Pv.gamma, Pv.beta,
+    bb.rc = {x.at<float>(lo.Y[l - 1]), Pv.out_dim, N, Pv.out_dim, x.at<double>(lo.pub.stat_enc_layer_off[l - 1]), Pv.gamma, Pv.beta,
              (double)N, b.gB, make_drop(x, m->dropout_enc), mtmc::kDropEncNode + l - 1, 0, amax_act, tB, npad};
     bb.rc_on = mtmc::rows_t_form_takes(bb.rc) ? 1 : 0;
     aT = tB;
@@ -240,11 +239,11 @@ int bwd_node_encoder_layer(Bwd& b, int l) {
   // dW_l [d][in] = dY^T . a  -> NT GEMM on the transposes (reduction over the node rows, padded to 32)
   mtmc::GemmParams g = mtmc::plain_gemm(tA, npad, aT, zeros, b.gr.enc_node[l].w, in, d, (int)npad, in, amax_dy,
                                         l > 0 ? amax_act : amax_x(x));
-  if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "backward: weight-gradient GEMM shape");
+  if (int rc = mtmc::launch_gemm_bn(g, s)) return fail(rc, "backward: weight-gradient GEMM shape");
   // dA_{l-1} [N][in] = dY . W_l  -> NT GEMM against W^T
   if (l > 0 || b.d_x) {
     g = mtmc::plain_gemm(dY, d, b.tWl[l], zeros, l > 0 ? b.gB : b.d_x, in, N, d, in, amax_dy, amax_w(x, l));    // W_l^T [in][d]
-    if (mtmc::launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "backward: input-gradient GEMM shape");
+    if (int rc = mtmc::launch_gemm_bn(g, s)) return fail(rc, "backward: input-gradient GEMM shape");
     std::swap(b.gA, b.gB);
   }
   return MTMC_OK;

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(512) void few_l0_kernel(FewL0Params p, int tiles_m,
 bool few_l0_shape(int K, int Nout) { return K % 64 == 0 && K >= 64 && K <= 2048 && Nout % kL0BN == 0 && Nout >= kL0BN; }
 
 int launch_few_l0(const FewL0Params& p, hipStream_t s) {
-  if (p.M < 1 || !few_l0_shape(p.K, p.Nout) || !p.Ah || !p.Wh || !p.inv_a || !p.inv_w || !p.bias || !p.Y) return 1;
+  if (p.M < 1 || !few_l0_shape(p.K, p.Nout) || !p.Ah || !p.Wh || !p.inv_a || !p.inv_w || !p.bias || !p.Y) return MTMC_E_ARG;
   const int tiles_m = (int)((p.M + kL0BM - 1) / kL0BM), tiles_n = p.Nout / kL0BN;
   int cpx = tiles_n >= 8 ? (tiles_n + 7) / 8 : 0;
   int grid = cpx > 0 ? 8 * cpx * tiles_m : tiles_n * tiles_m;
@@ -460,7 +460,7 @@ int launch_few_wave(const FewWaveParams& p0, hipStream_t s) {
   FewWaveParams p = p0;
   if (p.M < 1 || !few_wave_shape(p.K, p.Nout) || !p.A || !p.Wh || !p.inv_w || !p.bias || !p.Y || !p.stats_in || !p.gamma_in ||
       !p.beta_in || (p.lda & 3) || ((uintptr_t)p.A & 15))
-    return 1;
+    return MTMC_E_ARG;
   const int nkb = few_wave_nkb(p.K), cb = few_wave_cb(p.M, p.K, p.Nout), rb = few_wave_rb(p.M, p.K, p.Nout, cb);
   const int nw = p.K / (32 * nkb);
   p.tiles = (int)((p.M + 16 * rb - 1) / (16 * rb)) * (p.Nout / (16 * cb));

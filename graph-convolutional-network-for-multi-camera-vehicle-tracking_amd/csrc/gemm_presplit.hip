@@ -276,7 +276,7 @@ int presplit_tile_rows(int64_t M, int tiles_n) {
 int launch_gemm_presplit(const SplitGemmParams& p, hipStream_t s) {
   if (p.K % 64 || p.K > 2048 || p.M < 1 || p.Nout < 1 || p.m_lo < 0 || p.m_lo >= p.M || (p.m_lo & 15) ||
       (p.M_rows > 0 && p.M_rows < p.M))
-    return 1;
+    return MTMC_E_ARG;
   const int tiles_n = (p.Nout + 255) / 256;
   const int bm = (p.bm >= 144 && p.bm <= 256 && p.bm % 16 == 0) ? p.bm : presplit_tile_rows(p.M - p.m_lo, tiles_n);
   const int tiles_m = (int)((p.M - p.m_lo + bm - 1) / bm);

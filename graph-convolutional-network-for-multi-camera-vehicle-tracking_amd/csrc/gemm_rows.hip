@@ -195,7 +195,7 @@ bool rows_layer(int64_t rows, int K, int Nout) {
 int launch_gemm_rows(const GemmParams& p, hipStream_t s) {
   if (p.M < 1 || p.K != 128 || p.Nout != 32 || !p.stats_in || !p.amax_a || p.drop_in.on || (p.lda & 3) || ((uintptr_t)p.A & 15) ||
       ((uintptr_t)p.W & 15))
-    return 1;
+    return MTMC_E_ARG;
   const int64_t groups = (p.M + 15) / 16, blocks = (groups + 3) / 4;
   // ~8 groups per wave: the per-wave prologue (weights -> fragments) is paid once per wave
   const int64_t want = (blocks + 7) / 8;

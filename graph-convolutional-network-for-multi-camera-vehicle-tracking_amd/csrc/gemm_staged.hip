@@ -451,10 +451,10 @@ static int launch_staged(const StagedGemmParams& p, hipStream_t s) {
 }
 
 int launch_gemm_staged(const StagedGemmParams& p, hipStream_t s) {
-  if (p.M < 1 || p.K % 32 || p.K < 64 || p.K > 2048 || !p.stats_in || !p.amax_a) return 1;
+  if (p.M < 1 || p.K % 32 || p.K < 64 || p.K > 2048 || !p.stats_in || !p.amax_a) return MTMC_E_ARG;
   if (p.Nout >= 256 && p.Nout % 256 == 0) return launch_staged<256, 2>(p, s);
   if (p.Nout == 128) return launch_staged<128, 4>(p, s);
-  return 1;
+  return MTMC_E_ARG;
 }
 
 }  // namespace mtmc

@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI layer (api.hip) and the kernel translation units.
+// Internal launch interface between the C-ABI layer (api.hip, api_train.hip, linear_api.hip) and the kernel translation units.
 #pragma once
 #include "../../include/mtmc_mpn.h"
 #include "common.h"
@@ -143,8 +143,11 @@ struct NodeStatParams {
 
 // ---- One linear layer of the node encoder, described in parts.  The five parameter blocks below compose them as public bases
 // (like PrepParams : PrepEdge), so a kernel reads p.A, p.Wh, p.pass_blocks, ... and a launch site fills each part once
-// (api_internal.h: fill_in / fill_out / fill_w / fill_x / ride_enc2; plain_gemm below).  Every field has a default: a block
+// (api.hip: fill_in / fill_out / fill_w / fill_x / ride_enc2; plain_gemm below).  Every field has a default: a block
 // that a site only partly fills has null pointers, zero sizes and no Dropout in the rest.
+// Their six launchers (launch_gemm_bn, launch_gemm_rows, launch_few_l0, launch_few_wave, launch_gemm_staged,
+// launch_gemm_presplit) answer alike: MTMC_OK, MTMC_E_ARG (shape or argument refused, nothing launched) or MTMC_E_HIP -- an
+// entry point hands the code on as it is, fail(rc, ...) (api_error.h).
 // The activation input with its producer's BatchNorm and Dropout
 struct ActIn {
   const float* A = nullptr; int64_t lda = 0;   // [M][K] activations (raw pre-BN outputs of the previous layer, or x)
@@ -184,7 +187,7 @@ struct GemmParams : ActIn, LayerOut, Enc2Ride {
   const unsigned* amax_a = nullptr;            // of A's source: x itself (no stats_in) or the producing layer's raw Y
   const unsigned* amax_w = nullptr;            // of W
 };
-// the two sides of a block from bare arguments (the diagnostics entry points and plain_gemm; the forward: api_internal.h)
+// the two sides of a block from bare arguments (the diagnostics entry points and plain_gemm; the forward: api.hip)
 inline void set_in(ActIn* q, const float* A, int64_t lda, const double* stats_in = nullptr, const float* gamma_in = nullptr,
                    const float* beta_in = nullptr, double count = 0) {
   q->A = A; q->lda = lda; q->stats_in = stats_in; q->gamma_in = gamma_in; q->beta_in = beta_in; q->count = count;
@@ -216,8 +219,8 @@ bool few_l0_shape(int K, int Nout);
 bool few_wave_shape(int K, int Nout);
 int few_wave_threads(int K);                // threads per workgroup launch_few_wave uses for a layer of depth K
 bool few_rows_path(int64_t rows, int n_layers, const int* in_dim, const int* out_dim);
-int launch_few_l0(const FewL0Params& p, hipStream_t s);       // 0 ok, 1 unsupported shape, MTMC_E_HIP
-int launch_few_wave(const FewWaveParams& p, hipStream_t s);   // 0 ok, 1 unsupported shape
+int launch_few_l0(const FewL0Params& p, hipStream_t s);
+int launch_few_wave(const FewWaveParams& p, hipStream_t s);
 
 // First encoder layer on pre-split operands (gemm_presplit.hip): fp16 planes [2][rows][K] and one power-of-two
 // inverse scale per row, written by launch_split_rows.
@@ -236,11 +239,11 @@ static_assert(std::is_trivially_copyable<GemmParams>::value && std::is_trivially
               std::is_trivially_copyable<FewWaveParams>::value && std::is_trivially_copyable<SplitGemmParams>::value &&
               std::is_trivially_copyable<StagedGemmParams>::value, "the blocks are passed to kernels by value");
 bool staged_layer(int64_t rows, int K, int Nout);       // many rows, K % 32 == 0, K <= 2048, Nout % 256 == 0 or (Nout == 128, rows >= 49152), not disabled
-int launch_gemm_staged(const StagedGemmParams& p, hipStream_t s);   // 0 ok, 1 unsupported shape, MTMC_E_HIP
+int launch_gemm_staged(const StagedGemmParams& p, hipStream_t s);
 int staged_tile_rows(int64_t M, int tiles_n, int wm);   // (also used by the laboratory's second form, lab/staged2_lab.hip)
 // The last, narrow encoder layers of many-row graphs as a row-streaming kernel (gemm_rows.hip): 128 -> 32
 bool rows_layer(int64_t rows, int K, int Nout);
-int launch_gemm_rows(const GemmParams& p, hipStream_t s);          // 0 ok, 1 unsupported shape
+int launch_gemm_rows(const GemmParams& p, hipStream_t s);
 void launch_split_rows(const float* X, int64_t ld, int64_t rows, int K, void* H, float* inv, hipStream_t s);
 // rows [r_lo, r_hi) only, of planes laid out for `rows` rows (X points at row 0)
 void launch_split_rows_range(const float* X, int64_t ld, int64_t rows, int K, void* H, float* inv, int64_t r_lo, int64_t r_hi,
@@ -249,9 +252,9 @@ int presplit_tile_rows(int64_t M, int tiles_n);       // tile height the layer-0
 // hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device); false when HIP refuses (gemm_bn.hip)
 bool allow_big_lds(const void* fn, int bytes);
 bool presplit_layer0(int64_t rows, int K, int Nout);   // many rows, K % 64 == 0, K <= 2048, not disabled (MTMC_GEMM_NO_PRESPLIT)
-int launch_gemm_presplit(const SplitGemmParams& p, hipStream_t s);   // 0 ok, 1 unsupported shape, MTMC_E_HIP
+int launch_gemm_presplit(const SplitGemmParams& p, hipStream_t s);
 
-// Shared by the mtmc_linear_*_raw diagnostics (api.hip) and their laboratory twins (lab/).  Their work buffer: the fp16 planes
+// Shared by the mtmc_linear_*_raw diagnostics (linear_api.hip) and their laboratory twins (lab/).  Their work buffer: the fp16 planes
 // of A (a_planes) and its [M] inverse row scales, then from the next 256-byte boundary the planes of W and its [N] scales
 struct RawWork { _Float16* Ah; float* inv_a; _Float16* Wh; float* inv_w; uint64_t bytes; };
 inline RawWork raw_work(void* work, int64_t M, int K, int N, bool a_planes) {
@@ -318,21 +321,7 @@ void launch_bn_relu_rows(const RowsTJob& j, hipStream_t s);
 // dst = src (sum/max) or src / max(deg,1) (mean)
 void launch_h_final(const float* src, const int* deg, int mean, int64_t n_nodes, float* dst, hipStream_t s);
 
-int launch_gemm_bn(const GemmParams& p, hipStream_t s, int which = 3);   // returns 0 or MTMC_E_ARG
+int launch_gemm_bn(const GemmParams& p, hipStream_t s, int which = 3);
 int gemm_plan(int64_t M, int K, int Nout, int* split_k, bool long_k_ok = false);
-
-void launch_scatter(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                    float* out, float* count, int64_t* arg_out, int mode, hipStream_t s);
-
-void launch_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                            int64_t* out, hipStream_t s);
-// the gradient of launch_scatter's out with respect to src (mode as there); count: int[dim_size] zeroed on s (mean only)
-void launch_scatter_backward(const float* g, const int64_t* arg, const int64_t* index, int64_t n_src, int64_t n_cols,
-                             int64_t dim_size, int* count, float* d_src, int mode, hipStream_t s);
-
-size_t pp_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t max_active);
-int launch_postprocess(const float* logits, const int64_t* row, const int64_t* col, int64_t idx_stride, int64_t n_nodes,
-                       int64_t n_edges, int num_cameras, int flags, int64_t max_active, float* prob1, int64_t* pred,
-                       int64_t* id_pred, int32_t* info, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 }  // namespace mtmc

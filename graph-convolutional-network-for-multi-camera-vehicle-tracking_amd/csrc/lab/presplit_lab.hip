@@ -647,7 +647,7 @@ static int launch_variant(const SplitGemmParams& p, hipStream_t s) {
 }
 
 static int launch_lab(const SplitGemmParams& p, hipStream_t s, int variant) {
-  if (p.K % 64 || p.K > 2048 || p.M < 1 || p.Nout < 1) return 1;
+  if (p.K % 64 || p.K > 2048 || p.M < 1 || p.Nout < 1) return MTMC_E_ARG;
   switch (variant) {
     case 2: return launch_variant<128, 32, 1, 3>(p, s);
     case 3: return launch_variant<128, 32, 2, 2>(p, s);
@@ -686,6 +686,6 @@ extern "C" int32_t mtmc_lab_linear_presplit_raw(const float* A, int64_t lda, con
   g.Ah = wk.Ah; g.inv_a = wk.inv_a; g.Wh = wk.Wh; g.inv_w = wk.inv_w;
   mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
   const int rc = mtmc::launch_lab(g, s, variant);
-  if (rc != 0) return rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG;
+  if (rc != MTMC_OK) return rc;
   return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
 }

@@ -362,7 +362,7 @@ __global__ __launch_bounds__(kS2NT) void gemm_staged_w_kernel(StagedGemmParams p
 }
 
 int launch_gemm_staged2(const StagedGemmParams& p, hipStream_t s) {
-  if (p.M < 1 || p.Nout < 256 || p.Nout % 256 || p.K % 64 || p.K < 128 || p.K > 2048 || !p.stats_in || !p.amax_a) return 1;
+  if (p.M < 1 || p.Nout < 256 || p.Nout % 256 || p.K % 64 || p.K < 128 || p.K > 2048 || !p.stats_in || !p.amax_a) return MTMC_E_ARG;
   const int tiles_n = p.Nout / kS2BN;
   const int bm = staged_tile_rows(p.M, tiles_n, 2);     // 80 .. 128 rows, the height that fills the last round of workgroups
   const int tiles_m = (int)((p.M + bm - 1) / bm);
@@ -375,7 +375,7 @@ int launch_gemm_staged2(const StagedGemmParams& p, hipStream_t s) {
 
 }  // namespace mtmc
 
-// The laboratory twin of mtmc_linear_staged_raw (csrc/api.hip): same arguments, the second form of the kernel.
+// The laboratory twin of mtmc_linear_staged_raw (csrc/linear_api.hip): same arguments, the second form of the kernel.
 extern "C" int32_t mtmc_lab_linear_staged2_raw(const float* A, int64_t lda, const double* stats_in, const float* gamma_in,
                                                const float* beta_in, double count, const float* W, const float* bias, float* Y,
                                                int64_t M, int32_t K, int32_t N, void* work, uint64_t work_bytes, uint32_t* scratch,
@@ -399,6 +399,6 @@ extern "C" int32_t mtmc_lab_linear_staged2_raw(const float* A, int64_t lda, cons
   g.Wh = static_cast<_Float16*>(work); g.inv_w = inv_w;
   mtmc::set_out(&g, bias, Y, N, M, K, N, stats, scratch + 2 * mtmc::kAmaxRep);
   const int rc = mtmc::launch_gemm_staged2(g, s);
-  if (rc != 0) return rc == MTMC_E_HIP ? MTMC_E_HIP : MTMC_E_ARG;
+  if (rc != MTMC_OK) return rc;
   return hipGetLastError() == hipSuccess ? MTMC_OK : MTMC_E_HIP;
 }

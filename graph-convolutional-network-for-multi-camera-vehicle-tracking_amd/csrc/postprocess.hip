@@ -702,15 +702,15 @@ static size_t pp_carve(PpParams& p, int64_t max_active, char* ws) {
   return off;
 }
 
-size_t pp_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t max_active) {
+static size_t pp_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t max_active) {
   PpParams p;
   p.n_nodes = n_nodes; p.n_edges = n_edges;
   return pp_carve(p, max_active, nullptr);
 }
 
-int launch_postprocess(const float* logits, const int64_t* row, const int64_t* col, int64_t idx_stride, int64_t n_nodes,
-                       int64_t n_edges, int num_cameras, int flags, int64_t max_active, float* prob1, int64_t* pred,
-                       int64_t* id_pred, int32_t* info, void* workspace, size_t workspace_bytes, hipStream_t s) {
+static int launch_postprocess(const float* logits, const int64_t* row, const int64_t* col, int64_t idx_stride, int64_t n_nodes,
+                              int64_t n_edges, int num_cameras, int flags, int64_t max_active, float* prob1, int64_t* pred,
+                              int64_t* id_pred, int32_t* info, void* workspace, size_t workspace_bytes, hipStream_t s) {
   PpParams p;
   p.logits = logits; p.row = row; p.col = col; p.idx_stride = idx_stride; p.n_nodes = n_nodes; p.n_edges = n_edges;
   p.num_cameras = num_cameras; p.flags = flags; p.prob1 = prob1; p.pred = pred; p.id_pred = id_pred; p.info = info;

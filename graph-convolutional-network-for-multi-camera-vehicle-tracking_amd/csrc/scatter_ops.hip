@@ -5,6 +5,7 @@
 //   add : out zero-filled, out[index[e], c] += src[e, c]
 //   mean: add, then divide by max(count, 1)
 //   max : per-column maximum, rows nobody writes stay 0, argmax = smallest e attaining it (E if none)
+#include "api_error.h"
 #include "kernels.h"
 #include <limits.h>
 
@@ -86,8 +87,8 @@ __global__ void scatter_add_i64_kernel(const int64_t* src, const int64_t* index,
 constexpr int kScatterBlocks = 4096;      // most workgroups (of 256 elements) of a launch
 
 // mode 0 add, 1 mean, 2 max
-void launch_scatter(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                    float* out, float* count, int64_t* arg_out, int mode, hipStream_t s) {
+static void launch_scatter(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                           float* out, float* count, int64_t* arg_out, int mode, hipStream_t s) {
   const int64_t n_out = dim_size * n_cols, n_in = n_src * n_cols;
   const dim3 g_out(blocks_for(n_out, 256, kScatterBlocks)), g_in(blocks_for(n_in, 256, kScatterBlocks));
   if (mode == 2) {
@@ -110,8 +111,8 @@ void launch_scatter(const float* src, const int64_t* index, int64_t n_src, int64
   if (mode == 1) hipLaunchKernelGGL(scatter_div_kernel, g_out, dim3(256), 0, s, out, count, dim_size, n_cols);
 }
 
-void launch_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
-                            int64_t* out, hipStream_t s) {
+static void launch_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                                   int64_t* out, hipStream_t s) {
   const int64_t n_out = dim_size * n_cols, n_in = n_src * n_cols;
   hipLaunchKernelGGL(scatter_fill_i64_kernel, dim3(blocks_for(n_out, 256, kScatterBlocks)), dim3(256), 0, s, out, n_out, (int64_t)0);
   if (n_in > 0)
@@ -234,8 +235,8 @@ static void launch_scatter_backward_as(const float* g, const int64_t* arg, const
 }
 
 // mode 0 add, 1 mean, 2 max; n_src, n_cols >= 1.  count: int[dim_size], zeroed by the caller on this stream (mean only)
-void launch_scatter_backward(const float* g, const int64_t* arg, const int64_t* index, int64_t n_src, int64_t n_cols,
-                             int64_t dim_size, int* count, float* d_src, int mode, hipStream_t s) {
+static void launch_scatter_backward(const float* g, const int64_t* arg, const int64_t* index, int64_t n_src, int64_t n_cols,
+                                    int64_t dim_size, int* count, float* d_src, int mode, hipStream_t s) {
   if (dim_size == 0) {                                     // every row is out of range, and g has none to read
     const int64_t n = n_src * n_cols;
     hipLaunchKernelGGL(scatter_fill_kernel, dim3(blocks_for(n, 256, kScatterBlocks)), dim3(256), 0, s, d_src, n, 0);
@@ -261,3 +262,73 @@ void launch_scatter_backward(const float* g, const int64_t* arg, const int64_t* 
 }
 
 }  // namespace mtmc
+
+extern "C" {
+
+using mtmc_api::fail;
+using mtmc_api::launched;
+
+static int scatter_common(const char* entry, const float* src, const int64_t* index, int64_t n_src, int64_t n_cols,
+                          int64_t dim_size, float* out, float* count, int64_t* arg_out, int mode, void* stream) {
+  if (n_src < 0 || n_cols < 1 || dim_size < 0 || !out || (n_src > 0 && (!src || !index)))
+    return fail(MTMC_E_ARG, "%s: n_src and dim_size must be >= 0, n_cols >= 1, and out (with rows: src and index) not NULL", entry);
+  if (mode == 1 && !count) return fail(MTMC_E_ARG, "%s: needs count_scratch[dim_size]", entry);
+  if (dim_size == 0) return MTMC_OK;
+  mtmc::launch_scatter(src, index, n_src, n_cols, dim_size, out, count, arg_out, mode, static_cast<hipStream_t>(stream));
+  return launched(entry);
+}
+int32_t mtmc_scatter_add(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                         float* out, void* stream) {
+  return scatter_common("scatter_add", src, index, n_src, n_cols, dim_size, out, nullptr, nullptr, 0, stream);
+}
+int32_t mtmc_scatter_add_i64(const int64_t* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                             int64_t* out, void* stream) {
+  if (n_src < 0 || n_cols < 1 || dim_size < 0 || !out || (n_src > 0 && (!src || !index)))
+    return fail(MTMC_E_ARG, "scatter_add_i64: n_src and dim_size must be >= 0, n_cols >= 1, and out (with rows: src and index) not NULL");
+  if (dim_size == 0) return MTMC_OK;
+  mtmc::launch_scatter_add_i64(src, index, n_src, n_cols, dim_size, out, static_cast<hipStream_t>(stream));
+  return launched("scatter_add_i64");
+}
+int32_t mtmc_scatter_mean(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                          float* out, float* count_scratch, void* stream) {
+  return scatter_common("scatter_mean", src, index, n_src, n_cols, dim_size, out, count_scratch, nullptr, 1, stream);
+}
+int32_t mtmc_scatter_max(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                         float* out, int64_t* arg_out, void* stream) {
+  return scatter_common("scatter_max", src, index, n_src, n_cols, dim_size, out, nullptr, arg_out, 2, stream);
+}
+
+static int scatter_backward_common(const char* entry, const float* grad_out, const int64_t* arg, const int64_t* index,
+                                   int64_t n_src, int64_t n_cols, int64_t dim_size, int32_t* count, float* grad_src, int mode,
+                                   void* stream) {
+  if (n_src < 0 || n_cols < 0 || dim_size < 0) return fail(MTMC_E_ARG, "%s: n_src, n_cols and dim_size must be >= 0", entry);
+  if (n_src == 0 || n_cols == 0) return MTMC_OK;
+  // (without destination rows there is no gradient to read: every row of grad_src is zero)
+  if (!index || !grad_src || (dim_size > 0 && !grad_out)) return fail(MTMC_E_ARG, "%s: NULL grad_out, index or grad_src", entry);
+  if (mode == 2 && dim_size > 0 && !arg) return fail(MTMC_E_ARG, "%s: NULL arg", entry);
+  if (mode == 1 && dim_size > 0 && !count) return fail(MTMC_E_ARG, "%s: needs count_scratch[dim_size]", entry);
+  if ((((uintptr_t)grad_out | (uintptr_t)grad_src | (uintptr_t)count) & 3) || (((uintptr_t)index | (uintptr_t)arg) & 7))
+    return fail(MTMC_E_ARG, "%s: grad_out, grad_src and count_scratch must be 4-byte, index and arg 8-byte aligned", entry);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mode == 1 && dim_size > 0 && hipMemsetAsync(count, 0, (size_t)dim_size * sizeof(int32_t), s) != hipSuccess)
+    return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
+  mtmc::launch_scatter_backward(grad_out, arg, index, n_src, n_cols, dim_size, count, grad_src, mode, s);
+  return launched(entry);
+}
+int32_t mtmc_scatter_add_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                                  float* grad_src, void* stream) {
+  return scatter_backward_common("scatter_add_backward", grad_out, nullptr, index, n_src, n_cols, dim_size, nullptr, grad_src, 0,
+                                 stream);
+}
+int32_t mtmc_scatter_mean_backward(const float* grad_out, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
+                                   int32_t* count_scratch, float* grad_src, void* stream) {
+  return scatter_backward_common("scatter_mean_backward", grad_out, nullptr, index, n_src, n_cols, dim_size, count_scratch,
+                                 grad_src, 1, stream);
+}
+int32_t mtmc_scatter_max_backward(const float* grad_out, const int64_t* arg, const int64_t* index, int64_t n_src, int64_t n_cols,
+                                  int64_t dim_size, float* grad_src, void* stream) {
+  return scatter_backward_common("scatter_max_backward", grad_out, arg, index, n_src, n_cols, dim_size, nullptr, grad_src, 2,
+                                 stream);
+}
+
+}  // extern "C"

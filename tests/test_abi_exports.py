@@ -91,6 +91,64 @@ def test_struct_sizes_match_the_header(tmp_path):
     assert got == [ctypes.sizeof(_lib.Model), ctypes.sizeof(_lib.Call), ctypes.sizeof(_lib.WsLayout), ctypes.sizeof(_lib.Plan)]
 
 
+def _header_without_comments():
+    text = open(os.path.join(ROOT, "include", "mtmc_mpn.h")).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def _ctype_choices(decl, mirrors):
+    """The ctypes types that may stand for one C parameter or return declaration (its name, if any, already cut off)."""
+    words = decl.replace("const", " ").replace("*", " * ").split()
+    if words == ["char", "*"]:
+        return [ctypes.c_char_p]                            # (a return value: the error text)
+    if "*" in words:
+        if words.count("*") == 1 and words[0] in mirrors:
+            return [ctypes.POINTER(mirrors[words[0]]), ctypes.c_void_p]
+        return [ctypes.c_void_p]
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64,
+               "float": ctypes.c_float, "double": ctypes.c_double}
+    assert len(words) == 1 and words[0] in scalars, f"a type this test does not know: {decl!r}"
+    return [scalars[words[0]]]
+
+
+def test_bindings_match_the_header():
+    """Every prototype `ret mtmc_name(params);` of the header has an entry of _lib.SIGNATURES with that return type and
+    exactly those argument types, no entry lacks a prototype, and every constant _lib.py mirrors has the header's value.
+    No library and no GPU: a c_int32 where the header says int64_t would otherwise be silent memory corruption."""
+    from mtmc_mpn import _lib
+    text = _header_without_comments()
+    mirrors = {"mtmc_layer": _lib.Layer, "mtmc_mpn_model": _lib.Model, "mtmc_mpn_call": _lib.Call,
+               "mtmc_ws_layout": _lib.WsLayout, "mtmc_mpn_plan": _lib.Plan}
+    protos = re.findall(r"^([\w ]+?\**)\s*\b(mtmc_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)
+    assert len(protos) >= 51 and len({name for _, name, _ in protos}) == len(protos)
+    for ret, name, params in protos:
+        assert name in _lib.SIGNATURES, f"{name}: declared in the header, no entry in _lib.SIGNATURES"
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype in _ctype_choices(ret, mirrors), f"{name}: returns {ret!r}, bound as {restype}"
+        params = [] if params.strip() in ("", "void") else [re.sub(r"\w+\s*$", "", p.strip()) for p in params.split(",")]
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters, {len(argtypes)} bound"
+        for i, (decl, got) in enumerate(zip(params, argtypes)):
+            assert got in _ctype_choices(decl, mirrors), f"{name}: parameter {i} is {decl.strip()!r}, bound as {got}"
+    assert set(_lib.SIGNATURES) == {name for _, name, _ in protos} and _lib.EXPORTS == list(_lib.SIGNATURES)
+
+    # the constants: `#define MTMC_X <expression of integers and earlier constants>` and `MTMC_X = <integer>` inside an enum
+    values = {}
+    for name, expr in re.findall(r"^#define[ \t]+(MTMC_\w+)[ \t]+(\S[^\n]*)$", text, flags=re.M):
+        values[name] = eval(expr, {"__builtins__": {}}, dict(values))
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for name, value in re.findall(r"\b(MTMC_\w+)\s*=\s*(-?\d+)", body):
+            values[name] = int(value)
+    assert values["MTMC_MPN_ABI_VERSION"] == _lib.ABI_VERSION
+    assert _lib.AGG == {"sum": values["MTMC_AGG_SUM"], "mean": values["MTMC_AGG_MEAN"], "max": values["MTMC_AGG_MAX"]}
+    mirrored = {name: value for name, value in values.items() if hasattr(_lib, name[len("MTMC_"):])}
+    for name, value in mirrored.items():
+        assert getattr(_lib, name[len("MTMC_"):]) == value, name
+    # ... and none of them has dropped out of the comparison by a change of name on either side: every upper-case integer
+    # of _lib.py is one of the header's, except the one limit the header only states in prose
+    ints = {k for k, v in vars(_lib).items() if k.isupper() and not k.startswith("_") and type(v) is int}
+    assert ints - {"ABI_VERSION", "CLUSTER_SCORES_MAX_N"} == {name[len("MTMC_"):] for name in mirrored}
+
+
 def test_header_is_plain_c(tmp_path):
     """include/mtmc_mpn.h is a C ABI: it must compile as C99 (and C++11) on its own."""
     import shutil
