@@ -1,8 +1,11 @@
-// build_graph(k=...): the cross-camera list of graph_build.hip thinned to a symmetric k-nearest list (the
-// reference's authors left the same idea as a commented-out block, inference.py:415-441).
+// build_graph(k=..., start_frames=..., max_gap=...): the cross-camera list of graph_build.hip thinned by a temporal gate, to
+// a symmetric k-nearest list, or both (the reference's authors left both ideas as one commented-out
+// block, inference.py:415-441).
+//     cand(i, j) = j is in another camera than i, and |start_i - start_j| < max_gap where a gate is given (:420-441)
 //     key(i, j)  = the cosine distance edge_attr[e][1] that the dense builder writes for the directed edge (i, j)
-//     top_i      = the first min(k, n_out(i)) cross-camera nodes j of row i in the order (key, j) ascending
+//     top_i      = the first min(k, n_cand(i)) candidates j of row i in the order (key, j) ascending
 //     keep (i,j) iff j in top_i or i in top_j            -- a union: symmetric whether or not G[i][j] == G[j][i] bitwise
+//     k == 0     : keep (i, j) iff cand(i, j); no selection and no bit matrix
 // Kept edges appear in the dense list's order with the dense list's bits (gb_edge_attr, graph_build.h) and carry their dense
 // position in edge_pos.  Only G and an N x N BIT matrix are N^2-sized; the dense edge arrays are never formed.
 //     gk_select_kernel   one workgroup per row: radix select of the k-th (key, j), then bit (i, j) and bit (j, i) per pick
@@ -16,7 +19,9 @@ namespace mtmc {
 
 struct KnnParams {
   EdgeBuildParams e;          // camera tables, G, row norms, labels; the edge outputs hold `capacity` edges
-  int k; int64_t capacity;
+  int k; int64_t capacity;    // k == 0: the gate alone, `bits` is not touched
+  const int64_t* start;       // [N] first frame of every tracklet; null: no gate
+  int64_t max_gap;            // cand(i, j) needs |start[i] - start[j]| < max_gap
   unsigned* bits;             // bit i * N + j: edge (i, j) is kept
   int64_t* row_off;           // [N] by in_list position: kept edges of the row, then (scanned in place) its first output slot
   int64_t* edge_pos;          // [capacity]: dense position of every kept edge
@@ -35,9 +40,17 @@ __device__ __forceinline__ bool knn_row(const EdgeBuildParams& p, int64_t q, Knn
   return r->i >= 0 && r->i < p.n_nodes;
 }
 
-// order-preserving uint32 image of key(i, j); false where j is no node
-__device__ __forceinline__ bool knn_key(const EdgeBuildParams& p, int i, int j, uint32_t* u) {
-  if (j < 0 || j >= p.n_nodes) return false;
+// the temporal gate of the node pair (i, j); symmetric in i and j
+__device__ __forceinline__ bool knn_gate(const KnnParams& p, int i, int j) {
+  if (!p.start) return true;
+  const int64_t a = p.start[i], b = p.start[j];
+  return (a > b ? (uint64_t)a - (uint64_t)b : (uint64_t)b - (uint64_t)a) < (uint64_t)p.max_gap;   // no overflow at any starts
+}
+
+// order-preserving uint32 image of key(i, j); false where j is no candidate: no node, or outside the gate
+__device__ __forceinline__ bool knn_key(const KnnParams& kp, int i, int j, uint32_t* u) {
+  if (j < 0 || j >= kp.e.n_nodes || !knn_gate(kp, i, j)) return false;
+  const EdgeBuildParams& p = kp.e;
   const float key = gb_edge_attr(p.G[(int64_t)i * p.n_nodes + j], p.row_sq[i], p.row_sq[j], p.row_sum[i], p.row_sum[j], p.f).y;
   const uint32_t b = __float_as_uint(key);
   *u = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
@@ -51,6 +64,12 @@ __device__ __forceinline__ void knn_set(unsigned* bits, int64_t n, int i, int j)
 __device__ __forceinline__ bool knn_get(const unsigned* bits, int64_t n, int i, int j) {
   const int64_t b = (int64_t)i * n + j;
   return (bits[b >> 5] >> (b & 31)) & 1u;
+}
+// edge (i, j) is in the result: its bit where rows selected (the gate is symmetric, so only candidates have bits), the
+// candidate test itself where the gate stands alone.  p.k is uniform over the grid.
+__device__ __forceinline__ bool knn_kept(const KnnParams& p, int i, int j) {
+  if (j < 0 || j >= p.e.n_nodes) return false;
+  return p.k ? knn_get(p.bits, p.e.n_nodes, i, j) : knn_gate(p, i, j);
 }
 
 // exclusive prefix of v over the 256 threads of the workgroup in thread order, *total = the sum; smem: 4 ints.
@@ -73,7 +92,8 @@ __device__ __forceinline__ int block_excl_scan(int v, int* smem, int* total) {
 // Radix select over the key images, most significant byte first: after pass b, `prefix` holds the top 8 (b + 1) bits of the
 // k-th smallest image and `want` its rank among the keys that share them.  The row is read again on every pass (184 KB at
 // the most: it stays in L2).  After four passes `want` of the keys equal to the k-th are admitted with every smaller one;
-// out_list ascends, so a prefix count in sweep order admits the lowest columns first.
+// out_list ascends, so a prefix count in sweep order admits the lowest columns first.  Only candidates have a key
+// (knn_key): with a gate the row ranks what passes it, want = min(k, candidates), and a row without any sets no bit.
 __global__ __launch_bounds__(256) void gk_select_kernel(KnnParams p) {
   __shared__ int hist[256];
   __shared__ int scan_s[4];
@@ -88,7 +108,7 @@ __global__ __launch_bounds__(256) void gk_select_kernel(KnnParams p) {
     __syncthreads();
     for (int t = threadIdx.x; t < r.n_out; t += 256) {
       uint32_t u;
-      if (knn_key(p.e, r.i, r.ol[t], &u) && (u & mask) == prefix) atomicAdd(&hist[(u >> shift) & 255], 1);
+      if (knn_key(p, r.i, r.ol[t], &u) && (u & mask) == prefix) atomicAdd(&hist[(u >> shift) & 255], 1);
     }
     __syncthreads();
     const int h = hist[threadIdx.x];
@@ -111,7 +131,7 @@ __global__ __launch_bounds__(256) void gk_select_kernel(KnnParams p) {
     uint32_t u = 0;
     int j = -1;
     bool ok = false;
-    if (t < r.n_out) { j = r.ol[t]; ok = knn_key(p.e, r.i, j, &u); }
+    if (t < r.n_out) { j = r.ol[t]; ok = knn_key(p, r.i, j, &u); }
     const bool eq = ok && u == prefix;
     int total;
     const int rank = block_excl_scan(eq ? 1 : 0, scan_s, &total);
@@ -128,10 +148,8 @@ __global__ __launch_bounds__(256) void gk_count_kernel(KnnParams p) {
   KnnRow r;
   int c = 0;
   if (knn_row(p.e, blockIdx.x, &r))
-    for (int t = threadIdx.x; t < r.n_out; t += 256) {
-      const int j = r.ol[t];
-      if (j >= 0 && j < p.e.n_nodes && knn_get(p.bits, p.e.n_nodes, r.i, j)) ++c;
-    }
+    for (int t = threadIdx.x; t < r.n_out; t += 256)
+      if (knn_kept(p, r.i, r.ol[t])) ++c;
   int total;
   block_excl_scan(c, scan_s, &total);
   if (threadIdx.x == 0) p.row_off[blockIdx.x] = total;
@@ -163,7 +181,7 @@ __global__ __launch_bounds__(256) void gk_fill_kernel(KnnParams p) {
     const int t = t0 + threadIdx.x;
     int j = -1;
     bool kept = false;
-    if (t < r.n_out) { j = r.ol[t]; kept = j >= 0 && j < p.e.n_nodes && knn_get(p.bits, p.e.n_nodes, r.i, j); }
+    if (t < r.n_out) { j = r.ol[t]; kept = knn_kept(p, r.i, j); }
     int total;
     const int64_t pos = at + block_excl_scan(kept ? 1 : 0, scan_s, &total);
     if (kept && pos < p.capacity) {
@@ -191,12 +209,61 @@ KnnLayout knn_layout(int64_t n, int f) {
   l.total = up256(l.row_off + (size_t)n * sizeof(int64_t));
   return l;
 }
+// The one body of mtmc_build_graph_knn (start == null, k >= 1) and mtmc_build_graph_gated (start given, k >= 0); each entry
+// has checked its own k / gate arguments.  `entry` heads the messages.
+int knn_build(const char* entry, const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
+              const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
+              const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels, float* x_out,
+              int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, const int64_t* start, int64_t max_gap,
+              int32_t k, int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out, void* workspace,
+              size_t workspace_bytes, void* stream) {
+  using mtmc_api::fail;
+  using mtmc_api::launched;
+  int rc = mtmc::graph_check_args(entry, feats, feat_row_stride, n_nodes, feat_dim, in_list, in_off, out_list, out_off,
+                                  block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out,
+                                  edge_labels_out, workspace);
+  if (rc != MTMC_OK) return rc;
+  if (edge_capacity < 0) return fail(MTMC_E_ARG, "%s: edge_capacity must be >= 0", entry);
+  if (!n_kept_out || (n_edges > 0 && !edge_pos_out))
+    return fail(MTMC_E_ARG, "%s: NULL n_kept_out, or NULL edge_pos_out with n_edges > 0", entry);
+  if (((uintptr_t)edge_index_out & 15) || ((uintptr_t)edge_attr_out & 7))
+    return fail(MTMC_E_ARG, "%s: edge_index_out must be 16-byte and edge_attr_out 8-byte aligned", entry);
+  const KnnLayout l = knn_layout(n_nodes, feat_dim);
+  if (!workspace || workspace_bytes < l.total)
+    return fail(MTMC_E_WORKSPACE, "%s: workspace has %zu bytes, %zu needed (mtmc_graph_knn_workspace_bytes)", entry,
+                workspace ? workspace_bytes : (size_t)0, l.total);
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  rc = mtmc::graph_normalize_gram(entry, feats, feat_row_stride, n_nodes, feat_dim, l2norm, x_out, ws, l.g, n_edges > 0, s);
+  if (rc != MTMC_OK) return rc;
+  if (n_edges <= 0) {
+    if (hipMemsetAsync(n_kept_out, 0, sizeof(int64_t), s) != hipSuccess) return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
+    return launched(entry);
+  }
+  mtmc::KnnParams p;
+  p.e.in_list = in_list; p.e.in_off = in_off; p.e.out_list = out_list; p.e.out_off = out_off; p.e.block_off = block_off;
+  p.e.n_cams = n_cams; p.e.n_nodes = n_nodes; p.e.n_edges = n_edges; p.e.f = feat_dim;
+  p.e.G = reinterpret_cast<float*>(ws + l.g.G); p.e.row_sq = reinterpret_cast<float*>(ws + l.g.row_sq);
+  p.e.row_sum = reinterpret_cast<float*>(ws + l.g.row_sum); p.e.node_labels = node_labels;
+  p.e.edge_index = edge_index_out; p.e.edge_attr = edge_attr_out; p.e.edge_labels = edge_labels_out;
+  p.k = k; p.capacity = edge_capacity; p.start = start; p.max_gap = max_gap;
+  p.bits = reinterpret_cast<unsigned*>(ws + l.bits); p.row_off = reinterpret_cast<int64_t*>(ws + l.row_off);
+  p.edge_pos = edge_pos_out;
+  const dim3 rows((unsigned)n_nodes), wg(256);
+  if (k > 0) {                                    // k == 0: the gate alone, decided per column in count and fill
+    if (hipMemsetAsync(p.bits, 0, l.bits_bytes, s) != hipSuccess) return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
+    hipLaunchKernelGGL(mtmc::gk_select_kernel, rows, wg, 0, s, p);
+  }
+  hipLaunchKernelGGL(mtmc::gk_count_kernel, rows, wg, 0, s, p);
+  hipLaunchKernelGGL(mtmc::gk_scan_kernel, dim3(1), wg, 0, s, p.row_off, n_nodes, n_kept_out);
+  hipLaunchKernelGGL(mtmc::gk_fill_kernel, rows, wg, 0, s, p);
+  return launched(entry);
+}
 }  // namespace
 
 extern "C" {
 
 using mtmc_api::fail;
-using mtmc_api::launched;
 
 size_t mtmc_graph_knn_workspace_bytes(int64_t n_nodes, int32_t feat_dim) {
   if (n_nodes < 1 || n_nodes > 46000 || feat_dim < 32) return 0;
@@ -209,45 +276,24 @@ int32_t mtmc_build_graph_knn(const float* feats, int64_t feat_row_stride, int64_
                              float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
                              int32_t k, int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
                              void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = mtmc::graph_check_args("build_graph_knn", feats, feat_row_stride, n_nodes, feat_dim, in_list, in_off, out_list,
-                                  out_off, block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out,
-                                  edge_labels_out, workspace);
-  if (rc != MTMC_OK) return rc;
-  if (k < 1 || edge_capacity < 0) return fail(MTMC_E_ARG, "build_graph_knn: k must be >= 1 and edge_capacity >= 0");
-  if (!n_kept_out || (n_edges > 0 && !edge_pos_out))
-    return fail(MTMC_E_ARG, "build_graph_knn: NULL n_kept_out, or NULL edge_pos_out with n_edges > 0");
-  if (((uintptr_t)edge_index_out & 15) || ((uintptr_t)edge_attr_out & 7))
-    return fail(MTMC_E_ARG, "build_graph_knn: edge_index_out must be 16-byte and edge_attr_out 8-byte aligned");
-  const KnnLayout l = knn_layout(n_nodes, feat_dim);
-  if (!workspace || workspace_bytes < l.total)
-    return fail(MTMC_E_WORKSPACE, "build_graph_knn: workspace has %zu bytes, %zu needed (mtmc_graph_knn_workspace_bytes)",
-                workspace ? workspace_bytes : (size_t)0, l.total);
-  char* ws = static_cast<char*>(workspace);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  rc = mtmc::graph_normalize_gram("build_graph_knn", feats, feat_row_stride, n_nodes, feat_dim, l2norm, x_out, ws, l.g,
-                                  n_edges > 0, s);
-  if (rc != MTMC_OK) return rc;
-  if (n_edges <= 0) {
-    if (hipMemsetAsync(n_kept_out, 0, sizeof(int64_t), s) != hipSuccess)
-      return fail(MTMC_E_HIP, "build_graph_knn: hipMemsetAsync failed");
-    return launched("build_graph_knn");
-  }
-  mtmc::KnnParams p;
-  p.e.in_list = in_list; p.e.in_off = in_off; p.e.out_list = out_list; p.e.out_off = out_off; p.e.block_off = block_off;
-  p.e.n_cams = n_cams; p.e.n_nodes = n_nodes; p.e.n_edges = n_edges; p.e.f = feat_dim;
-  p.e.G = reinterpret_cast<float*>(ws + l.g.G); p.e.row_sq = reinterpret_cast<float*>(ws + l.g.row_sq);
-  p.e.row_sum = reinterpret_cast<float*>(ws + l.g.row_sum); p.e.node_labels = node_labels;
-  p.e.edge_index = edge_index_out; p.e.edge_attr = edge_attr_out; p.e.edge_labels = edge_labels_out;
-  p.k = k; p.capacity = edge_capacity;
-  p.bits = reinterpret_cast<unsigned*>(ws + l.bits); p.row_off = reinterpret_cast<int64_t*>(ws + l.row_off);
-  p.edge_pos = edge_pos_out;
-  if (hipMemsetAsync(p.bits, 0, l.bits_bytes, s) != hipSuccess) return fail(MTMC_E_HIP, "build_graph_knn: hipMemsetAsync failed");
-  const dim3 rows((unsigned)n_nodes), wg(256);
-  hipLaunchKernelGGL(mtmc::gk_select_kernel, rows, wg, 0, s, p);
-  hipLaunchKernelGGL(mtmc::gk_count_kernel, rows, wg, 0, s, p);
-  hipLaunchKernelGGL(mtmc::gk_scan_kernel, dim3(1), wg, 0, s, p.row_off, n_nodes, n_kept_out);
-  hipLaunchKernelGGL(mtmc::gk_fill_kernel, rows, wg, 0, s, p);
-  return launched("build_graph_knn");
+  if (k < 1) return fail(MTMC_E_ARG, "build_graph_knn: k must be >= 1");
+  return knn_build("build_graph_knn", feats, feat_row_stride, n_nodes, feat_dim, l2norm, in_list, in_off, out_list, out_off,
+                   block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out, edge_labels_out, nullptr, 0,
+                   k, edge_capacity, edge_pos_out, n_kept_out, workspace, workspace_bytes, stream);
+}
+
+int32_t mtmc_build_graph_gated(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
+                               const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
+                               const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
+                               float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                               const int64_t* start_frames, int64_t max_gap, int32_t k,
+                               int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (!start_frames || max_gap < 1 || k < 0)
+    return fail(MTMC_E_ARG, "build_graph_gated: NULL start_frames, max_gap < 1 or k < 0");
+  return knn_build("build_graph_gated", feats, feat_row_stride, n_nodes, feat_dim, l2norm, in_list, in_off, out_list, out_off,
+                   block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out, edge_labels_out, start_frames,
+                   max_gap, k, edge_capacity, edge_pos_out, n_kept_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -37,17 +37,75 @@ def camera_tables(cam_ids):
             np.asarray(out_off, dtype=np.int64), np.asarray(block_off, dtype=np.int64), len(uniq))
 
 
-def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None):
+FRAME_LIMIT = 1 << 62           # |start frame| at the most, so that no difference of two leaves int64
+_GAP_LIMIT = (1 << 63) - 1
+
+
+def _start_frames(start_frames, n):
+    """N start frames as an int64 numpy array; RuntimeError for anything but N host integers within +-FRAME_LIMIT."""
+    if isinstance(start_frames, torch.Tensor):
+        if start_frames.is_cuda:
+            raise RuntimeError("mtmc_mpn.build_graph: start_frames live on the host, like cam_ids")
+        start_frames = start_frames.numpy()
+    s = np.asarray(start_frames)
+    if s.dtype.kind not in "iu" or s.ndim != 1:
+        raise RuntimeError("mtmc_mpn.build_graph: start_frames must be a one-dimensional list / array / CPU tensor of integers")
+    if s.shape[0] != n:
+        raise RuntimeError("mtmc_mpn.build_graph: one start frame per node expected")
+    if s.size and (int(s.max()) > FRAME_LIMIT or int(s.min()) < -FRAME_LIMIT):
+        raise RuntimeError("mtmc_mpn.build_graph: start_frames must lie within +-2^62")
+    return np.ascontiguousarray(s, dtype=np.int64)
+
+
+def _max_gap(max_gap):
+    if isinstance(max_gap, bool) or not isinstance(max_gap, (int, np.integer)) or not 1 <= max_gap <= _GAP_LIMIT:
+        raise RuntimeError("mtmc_mpn.build_graph: max_gap must be an integer >= 1")
+    return int(max_gap)
+
+
+def _pairs_inside(u, gap):
+    """Unordered pairs {a, b} of entries of `u` (uint64) with |u_a - u_b| < gap: in sorted order, for every entry the later
+    ones below it + gap.  The queries ascend with the array they search, and u + gap < 2^64."""
+    u = np.sort(u)
+    below = np.searchsorted(u, u + gap, side="left")          # > own index: gap >= 1
+    return int(below.sum()) - u.size * (u.size + 1) // 2
+
+
+def _gated_count(cams, starts, gap):
+    u = starts.astype(np.uint64) + np.uint64(FRAME_LIMIT)     # order-preserving image in [0, 2^63] (the sum wraps back)
+    gap = np.uint64(gap)
+    pairs = _pairs_inside(u, gap)                             # all pairs inside the window ...
+    for c in np.unique(cams):
+        pairs -= _pairs_inside(u[cams == c], gap)             # ... less those of one camera
+    return 2 * pairs                                          # both directions
+
+
+def gated_edge_count(cam_ids, start_frames, max_gap) -> int:
+    """The exact length of the list `build_graph(..., start_frames=, max_gap=)` returns without `k`: the directed pairs
+    (i, j) in different cameras with |start_i - start_j| < max_gap.  Host only, O(N log N) per camera: sorted starts and
+    `searchsorted` -- the pairs inside the window among all nodes, less those inside it within each camera."""
+    cams = np.asarray(cam_ids)
+    return _gated_count(cams, _start_frames(start_frames, cams.shape[0]), _max_gap(max_gap))
+
+
+def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None, starts=None, max_gap=None):
     """The raw library call: (x, edge_pairs [E,2], edge_attr, edge_labels, labels_dev, edge_pos) and what a backward needs
     again.  k=None: `mtmc_build_graph`, the reference's list (edge_pos None).  k given: `mtmc_build_graph_knn`; the edge
     outputs are allocated at min(E_dense, 2 k N) and narrowed to the E_k the device reports -- one host read-back (the host
-    builds the camera tables anyway).  `e` in the second tuple is the DENSE list's length either way: the backward's."""
+    builds the camera tables anyway).  starts (int64 array) / max_gap given: `mtmc_build_graph_gated`; the host counts the
+    gated list (`_gated_count`), so without k the outputs are allocated at exactly E_g and nothing is read back, and with
+    k at min(E_g, 2 k N) before the same read-back.  `e` in the second tuple is the DENSE list's length in every form:
+    the backward's."""
     n, f = node_feats.shape
     dev = node_feats.device
     feats = node_feats if (node_feats.stride(1) == 1 and node_feats.stride(0) % 4 == 0) else node_feats.contiguous()
     in_list, in_off, out_list, out_off, block_off, n_cams = camera_tables(cam_ids)
     e = int(block_off[-1])
-    cap = e if k is None else min(e, 2 * min(k, n) * n)
+    thinned = k is not None or starts is not None
+    cap = e if starts is None else _gated_count(np.asarray(cam_ids), starts, max_gap)
+    if k is not None:
+        cap = min(cap, 2 * min(k, n) * n)
+    e_call = e if cap else 0                                  # an empty gate: x alone, as with one camera
     lib = _lib.load()
     up = lambda a: torch.from_numpy(a).to(dev)
     t_in, t_inoff, t_out, t_outoff, t_blk = up(in_list), up(in_off), up(out_list), up(out_off), up(block_off)
@@ -58,23 +116,29 @@ def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None)
     edge_pairs = torch.empty((cap, 2), dtype=torch.int64, device=dev)
     edge_attr = torch.empty((cap, 2), dtype=torch.float32, device=dev)
     edge_labels = torch.empty((cap,), dtype=torch.float32, device=dev) if labels_dev is not None else None
-    need = lib.mtmc_graph_workspace_bytes(n, f) if k is None else lib.mtmc_graph_knn_workspace_bytes(n, f)
+    need = lib.mtmc_graph_knn_workspace_bytes(n, f) if thinned else lib.mtmc_graph_workspace_bytes(n, f)
     if need == 0:
         raise RuntimeError("mtmc_mpn.build_graph: unsupported size")
     ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
     shared = (feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
-              t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
-              n_cams, e, labels_dev.data_ptr() if labels_dev is not None else None,
-              x.data_ptr(), edge_pairs.data_ptr() if e else None, edge_attr.data_ptr() if e else None,
+              t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e_call else None, t_outoff.data_ptr(), t_blk.data_ptr(),
+              n_cams, e_call, labels_dev.data_ptr() if labels_dev is not None else None,
+              x.data_ptr(), edge_pairs.data_ptr() if e_call else None, edge_attr.data_ptr() if e_call else None,
               edge_labels.data_ptr() if edge_labels is not None else None)
     edge_pos = None
-    if k is None:
+    if not thinned:
         _call.run(dev, lib.mtmc_build_graph, *shared, ws.data_ptr(), ws.numel(), _call.stream(dev))
     else:
         edge_pos = torch.empty((cap,), dtype=torch.int64, device=dev)
         n_kept = torch.zeros((1,), dtype=torch.int64, device=dev)
-        _call.run(dev, lib.mtmc_build_graph_knn, *shared, min(k, n), cap, edge_pos.data_ptr() if e else None,
-                  n_kept.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
+        tail = (cap, edge_pos.data_ptr() if e_call else None, n_kept.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
+        if starts is None:
+            _call.run(dev, lib.mtmc_build_graph_knn, *shared, min(k, n), *tail)
+        else:
+            t_start = up(starts)
+            _call.run(dev, lib.mtmc_build_graph_gated, *shared, t_start.data_ptr(), max_gap, min(k, n) if k is not None else 0,
+                      *tail)
+    if k is not None:
         e_k = int(n_kept.item())                              # the one host synchronisation of the k path
         if e_k > cap:
             raise RuntimeError(f"mtmc_mpn.build_graph: {e_k} edges kept, capacity {cap}")
@@ -88,17 +152,17 @@ class _BuildGraph(torch.autograd.Function):
     """`build_graph` with its HIP backward to the node features (`mtmc_build_graph_backward`): the reference's fine-tuning
     chain (train.py:304-342) without its two [E, F] gathers -- one [N, N] x [N, F] product on the matrix cores.
 
-    With `k` the gradient flows through the kept edges only (the selection has none).  A dropped edge adds exactly zero to
-    every term of the backward (a_e = b_e = 0), so the kept edges' attributes and gradients are scattered through
-    `edge_pos` into dense-layout buffers and the same backward runs: 16 bytes x E_dense of extra memory, sized for the
-    few-hundred-node graphs that are fine-tuned."""
+    With `k` or a temporal gate the gradient flows through the kept edges only (neither selection has one).  A dropped
+    edge adds exactly zero to every term of the backward (a_e = b_e = 0), so the kept edges' attributes and gradients are
+    scattered through `edge_pos` into dense-layout buffers and the same backward runs: 16 bytes x E_dense of extra memory,
+    sized for the few-hundred-node graphs that are fine-tuned."""
 
     @staticmethod
-    def forward(ctx, node_feats, cam_ids, node_labels, l2norm, k):
+    def forward(ctx, node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap):
         (x, edge_pairs, edge_attr, edge_labels, labels_dev, edge_pos), (feats, tables, n_cams, e) = \
-            _build(node_feats.detach(), cam_ids, node_labels, l2norm, k)
+            _build(node_feats.detach(), cam_ids, node_labels, l2norm, k, starts, max_gap)
         edge_index = edge_pairs.t()
-        ctx.save_for_backward(feats, x, edge_attr, *tables, *([edge_pos] if k is not None else []))
+        ctx.save_for_backward(feats, x, edge_attr, *tables, *([edge_pos] if edge_pos is not None else []))
         ctx.meta = (bool(l2norm), n_cams, e)
         ctx.mark_non_differentiable(*[t for t in (edge_index, edge_labels, labels_dev, edge_pos) if t is not None])
         return x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos
@@ -110,10 +174,10 @@ class _BuildGraph(torch.autograd.Function):
         l2norm, n_cams, e = ctx.meta
         n, f = x.shape
         dev = x.device
-        if e == 0:
-            g_attr = None
+        if edge_attr.shape[0] == 0:                               # no edges, or none kept: the gradient of x alone
+            e, g_attr = 0, None
         if g_x is None and g_attr is None:
-            return torch.zeros((n, f), dtype=torch.float32, device=dev), None, None, None, None
+            return torch.zeros((n, f), dtype=torch.float32, device=dev), None, None, None, None, None, None
         g_x = g_x.contiguous().float() if g_x is not None else None
         g_attr = g_attr.contiguous().float() if g_attr is not None else None
         if pos and g_attr is not None:
@@ -134,10 +198,11 @@ class _BuildGraph(torch.autograd.Function):
                   n_cams, e, x.data_ptr(), edge_attr.data_ptr() if e else None,
                   g_x.data_ptr() if g_x is not None else None, g_attr.data_ptr() if g_attr is not None else None,
                   d_feats.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
-        return d_feats, None, None, None, None
+        return d_feats, None, None, None, None, None, None
 
 
-def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: bool = True, k=None):
+def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: bool = True, k=None, start_frames=None,
+                max_gap=None):
     """node_feats: [N, F] float32 on a ROCm GPU (the stacked per-tracklet ReID features); cam_ids: N camera ids
     (host list / array, as the reference keeps them); node_labels: optional N identities (edge labels for training).
     With grad mode on and `node_feats.requires_grad`, `x` and `edge_attr` carry the gradient back to `node_feats`.
@@ -149,7 +214,20 @@ def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: boo
     subsequence of the dense list, with the dense call's `edge_attr` / `edge_labels` bits, E_k <= min(E_dense, 2 k N), and
     the extra field `edge_pos` (int64 [E_k]) holds each one's index in the dense list.  Costs one host read-back of E_k;
     the backward costs 16 bytes x E_dense (see `_BuildGraph`).  The encoders normalise over the edges of a call, so train
-    a model on the kind of list it is run on: nothing is claimed about the accuracy of a dense-trained model on a k list."""
+    a model on the kind of list it is run on: nothing is claimed about the accuracy of a dense-trained model on a k list.
+
+    start_frames = N integers on the host (list, integer array or integer CPU tensor: each tracklet's first frame, within
+    +-2^62) with max_gap = int >= 1: the temporal gate the reference leaves commented out (inference.py:420-441), through
+    `mtmc_build_graph_gated`.  (i, j) is a candidate iff the cameras differ and |start_i - start_j| < max_gap -- strict:
+    equal starts pass, a difference of max_gap does not.  Without `k` the kept edges are exactly the candidates, again a
+    subsequence of the dense list with its bits and with `edge_pos`; the host counts them beforehand (`gated_edge_count`),
+    so the outputs are allocated at exactly that length and nothing is read back.  With `k` every row ranks its candidates
+    only, top_i is the first min(k, candidates of i) of them, and the union rule above applies: "gate, then k", which is
+    not the k list filtered afterwards; outputs are allocated at min(E_gated, 2 k N) and E is read back once.  A node
+    without candidates is isolated, and no candidates at all gives E = 0, as one camera does.  Both arguments or neither.
+    The backward is the k path's: it scatters through `edge_pos` into dense-layout buffers, 16 bytes x E_dense.  And the
+    same warning holds: the encoders normalise over the edges of a call, so train a model on the kind of list -- gated,
+    k-nearest, both or neither -- it is run on."""
     _call.require_gpu("build_graph", node_feats)
     if node_feats.dim() != 2 or node_feats.dtype != torch.float32 or node_feats.shape[1] % 32:
         raise RuntimeError("mtmc_mpn.build_graph: node_feats must be float32 [N, F] with F a multiple of 32")
@@ -162,13 +240,19 @@ def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: boo
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
             raise RuntimeError("mtmc_mpn.build_graph: k must be None or an integer >= 1")
         k = int(k)
+    starts = None
+    if start_frames is not None or max_gap is not None:
+        if start_frames is None or max_gap is None:
+            raise RuntimeError("mtmc_mpn.build_graph: start_frames and max_gap go together")
+        starts, max_gap = _start_frames(start_frames, n), _max_gap(max_gap)
     if torch.is_grad_enabled() and node_feats.requires_grad:
         x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos = \
-            _BuildGraph.apply(node_feats, cam_ids, node_labels, l2norm, k)
+            _BuildGraph.apply(node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap)
     else:
-        (x, edge_pairs, edge_attr, edge_labels, labels_dev, edge_pos), _ = _build(node_feats, cam_ids, node_labels, l2norm, k)
+        (x, edge_pairs, edge_attr, edge_labels, labels_dev, edge_pos), _ = \
+            _build(node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap)
         edge_index = edge_pairs.t()
     out = types.SimpleNamespace(x=x, edge_index=edge_index, edge_attr=edge_attr, edge_labels=edge_labels, y=labels_dev)
-    if k is not None:
+    if edge_pos is not None:
         out.edge_pos = edge_pos
     return out

@@ -372,6 +372,25 @@ int32_t mtmc_build_graph_knn(const float* feats, int64_t feat_row_stride, int64_
                              int32_t k, int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* The other thinning of that commented-out block, a temporal gate (inference.py:420-441), alone or before the k-nearest
+ * rule: with start_frames [n_nodes] int64 in device memory (each tracklet's first frame; any int64, the difference does not overflow) and
+ * max_gap >= 1, (i, j) is a candidate iff the two nodes are in different cameras and |start_i - start_j| < max_gap --
+ * strict, the reference's comparison: equal starts pass, a difference of max_gap does not.  k == 0: the kept edges are
+ * exactly the candidates.  k >= 1: row i ranks its CANDIDATES by (key, j) ascending, top_i = the first
+ * min(k, candidates of i) of them, and (i, j) is kept iff j is in top_i or i is in top_j -- "gate, then k", which is not
+ * the k list filtered afterwards.  A row without candidates has no edges; no candidates at all gives n_kept_out[0] = 0.
+ * Order, bits, edge_pos_out, edge_capacity and the n_kept_out status as mtmc_build_graph_knn, whose body this shares
+ * (the exact length of the gated list always suffices as capacity; with k, the smaller of it and 2 k n_nodes).  The
+ * workspace is that of mtmc_graph_knn_workspace_bytes; its bit matrix goes unused when k == 0.  MTMC_E_ARG also for a
+ * NULL start_frames, max_gap < 1 or k < 0. */
+int32_t mtmc_build_graph_gated(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
+                               const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
+                               const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
+                               float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                               const int64_t* start_frames, int64_t max_gap, int32_t k,
+                               int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the construction to the node features (the reference's CNN_MODEL.finetune chain, train.py:304-342:
  * autograd through F.normalize(dim=0), F.pairwise_distance and 1 - F.cosine_similarity along the edge list).
  * feats, l2norm and the five camera tables as in the forward call (in_list per camera and out_list per camera
