@@ -6,7 +6,7 @@
 //     top_i      = the first min(k, n_cand(i)) candidates j of row i in the order (key, j) ascending
 //     keep (i,j) iff j in top_i or i in top_j            -- a union: symmetric whether or not G[i][j] == G[j][i] bitwise
 //     k == 0     : keep (i, j) iff cand(i, j); no selection and no bit matrix
-// Kept edges appear in the dense list's order with the dense list's bits (gb_edge_attr, graph_build.h) and carry their dense
+// Kept edges appear in the dense list's order with the dense list's bits (gb_write_edge, graph_build.h) and carry their dense
 // position in edge_pos.  Only G and an N x N BIT matrix are N^2-sized; the dense edge arrays are never formed.
 //     gk_select_kernel   one workgroup per row: radix select of the k-th (key, j), then bit (i, j) and bit (j, i) per pick
 //     gk_count_kernel    one workgroup per row: kept columns of its out_list
@@ -27,19 +27,6 @@ struct KnnParams {
   int64_t* edge_pos;          // [capacity]: dense position of every kept edge
 };
 
-struct KnnRow { int i; const int* ol; int n_out; int64_t e0; };   // node, its camera's out_list, its first dense edge
-
-// row of in_list position q; false where in_list names no node (such a row has no edges in any of the kernels)
-__device__ __forceinline__ bool knn_row(const EdgeBuildParams& p, int64_t q, KnnRow* r) {
-  const int c = gb_segment_of(p.in_off, p.n_cams, q);
-  const int64_t n_out = p.out_off[c + 1] - p.out_off[c];
-  r->i = p.in_list[q];
-  r->ol = p.out_list + p.out_off[c];
-  r->n_out = (int)n_out;
-  r->e0 = p.block_off[c] + (q - p.in_off[c]) * n_out;
-  return r->i >= 0 && r->i < p.n_nodes;
-}
-
 // the temporal gate of the node pair (i, j); symmetric in i and j
 __device__ __forceinline__ bool knn_gate(const KnnParams& p, int i, int j) {
   if (!p.start) return true;
@@ -49,10 +36,8 @@ __device__ __forceinline__ bool knn_gate(const KnnParams& p, int i, int j) {
 
 // order-preserving uint32 image of key(i, j); false where j is no candidate: no node, or outside the gate
 __device__ __forceinline__ bool knn_key(const KnnParams& kp, int i, int j, uint32_t* u) {
-  if (j < 0 || j >= kp.e.n_nodes || !knn_gate(kp, i, j)) return false;
-  const EdgeBuildParams& p = kp.e;
-  const float key = gb_edge_attr(p.G[(int64_t)i * p.n_nodes + j], p.row_sq[i], p.row_sq[j], p.row_sum[i], p.row_sum[j], p.f).y;
-  const uint32_t b = __float_as_uint(key);
+  if (j < 0 || j >= kp.e.t.n_nodes || !knn_gate(kp, i, j)) return false;
+  const uint32_t b = __float_as_uint(gb_edge_attr_of(kp.e, i, j).y);
   *u = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
   return true;
 }
@@ -68,8 +53,8 @@ __device__ __forceinline__ bool knn_get(const unsigned* bits, int64_t n, int i, 
 // edge (i, j) is in the result: its bit where rows selected (the gate is symmetric, so only candidates have bits), the
 // candidate test itself where the gate stands alone.  p.k is uniform over the grid.
 __device__ __forceinline__ bool knn_kept(const KnnParams& p, int i, int j) {
-  if (j < 0 || j >= p.e.n_nodes) return false;
-  return p.k ? knn_get(p.bits, p.e.n_nodes, i, j) : knn_gate(p, i, j);
+  if (j < 0 || j >= p.e.t.n_nodes) return false;
+  return p.k ? knn_get(p.bits, p.e.t.n_nodes, i, j) : knn_gate(p, i, j);
 }
 
 // exclusive prefix of v over the 256 threads of the workgroup in thread order, *total = the sum; smem: 4 ints.
@@ -98,8 +83,8 @@ __global__ __launch_bounds__(256) void gk_select_kernel(KnnParams p) {
   __shared__ int hist[256];
   __shared__ int scan_s[4];
   __shared__ int pick[2];
-  KnnRow r;
-  if (!knn_row(p.e, blockIdx.x, &r)) return;
+  GbRow r;
+  if (!gb_row_of(p.e.t, blockIdx.x, &r)) return;
   uint32_t prefix = 0, mask = 0;
   int want = p.k;
   for (int pass = 0; pass < 4; ++pass) {
@@ -136,8 +121,8 @@ __global__ __launch_bounds__(256) void gk_select_kernel(KnnParams p) {
     int total;
     const int rank = block_excl_scan(eq ? 1 : 0, scan_s, &total);
     if (ok && (u < prefix || (eq && seen + rank < want))) {
-      knn_set(p.bits, p.e.n_nodes, r.i, j);
-      knn_set(p.bits, p.e.n_nodes, j, r.i);
+      knn_set(p.bits, p.e.t.n_nodes, r.i, j);
+      knn_set(p.bits, p.e.t.n_nodes, j, r.i);
     }
     seen += total;
   }
@@ -145,9 +130,9 @@ __global__ __launch_bounds__(256) void gk_select_kernel(KnnParams p) {
 
 __global__ __launch_bounds__(256) void gk_count_kernel(KnnParams p) {
   __shared__ int scan_s[4];
-  KnnRow r;
+  GbRow r;
   int c = 0;
-  if (knn_row(p.e, blockIdx.x, &r))
+  if (gb_row_of(p.e.t, blockIdx.x, &r))
     for (int t = threadIdx.x; t < r.n_out; t += 256)
       if (knn_kept(p, r.i, r.ol[t])) ++c;
   int total;
@@ -174,8 +159,8 @@ __global__ __launch_bounds__(256) void gk_scan_kernel(int64_t* row_off, int64_t 
 // the first `capacity` edges.
 __global__ __launch_bounds__(256) void gk_fill_kernel(KnnParams p) {
   __shared__ int scan_s[4];
-  KnnRow r;
-  if (!knn_row(p.e, blockIdx.x, &r)) return;
+  GbRow r;
+  if (!gb_row_of(p.e.t, blockIdx.x, &r)) return;
   int64_t at = p.row_off[blockIdx.x];
   for (int t0 = 0; t0 < r.n_out; t0 += 256) {
     const int t = t0 + threadIdx.x;
@@ -185,10 +170,7 @@ __global__ __launch_bounds__(256) void gk_fill_kernel(KnnParams p) {
     int total;
     const int64_t pos = at + block_excl_scan(kept ? 1 : 0, scan_s, &total);
     if (kept && pos < p.capacity) {
-      reinterpret_cast<longlong2*>(p.e.edge_index)[pos] = make_longlong2(r.i, j);
-      reinterpret_cast<float2*>(p.e.edge_attr)[pos] =
-          gb_edge_attr(p.e.G[(int64_t)r.i * p.e.n_nodes + j], p.e.row_sq[r.i], p.e.row_sq[j], p.e.row_sum[r.i], p.e.row_sum[j], p.e.f);
-      if (p.e.edge_labels) p.e.edge_labels[pos] = p.e.node_labels[r.i] == p.e.node_labels[j] ? 1.f : 0.f;
+      gb_write_edge(p.e, pos, r.i, j);
       p.edge_pos[pos] = r.e0 + t;
     }
     at += total;
@@ -198,66 +180,50 @@ __global__ __launch_bounds__(256) void gk_fill_kernel(KnnParams p) {
 }  // namespace mtmc
 
 namespace {
+using mtmc::GraphCall, mtmc::KnnParams;
+
 struct KnnLayout { mtmc::GraphLayout g; size_t bits, bits_bytes, row_off, total; };
 KnnLayout knn_layout(int64_t n, int f) {
   KnnLayout l;
   l.g = mtmc::graph_layout(n, f);
-  auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
-  l.bits = l.g.total;
+  mtmc::Carver ws{l.g.total};
   l.bits_bytes = ((size_t)n * n + 31) / 32 * sizeof(unsigned);      // N^2 / 8 bytes, rounded up to a word
-  l.row_off = up256(l.bits + l.bits_bytes);
-  l.total = up256(l.row_off + (size_t)n * sizeof(int64_t));
+  l.bits = ws.take(l.bits_bytes);
+  l.row_off = ws.take((size_t)n * sizeof(int64_t));
+  l.total = ws.off;
   return l;
 }
-// The one body of mtmc_build_graph_knn (start == null, k >= 1) and mtmc_build_graph_gated (start given, k >= 0); each entry
-// has checked its own k / gate arguments.  `entry` heads the messages.
-int knn_build(const char* entry, const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
-              const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
-              const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels, float* x_out,
-              int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out, const int64_t* start, int64_t max_gap,
-              int32_t k, int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out, void* workspace,
-              size_t workspace_bytes, void* stream) {
+
+// The one body of mtmc_build_graph_knn (start == null, k >= 1) and mtmc_build_graph_gated (start given, k >= 0).  Each entry
+// has checked its own k / gate arguments and put them, the capacity and edge_pos_out into `p`; the rest of `p` is filled
+// here.  `entry` heads the messages.
+int knn_build(const char* entry, const GraphCall& c, KnnParams p, int64_t* n_kept_out) {
   using mtmc_api::fail;
-  using mtmc_api::launched;
-  int rc = mtmc::graph_check_args(entry, feats, feat_row_stride, n_nodes, feat_dim, in_list, in_off, out_list, out_off,
-                                  block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out,
-                                  edge_labels_out, workspace);
-  if (rc != MTMC_OK) return rc;
-  if (edge_capacity < 0) return fail(MTMC_E_ARG, "%s: edge_capacity must be >= 0", entry);
-  if (!n_kept_out || (n_edges > 0 && !edge_pos_out))
+  if (int rc = mtmc::graph_check_args(entry, c)) return rc;
+  if (p.capacity < 0) return fail(MTMC_E_ARG, "%s: edge_capacity must be >= 0", entry);
+  if (!n_kept_out || (c.t.n_edges > 0 && !p.edge_pos))
     return fail(MTMC_E_ARG, "%s: NULL n_kept_out, or NULL edge_pos_out with n_edges > 0", entry);
-  if (((uintptr_t)edge_index_out & 15) || ((uintptr_t)edge_attr_out & 7))
+  if (((uintptr_t)c.edge_index_out & 15) || ((uintptr_t)c.edge_attr_out & 7))
     return fail(MTMC_E_ARG, "%s: edge_index_out must be 16-byte and edge_attr_out 8-byte aligned", entry);
-  const KnnLayout l = knn_layout(n_nodes, feat_dim);
-  if (!workspace || workspace_bytes < l.total)
-    return fail(MTMC_E_WORKSPACE, "%s: workspace has %zu bytes, %zu needed (mtmc_graph_knn_workspace_bytes)", entry,
-                workspace ? workspace_bytes : (size_t)0, l.total);
-  char* ws = static_cast<char*>(workspace);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  rc = mtmc::graph_normalize_gram(entry, feats, feat_row_stride, n_nodes, feat_dim, l2norm, x_out, ws, l.g, n_edges > 0, s);
-  if (rc != MTMC_OK) return rc;
-  if (n_edges <= 0) {
+  const KnnLayout l = knn_layout(c.t.n_nodes, c.feat_dim);
+  if (int rc = mtmc::graph_check_workspace(entry, c.workspace, c.workspace_bytes, l.total, "mtmc_graph_knn_workspace_bytes")) return rc;
+  hipStream_t s = c.stream;
+  if (int rc = mtmc::graph_normalize_gram(entry, c, l.g)) return rc;
+  if (c.t.n_edges <= 0) {
     if (hipMemsetAsync(n_kept_out, 0, sizeof(int64_t), s) != hipSuccess) return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
-    return launched(entry);
+    return mtmc_api::launched(entry);
   }
-  mtmc::KnnParams p;
-  p.e.in_list = in_list; p.e.in_off = in_off; p.e.out_list = out_list; p.e.out_off = out_off; p.e.block_off = block_off;
-  p.e.n_cams = n_cams; p.e.n_nodes = n_nodes; p.e.n_edges = n_edges; p.e.f = feat_dim;
-  p.e.G = reinterpret_cast<float*>(ws + l.g.G); p.e.row_sq = reinterpret_cast<float*>(ws + l.g.row_sq);
-  p.e.row_sum = reinterpret_cast<float*>(ws + l.g.row_sum); p.e.node_labels = node_labels;
-  p.e.edge_index = edge_index_out; p.e.edge_attr = edge_attr_out; p.e.edge_labels = edge_labels_out;
-  p.k = k; p.capacity = edge_capacity; p.start = start; p.max_gap = max_gap;
-  p.bits = reinterpret_cast<unsigned*>(ws + l.bits); p.row_off = reinterpret_cast<int64_t*>(ws + l.row_off);
-  p.edge_pos = edge_pos_out;
-  const dim3 rows((unsigned)n_nodes), wg(256);
-  if (k > 0) {                                    // k == 0: the gate alone, decided per column in count and fill
+  p.e = mtmc::edge_build_params(c, l.g);
+  p.bits = c.at<unsigned>(l.bits); p.row_off = c.at<int64_t>(l.row_off);
+  const dim3 rows((unsigned)c.t.n_nodes), wg(256);
+  if (p.k > 0) {                                  // k == 0: the gate alone, decided per column in count and fill
     if (hipMemsetAsync(p.bits, 0, l.bits_bytes, s) != hipSuccess) return fail(MTMC_E_HIP, "%s: hipMemsetAsync failed", entry);
     hipLaunchKernelGGL(mtmc::gk_select_kernel, rows, wg, 0, s, p);
   }
   hipLaunchKernelGGL(mtmc::gk_count_kernel, rows, wg, 0, s, p);
-  hipLaunchKernelGGL(mtmc::gk_scan_kernel, dim3(1), wg, 0, s, p.row_off, n_nodes, n_kept_out);
+  hipLaunchKernelGGL(mtmc::gk_scan_kernel, dim3(1), wg, 0, s, p.row_off, c.t.n_nodes, n_kept_out);
   hipLaunchKernelGGL(mtmc::gk_fill_kernel, rows, wg, 0, s, p);
-  return launched(entry);
+  return mtmc_api::launched(entry);
 }
 }  // namespace
 
@@ -266,8 +232,7 @@ extern "C" {
 using mtmc_api::fail;
 
 size_t mtmc_graph_knn_workspace_bytes(int64_t n_nodes, int32_t feat_dim) {
-  if (n_nodes < 1 || n_nodes > 46000 || feat_dim < 32) return 0;
-  return knn_layout(n_nodes, feat_dim).total;
+  return mtmc::graph_size_ok(n_nodes, feat_dim) ? knn_layout(n_nodes, feat_dim).total : 0;
 }
 
 int32_t mtmc_build_graph_knn(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
@@ -277,9 +242,12 @@ int32_t mtmc_build_graph_knn(const float* feats, int64_t feat_row_stride, int64_
                              int32_t k, int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
                              void* workspace, size_t workspace_bytes, void* stream) {
   if (k < 1) return fail(MTMC_E_ARG, "build_graph_knn: k must be >= 1");
-  return knn_build("build_graph_knn", feats, feat_row_stride, n_nodes, feat_dim, l2norm, in_list, in_off, out_list, out_off,
-                   block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out, edge_labels_out, nullptr, 0,
-                   k, edge_capacity, edge_pos_out, n_kept_out, workspace, workspace_bytes, stream);
+  const GraphCall c = {{in_list, in_off, out_list, out_off, block_off, n_cams, n_nodes, n_edges},
+                       feats, feat_row_stride, feat_dim, l2norm, node_labels, x_out, edge_index_out, edge_attr_out,
+                       edge_labels_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+  KnnParams p = {};
+  p.k = k; p.capacity = edge_capacity; p.edge_pos = edge_pos_out;
+  return knn_build("build_graph_knn", c, p, n_kept_out);
 }
 
 int32_t mtmc_build_graph_gated(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
@@ -291,9 +259,12 @@ int32_t mtmc_build_graph_gated(const float* feats, int64_t feat_row_stride, int6
                                void* workspace, size_t workspace_bytes, void* stream) {
   if (!start_frames || max_gap < 1 || k < 0)
     return fail(MTMC_E_ARG, "build_graph_gated: NULL start_frames, max_gap < 1 or k < 0");
-  return knn_build("build_graph_gated", feats, feat_row_stride, n_nodes, feat_dim, l2norm, in_list, in_off, out_list, out_off,
-                   block_off, n_cams, n_edges, node_labels, x_out, edge_index_out, edge_attr_out, edge_labels_out, start_frames,
-                   max_gap, k, edge_capacity, edge_pos_out, n_kept_out, workspace, workspace_bytes, stream);
+  const GraphCall c = {{in_list, in_off, out_list, out_off, block_off, n_cams, n_nodes, n_edges},
+                       feats, feat_row_stride, feat_dim, l2norm, node_labels, x_out, edge_index_out, edge_attr_out,
+                       edge_labels_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+  KnnParams p = {};
+  p.k = k; p.capacity = edge_capacity; p.edge_pos = edge_pos_out; p.start = start_frames; p.max_gap = max_gap;
+  return knn_build("build_graph_gated", c, p, n_kept_out);
 }
 
 }  // extern "C"

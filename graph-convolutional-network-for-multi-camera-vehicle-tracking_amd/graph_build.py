@@ -88,14 +88,23 @@ def gated_edge_count(cam_ids, start_frames, max_gap) -> int:
     return _gated_count(cams, _start_frames(start_frames, cams.shape[0]), _max_gap(max_gap))
 
 
+def _head(feats, l2norm, tables, n_cams, e):
+    """The 12 arguments every entry of the family starts with (feats ... n_edges).  A call without edges (e == 0) passes
+    no out_list: one camera has none, and the library asks for the tables only where n_edges > 0."""
+    t_in, t_inoff, t_out, t_outoff, t_blk = tables
+    return (feats.data_ptr(), feats.stride(0), feats.shape[0], feats.shape[1], 1 if l2norm else 0,
+            t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
+            n_cams, e)
+
+
 def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None, starts=None, max_gap=None):
-    """The raw library call: (x, edge_pairs [E,2], edge_attr, edge_labels, labels_dev, edge_pos) and what a backward needs
-    again.  k=None: `mtmc_build_graph`, the reference's list (edge_pos None).  k given: `mtmc_build_graph_knn`; the edge
-    outputs are allocated at min(E_dense, 2 k N) and narrowed to the E_k the device reports -- one host read-back (the host
-    builds the camera tables anyway).  starts (int64 array) / max_gap given: `mtmc_build_graph_gated`; the host counts the
-    gated list (`_gated_count`), so without k the outputs are allocated at exactly E_g and nothing is read back, and with
-    k at min(E_g, 2 k N) before the same read-back.  `e` in the second tuple is the DENSE list's length in every form:
-    the backward's."""
+    """The raw library call; returns a namespace of `outputs` (x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos)
+    and what a backward needs again: `feats` as the library read them, the five camera `tables` on the device, `n_cams` and
+    `e_dense`, the DENSE list's length in every form.  k=None: `mtmc_build_graph`, the reference's list (edge_pos None).
+    k given: `mtmc_build_graph_knn`; the edge outputs are allocated at min(E_dense, 2 k N) and narrowed to the E_k the device
+    reports -- one host read-back (the host builds the camera tables anyway).  starts (int64 array) / max_gap given:
+    `mtmc_build_graph_gated`; the host counts the gated list (`_gated_count`), so without k the outputs are allocated at
+    exactly E_g and nothing is read back, and with k at min(E_g, 2 k N) before the same read-back."""
     n, f = node_feats.shape
     dev = node_feats.device
     feats = node_feats if (node_feats.stride(1) == 1 and node_feats.stride(0) % 4 == 0) else node_feats.contiguous()
@@ -108,7 +117,7 @@ def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None,
     e_call = e if cap else 0                                  # an empty gate: x alone, as with one camera
     lib = _lib.load()
     up = lambda a: torch.from_numpy(a).to(dev)
-    t_in, t_inoff, t_out, t_outoff, t_blk = up(in_list), up(in_off), up(out_list), up(out_off), up(block_off)
+    tables = (up(in_list), up(in_off), up(out_list), up(out_off), up(block_off))
     labels_dev = None
     if node_labels is not None:
         labels_dev = torch.as_tensor(np.asarray(node_labels), dtype=torch.int64).to(dev)
@@ -120,9 +129,7 @@ def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None,
     if need == 0:
         raise RuntimeError("mtmc_mpn.build_graph: unsupported size")
     ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-    shared = (feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
-              t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e_call else None, t_outoff.data_ptr(), t_blk.data_ptr(),
-              n_cams, e_call, labels_dev.data_ptr() if labels_dev is not None else None,
+    shared = (*_head(feats, l2norm, tables, n_cams, e_call), labels_dev.data_ptr() if labels_dev is not None else None,
               x.data_ptr(), edge_pairs.data_ptr() if e_call else None, edge_attr.data_ptr() if e_call else None,
               edge_labels.data_ptr() if edge_labels is not None else None)
     edge_pos = None
@@ -144,8 +151,20 @@ def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None,
             raise RuntimeError(f"mtmc_mpn.build_graph: {e_k} edges kept, capacity {cap}")
         edge_pairs, edge_attr, edge_pos = edge_pairs[:e_k], edge_attr[:e_k], edge_pos[:e_k]
         edge_labels = edge_labels[:e_k] if edge_labels is not None else None
-    return ((x, edge_pairs, edge_attr, edge_labels, labels_dev, edge_pos),
-            (feats, (t_in, t_inoff, t_out, t_outoff, t_blk), n_cams, e))
+    return types.SimpleNamespace(outputs=(x, edge_pairs.t(), edge_attr, edge_labels, labels_dev, edge_pos), feats=feats,
+                                 tables=tables, n_cams=n_cams, e_dense=e)
+
+
+def _dense_scatter(edge_attr, g_attr, edge_pos, e):
+    """The kept edges' attributes and gradients at their positions in dense-layout [e, 2] buffers.  Dropped edges: zero
+    gradient, and an infinite distance so that the backward's near-duplicate pass (d^2 below 1e-3 (rho_r^2 + rho_c^2),
+    which d = 0 would meet) does not visit them: a_e = 0 / inf = 0 all the same."""
+    dense_attr = torch.zeros((e, 2), dtype=torch.float32, device=edge_attr.device)
+    dense_attr[:, 0] = float("inf")
+    dense_attr[edge_pos] = edge_attr
+    dense_g = torch.zeros((e, 2), dtype=torch.float32, device=edge_attr.device)
+    dense_g[edge_pos] = g_attr
+    return dense_attr, dense_g
 
 
 class _BuildGraph(torch.autograd.Function):
@@ -159,18 +178,18 @@ class _BuildGraph(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap):
-        (x, edge_pairs, edge_attr, edge_labels, labels_dev, edge_pos), (feats, tables, n_cams, e) = \
-            _build(node_feats.detach(), cam_ids, node_labels, l2norm, k, starts, max_gap)
-        edge_index = edge_pairs.t()
-        ctx.save_for_backward(feats, x, edge_attr, *tables, *([edge_pos] if edge_pos is not None else []))
-        ctx.meta = (bool(l2norm), n_cams, e)
+        b = _build(node_feats.detach(), cam_ids, node_labels, l2norm, k, starts, max_gap)
+        x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos = b.outputs
+        ctx.save_for_backward(b.feats, x, edge_attr, *b.tables, *([edge_pos] if edge_pos is not None else []))
+        ctx.meta = (bool(l2norm), b.n_cams, b.e_dense)
         ctx.mark_non_differentiable(*[t for t in (edge_index, edge_labels, labels_dev, edge_pos) if t is not None])
-        return x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos
+        return b.outputs
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_x, _g_index, g_attr, _g_labels, _g_y, _g_pos):
-        feats, x, edge_attr, t_in, t_inoff, t_out, t_outoff, t_blk, *pos = ctx.saved_tensors
+        feats, x, edge_attr, *tables = ctx.saved_tensors
+        pos = tables.pop() if len(tables) > 5 else None
         l2norm, n_cams, e = ctx.meta
         n, f = x.shape
         dev = x.device
@@ -180,22 +199,13 @@ class _BuildGraph(torch.autograd.Function):
             return torch.zeros((n, f), dtype=torch.float32, device=dev), None, None, None, None, None, None
         g_x = g_x.contiguous().float() if g_x is not None else None
         g_attr = g_attr.contiguous().float() if g_attr is not None else None
-        if pos and g_attr is not None:
-            # dropped edges: zero gradient, and an infinite distance so that the backward's near-duplicate pass (d^2 below
-            # 1e-3 (rho_r^2 + rho_c^2), which d = 0 would meet) does not visit them: a_e = 0 / inf = 0 all the same
-            dense_attr = torch.zeros((e, 2), dtype=torch.float32, device=dev)
-            dense_attr[:, 0] = float("inf")
-            dense_attr[pos[0]] = edge_attr
-            dense_g = torch.zeros((e, 2), dtype=torch.float32, device=dev)
-            dense_g[pos[0]] = g_attr
-            edge_attr, g_attr = dense_attr, dense_g
+        if pos is not None and g_attr is not None:
+            edge_attr, g_attr = _dense_scatter(edge_attr, g_attr, pos, e)
         lib = _lib.load()
         d_feats = torch.empty((n, f), dtype=torch.float32, device=dev)
         ws = torch.empty(lib.mtmc_graph_backward_workspace_bytes(n, f) + 256, dtype=torch.uint8, device=dev)
-        _call.run(dev, lib.mtmc_build_graph_backward,
-                  feats.data_ptr(), feats.stride(0), n, f, 1 if l2norm else 0,
-                  t_in.data_ptr(), t_inoff.data_ptr(), t_out.data_ptr() if e else None, t_outoff.data_ptr(), t_blk.data_ptr(),
-                  n_cams, e, x.data_ptr(), edge_attr.data_ptr() if e else None,
+        _call.run(dev, lib.mtmc_build_graph_backward, *_head(feats, l2norm, tables, n_cams, e),
+                  x.data_ptr(), edge_attr.data_ptr() if e else None,
                   g_x.data_ptr() if g_x is not None else None, g_attr.data_ptr() if g_attr is not None else None,
                   d_feats.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
         return d_feats, None, None, None, None, None, None
@@ -245,13 +255,9 @@ def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: boo
         if start_frames is None or max_gap is None:
             raise RuntimeError("mtmc_mpn.build_graph: start_frames and max_gap go together")
         starts, max_gap = _start_frames(start_frames, n), _max_gap(max_gap)
-    if torch.is_grad_enabled() and node_feats.requires_grad:
-        x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos = \
-            _BuildGraph.apply(node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap)
-    else:
-        (x, edge_pairs, edge_attr, edge_labels, labels_dev, edge_pos), _ = \
-            _build(node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap)
-        edge_index = edge_pairs.t()
+    args = (node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap)
+    grad = torch.is_grad_enabled() and node_feats.requires_grad
+    x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos = _BuildGraph.apply(*args) if grad else _build(*args).outputs
     out = types.SimpleNamespace(x=x, edge_index=edge_index, edge_attr=edge_attr, edge_labels=edge_labels, y=labels_dev)
     if edge_pos is not None:
         out.edge_pos = edge_pos

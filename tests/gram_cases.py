@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 EPS = 1e-6                                   # F.pairwise_distance's eps, added to the difference
-NEAR = 1e-3                                  # gb_near (csrc/graph_build.hip): d^2 < NEAR (rho_r^2 + rho_c^2)
+NEAR = 1e-3                                  # gb_near (csrc/graph_backward.hip): d^2 < NEAR (rho_r^2 + rho_c^2)
 FLOAT_EDGE_CAP = 200_000                     # floating outputs are compared on every edge up to here, on a sample above
 
 # (N, F, cameras, l2norm, expected split, regime / what the case is for); l2norm=False runs on feats.abs()

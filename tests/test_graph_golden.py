@@ -3,7 +3,7 @@
 
 CPU part: oracle/graph_oracle.py reproduces them (integers by hash, floats to host rounding) and
 mtmc_mpn.feature_store returns exactly the bytes the reference's reader returned.
-GPU part: `mtmc_mpn.build_graph` (csrc/graph_build.hip) against the same fixtures."""
+GPU part: `mtmc_mpn.build_graph` (csrc/graph_build.hip, graph_build.h) against the same fixtures."""
 import hashlib
 import json
 import os
