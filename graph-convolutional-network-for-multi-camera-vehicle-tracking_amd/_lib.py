@@ -126,6 +126,9 @@ SIGNATURES = {
     "mtmc_graph_knn_workspace_bytes": (_sz, [_i64, _i32]),
     "mtmc_build_graph_knn": (_i32, _graph_head + [_p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _sz, _p]),
     "mtmc_build_graph_gated": (_i32, _graph_head + [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _sz, _p]),
+    "mtmc_graph_panel_rows": (_i64, [_i64, _i32, _i64]),
+    "mtmc_graph_paneled_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "mtmc_build_graph_paneled": (_i32, _graph_head + [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _p, _p, _p, _sz, _p]),
     "mtmc_graph_backward_workspace_bytes": (_sz, [_i64, _i32]),
     "mtmc_build_graph_backward": (_i32, _graph_head + [_p, _p, _p, _p, _p, _p, _sz, _p]),
     "mtmc_cross_entropy_forward": (_i32, [_p, _p, _p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),

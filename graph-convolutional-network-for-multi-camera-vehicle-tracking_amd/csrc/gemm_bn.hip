@@ -849,7 +849,7 @@ int launch_gemm_bn(const GemmParams& p, hipStream_t s, int which) {
   }
   GemmParams q = p;
   int sk;
-  const int cfg = gemm_plan(p.M, p.K, p.Nout, &sk, long_k_ok);
+  const int cfg = gemm_plan(p.plan_rows > 0 ? p.plan_rows : p.M, p.K, p.Nout, &sk, long_k_ok);
   q.split_k = (p.slab != nullptr) ? sk : 1;
   // the passenger job (enc2) rides in the 64 x 64-tile fp16 kernel's launch; any other kernel: its own launch behind the GEMM
   const bool carries = cfg == 1 && f16_ok && q.split_k == 1;

@@ -20,6 +20,13 @@ __global__ __launch_bounds__(256) void gb_bwd_nodemap_kernel(const int* in_list,
   if (node >= 0 && node < n) { node_cam[node] = k; node_loc[node] = (int)(q - in_off[k]); }
 }
 
+int graph_node_map(const GraphTables& t, int* node_cam, int* node_loc, hipStream_t s) {
+  if (hipMemsetAsync(node_cam, 0xFF, (size_t)t.n_nodes * sizeof(int), s) != hipSuccess) return MTMC_E_HIP;
+  hipLaunchKernelGGL(gb_bwd_nodemap_kernel, dim3((unsigned)((t.n_nodes + 255) / 256)), dim3(256), 0, s, t.in_list, t.in_off,
+                     t.n_cams, t.n_nodes, node_cam, node_loc);
+  return MTMC_OK;
+}
+
 // rho_i = |x_i| exactly as the forward formed it: fp64 sum of squares -> f32 -> sqrtf
 __global__ __launch_bounds__(256) void gb_bwd_rownorm_kernel(const float* x, int f, float* rho) {
   __shared__ double red[4];
@@ -317,10 +324,8 @@ int32_t mtmc_build_graph_backward(const float* feats, int64_t feat_row_stride, i
     c.delta = reinterpret_cast<float*>(ws + l.delta); c.kappa = reinterpret_cast<float*>(ws + l.kappa);
     c.X = x; c.out = d_feats_out; c.f = feat_dim;
     if (hipMemsetAsync(c.S, 0, (size_t)n_nodes * l.npad * sizeof(float), s) != hipSuccess ||
-        hipMemsetAsync(node_cam, 0xFF, (size_t)n_nodes * sizeof(int), s) != hipSuccess)
+        mtmc::graph_node_map(t, node_cam, node_loc, s) != MTMC_OK)
       return fail(MTMC_E_HIP, "build_graph_backward: hipMemsetAsync failed");
-    hipLaunchKernelGGL(mtmc::gb_bwd_nodemap_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, in_list, in_off,
-                       n_cams, n_nodes, node_cam, node_loc);
     hipLaunchKernelGGL(mtmc::gb_bwd_rownorm_kernel, dim3((unsigned)n_nodes), dim3(256), 0, s, x, feat_dim, rho);
     hipLaunchKernelGGL(mtmc::gb_bwd_coef_kernel, dim3((unsigned)n_nodes), dim3(256), 0, s, c);
     mtmc::GraphBwdGemm g;

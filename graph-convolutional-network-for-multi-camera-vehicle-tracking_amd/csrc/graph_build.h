@@ -44,17 +44,22 @@ __device__ __forceinline__ void gb_edge_ends(const GraphTables& t, int64_t e, in
   *col = t.out_list[t.out_off[c] + local % n_out];
 }
 
+// rank of node i in the ascending list ol[0 .. n_out); -1 where it is not in it
+__device__ __forceinline__ int64_t gb_rank_in(const int* ol, int64_t n_out, int i) {
+  int64_t lo = 0, hi = n_out;
+  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (ol[mid] < i) lo = mid + 1; else hi = mid; }
+  return lo < n_out && ol[lo] == i ? lo : -1;
+}
+
 // dense position of the edge from in_list position q into node i of camera ci: block_off[k] + pos(q) * n_out(k) + rank of i
 // in camera k's ascending out_list; -1 where q is of camera ci itself or the tables hold no such edge.  *j = the node at q.
 __device__ __forceinline__ int64_t gb_edge_into(const GraphTables& t, int64_t q, int i, int ci, int* j) {
   const int k = gb_segment_of(t.in_off, t.n_cams, q);
   *j = t.in_list[q];
   if (k == ci) return -1;
-  const int* ol = t.out_list + t.out_off[k];
   const int64_t n_out = t.out_off[k + 1] - t.out_off[k];
-  int64_t lo = 0, hi = n_out;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (ol[mid] < i) lo = mid + 1; else hi = mid; }
-  if (lo >= n_out || ol[lo] != i) return -1;
+  const int64_t lo = gb_rank_in(t.out_list + t.out_off[k], n_out, i);
+  if (lo < 0) return -1;
   const int64_t e = t.block_off[k] + (q - t.in_off[k]) * n_out + lo;
   return e < t.n_edges ? e : -1;
 }
@@ -72,12 +77,13 @@ __device__ __forceinline__ float2 gb_edge_attr(float g, float nr, float nc, floa
 struct EdgeBuildParams {
   GraphTables t; int f;
   const float* G; const float* row_sq; const float* row_sum; const int64_t* node_labels;
+  int64_t g_row0 = 0;                           // G holds the Gram rows of the nodes from g_row0 on: [rows][N] (a row panel)
   int64_t* edge_index;                          // [E][2] (row, col): its .T is the [2,E] view the callers pass on
   float* edge_attr; float* edge_labels;
 };
 
 __device__ __forceinline__ float2 gb_edge_attr_of(const EdgeBuildParams& p, int i, int j) {
-  return gb_edge_attr(p.G[(int64_t)i * p.t.n_nodes + j], p.row_sq[i], p.row_sq[j], p.row_sum[i], p.row_sum[j], p.f);
+  return gb_edge_attr(p.G[(i - p.g_row0) * p.t.n_nodes + j], p.row_sq[i], p.row_sq[j], p.row_sum[i], p.row_sum[j], p.f);
 }
 
 // edge (row, col) into output slot `slot`: index pair, attributes, label.  (A thinned list's edge_pos is its caller's.)
@@ -104,6 +110,8 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* red) {
 
 // out[c] += sum over the rows of x[r][c]^2 (g == null) or of x[r][c] g[r][c] (g: [n][f]), in fp64; out is zero on entry
 void graph_column_sums(const float* x, int64_t ld, const float* g, int64_t n, int f, double* out, hipStream_t s);
+// node -> (camera block, position inside it), the inverse of in_list; a node that in_list does not name keeps node_cam < 0
+int graph_node_map(const GraphTables& t, int* node_cam, int* node_loc, hipStream_t s);
 
 struct GraphCall {                              // one call of a forward entry, as the host sees it
   GraphTables t;
@@ -116,8 +124,12 @@ struct GraphCall {                              // one call of a forward entry, 
 
 // The sizes every entry accepts.  The workspace queries of the forward entries answer for any feat_dim >= 32 (the calls
 // themselves then refuse one that is no multiple of 32: graph_dims_ok); the backward's query wants the multiple as well.
-inline bool graph_size_ok(int64_t n, int f) { return n >= 1 && n <= 46000 && f >= 32; }
-inline bool graph_dims_ok(const GraphTables& t, int f) { return graph_size_ok(t.n_nodes, f) && f % 32 == 0 && t.n_cams >= 1; }
+// max_nodes: 46000 where G is formed whole (N^2 x 4 bytes), 262144 where it is formed in row panels (graph_knn.hip).
+constexpr int64_t kGraphMaxNodes = 46000, kGraphMaxNodesPaneled = 262144;
+inline bool graph_size_ok(int64_t n, int f, int64_t max_nodes = kGraphMaxNodes) { return n >= 1 && n <= max_nodes && f >= 32; }
+inline bool graph_dims_ok(const GraphTables& t, int f, int64_t max_nodes = kGraphMaxNodes) {
+  return graph_size_ok(t.n_nodes, f, max_nodes) && f % 32 == 0 && t.n_cams >= 1;
+}
 inline bool graph_tables_given(const GraphTables& t) { return t.in_list && t.in_off && t.out_list && t.out_off && t.block_off; }
 
 // workspace carving: every region starts 256-byte aligned
@@ -126,11 +138,13 @@ struct Carver {
   size_t take(size_t bytes) { const size_t o = off; off = mtmc_api::align_up(off + bytes); return o; }
 };
 
+// G and the split-K slab hold g_rows Gram rows: all N, or a row panel
 struct GraphLayout { size_t colsq, row_sq, row_sum, G, zeros, slab, total; };
-GraphLayout graph_layout(int64_t n, int f);
+GraphLayout graph_layout(int64_t n, int f, int64_t g_rows);
+inline GraphLayout graph_layout(int64_t n, int f) { return graph_layout(n, f, n); }
 
-// what the three forward entries refuse alike; `entry` heads the message.  MTMC_OK or the failure's code.
-int graph_check_args(const char* entry, const GraphCall& c);
+// what the forward entries refuse alike; `entry` heads the message.  MTMC_OK or the failure's code.
+int graph_check_args(const char* entry, const GraphCall& c, int64_t max_nodes = kGraphMaxNodes);
 // the call's workspace holds `need` bytes, the answer of `query`
 inline int graph_check_workspace(const char* entry, const void* workspace, size_t have, size_t need, const char* query) {
   if (workspace && have >= need) return MTMC_OK;
@@ -138,9 +152,16 @@ inline int graph_check_workspace(const char* entry, const void* workspace, size_
                         need, query);
 }
 
-// x_out = the (column-normalised) features, row_sq / row_sum of its rows and, where the call has edges, G = x_out x_out^T,
-// all in the workspace laid out by `l`.  MTMC_OK or the failure's code.
-int graph_normalize_gram(const char* entry, const GraphCall& c, const GraphLayout& l);
+// x_out = the (column-normalised) features, row_sq / row_sum of its rows, in the workspace laid out by `l`
+int graph_normalize(const char* entry, const GraphCall& c, const GraphLayout& l);
+// G = x_out[row0 .. row0 + rows) x_out^T, [rows][N] at l.G.  Planned as the whole product is (GemmParams::plan_rows = N):
+// same kernel, BK and split, so an element of G has the same bits whichever panel forms it.
+int graph_gram(const char* entry, const GraphCall& c, const GraphLayout& l, int64_t row0, int64_t rows);
+// both, G whole and only where the call has edges.  MTMC_OK or the failure's code.
+inline int graph_normalize_gram(const char* entry, const GraphCall& c, const GraphLayout& l) {
+  if (int rc = graph_normalize(entry, c, l)) return rc;
+  return c.t.n_edges > 0 ? graph_gram(entry, c, l, 0, c.t.n_nodes) : MTMC_OK;
+}
 
 // the device-side view of the call's tables, Gram matrix and edge outputs
 EdgeBuildParams edge_build_params(const GraphCall& c, const GraphLayout& l);

@@ -13,6 +13,7 @@
 //     961 <= N <= 1920    the same kernel, unsplit at every F (256 tiles or more)
 //     N >= 1921           gemm_bn_bf16x6_kernel<2,2,32> (128 x 128 tiles, six bf16 products per fp32 product)
 //     F > 6144            linear_generic_kernel (one thread per element, a chain of F fmaf) up to N = 2048; refused above that
+// A row panel of G (graph_gram with fewer than N rows) is planned by N all the same, so its elements carry the same bits.
 // tests/gram_cases.py names a case for each line and tests/test_gram_cases.py pins the splits.
 // Here: the normalise -> Gram sequence, argument checks and workspace layout of every builder, and the dense builder itself.
 // graph_knn.hip thins its list, graph_backward.hip differentiates it; graph_build.h holds what the three share.
@@ -74,26 +75,26 @@ __global__ __launch_bounds__(256) void gb_edges_kernel(EdgeBuildParams p) {
   }
 }
 
-GraphLayout graph_layout(int64_t n, int f) {
+GraphLayout graph_layout(int64_t n, int f, int64_t g_rows) {
   GraphLayout l;
   Carver ws;
   l.colsq = ws.take((size_t)f * sizeof(double));
   l.row_sq = ws.take((size_t)n * sizeof(float));
   l.row_sum = ws.take((size_t)n * sizeof(float));
-  l.G = ws.take((size_t)n * n * sizeof(float));
+  l.G = ws.take((size_t)g_rows * n * sizeof(float));
   l.zeros = ws.take((size_t)n * sizeof(float));
   int sk = 1;
   gemm_plan(n, f, (int)n, &sk);
-  l.slab = ws.take(sk > 1 ? (size_t)sk * n * n * sizeof(float) : 0);
+  l.slab = ws.take(sk > 1 ? (size_t)sk * g_rows * n * sizeof(float) : 0);
   l.total = ws.off;
   return l;
 }
 
-int graph_check_args(const char* entry, const GraphCall& c) {
+int graph_check_args(const char* entry, const GraphCall& c, int64_t max_nodes) {
   using mtmc_api::fail;
   if (!c.feats || !c.x_out) return fail(MTMC_E_ARG, "%s: NULL feats or x_out", entry);
-  if (!graph_dims_ok(c.t, c.feat_dim))
-    return fail(MTMC_E_ARG, "%s: n_nodes must be in [1, 46000], feat_dim a multiple of 32 and n_cams >= 1", entry);
+  if (!graph_dims_ok(c.t, c.feat_dim, max_nodes))
+    return fail(MTMC_E_ARG, "%s: n_nodes must be in [1, %lld], feat_dim a multiple of 32 and n_cams >= 1", entry, (long long)max_nodes);
   if (c.t.n_edges > 0 && (!graph_tables_given(c.t) || !c.edge_index_out || !c.edge_attr_out))
     return fail(MTMC_E_ARG, "%s: NULL camera table or edge output with n_edges > 0", entry);
   if (c.edge_labels_out && !c.node_labels) return fail(MTMC_E_ARG, "%s: edge_labels_out needs node_labels", entry);
@@ -103,7 +104,7 @@ int graph_check_args(const char* entry, const GraphCall& c) {
   return MTMC_OK;
 }
 
-int graph_normalize_gram(const char* entry, const GraphCall& c, const GraphLayout& l) {
+int graph_normalize(const char* entry, const GraphCall& c, const GraphLayout& l) {
   using mtmc_api::fail;
   const int64_t n = c.t.n_nodes;
   double* colsq = c.at<double>(l.colsq);
@@ -115,13 +116,19 @@ int graph_normalize_gram(const char* entry, const GraphCall& c, const GraphLayou
   if (c.l2norm) graph_column_sums(c.feats, c.feat_row_stride, nullptr, n, c.feat_dim, colsq, s);
   hipLaunchKernelGGL(gb_normalize_kernel, dim3((unsigned)n), dim3(256), 0, s, c.feats, c.feat_row_stride, n, c.feat_dim, colsq,
                      c.l2norm, c.x_out, c.at<float>(l.row_sq), c.at<float>(l.row_sum));
-  if (c.t.n_edges > 0) {
-    GemmParams g = plain_gemm(c.x_out, c.feat_dim, c.x_out, zeros, c.at<float>(l.G), n, n, c.feat_dim, (int)n);
-    int sk = 1;
-    gemm_plan(n, c.feat_dim, (int)n, &sk);
-    if (sk > 1 && l.slab != l.total) g.slab = c.at<float>(l.slab);
-    if (launch_gemm_bn(g, s) != MTMC_OK) return fail(MTMC_E_ARG, "%s: the Gram-matrix GEMM refused its shape", entry);
-  }
+  return MTMC_OK;
+}
+
+int graph_gram(const char* entry, const GraphCall& c, const GraphLayout& l, int64_t row0, int64_t rows) {
+  const int64_t n = c.t.n_nodes;
+  GemmParams g = plain_gemm(c.x_out + row0 * c.feat_dim, c.feat_dim, c.x_out, c.at<float>(l.zeros), c.at<float>(l.G), n, rows,
+                            c.feat_dim, (int)n);
+  g.plan_rows = n;
+  int sk = 1;
+  gemm_plan(n, c.feat_dim, (int)n, &sk);
+  if (sk > 1) g.slab = c.at<float>(l.slab);
+  if (launch_gemm_bn(g, c.stream) != MTMC_OK)
+    return mtmc_api::fail(MTMC_E_ARG, "%s: the Gram-matrix GEMM refused its shape", entry);
   return MTMC_OK;
 }
 

@@ -182,6 +182,8 @@ struct GemmParams : ActIn, LayerOut, Enc2Ride {
   const float* W = nullptr;                    // [Nout][K]
   float* slab = nullptr;                       // [split_k][M][Nout] scratch for split-K partial tiles, or nullptr
   int split_k = 1;                             // set by launch_gemm_bn
+  int64_t plan_rows = 0;                       // launch_gemm_bn plans (kernel, tile, split) for this many rows; 0: for M.  A row
+                                               // panel of a larger product names the whole product's rows (graph_gram)
   // fp16 two-piece path (gemm_bn_f16x3_kernel): |.|max bit patterns, u32[kAmaxRep] each (take the max), device
   // memory; nullptr = not available
   const unsigned* amax_a = nullptr;            // of A's source: x itself (no stats_in) or the producing layer's raw Y

@@ -15,7 +15,9 @@ import torch
 
 from . import _call, _lib
 
-MAX_NODES = 46000
+MAX_NODES = 46000               # where the Gram matrix is formed whole: N^2 x 4 bytes
+MAX_NODES_PANELED = 262144      # where it is formed in row panels (`mtmc_build_graph_paneled`)
+MAX_K_PANELED = 4096
 
 
 def camera_tables(cam_ids):
@@ -97,14 +99,15 @@ def _head(feats, l2norm, tables, n_cams, e):
             n_cams, e)
 
 
-def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None, starts=None, max_gap=None):
+def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None, starts=None, max_gap=None, panel_rows=None):
     """The raw library call; returns a namespace of `outputs` (x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos)
     and what a backward needs again: `feats` as the library read them, the five camera `tables` on the device, `n_cams` and
     `e_dense`, the DENSE list's length in every form.  k=None: `mtmc_build_graph`, the reference's list (edge_pos None).
     k given: `mtmc_build_graph_knn`; the edge outputs are allocated at min(E_dense, 2 k N) and narrowed to the E_k the device
     reports -- one host read-back (the host builds the camera tables anyway).  starts (int64 array) / max_gap given:
     `mtmc_build_graph_gated`; the host counts the gated list (`_gated_count`), so without k the outputs are allocated at
-    exactly E_g and nothing is read back, and with k at min(E_g, 2 k N) before the same read-back."""
+    exactly E_g and nothing is read back, and with k at min(E_g, 2 k N) before the same read-back.  panel_rows given (0: the
+    library chooses): `mtmc_build_graph_paneled` in place of either thinned entry -- same outputs, same allocation."""
     n, f = node_feats.shape
     dev = node_feats.device
     feats = node_feats if (node_feats.stride(1) == 1 and node_feats.stride(0) % 4 == 0) else node_feats.contiguous()
@@ -125,7 +128,11 @@ def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None,
     edge_pairs = torch.empty((cap, 2), dtype=torch.int64, device=dev)
     edge_attr = torch.empty((cap, 2), dtype=torch.float32, device=dev)
     edge_labels = torch.empty((cap,), dtype=torch.float32, device=dev) if labels_dev is not None else None
-    need = lib.mtmc_graph_knn_workspace_bytes(n, f) if thinned else lib.mtmc_graph_workspace_bytes(n, f)
+    kk = min(k, n) if k is not None else 0
+    if panel_rows is not None:
+        need = lib.mtmc_graph_paneled_workspace_bytes(n, f, kk, panel_rows)
+    else:
+        need = lib.mtmc_graph_knn_workspace_bytes(n, f) if thinned else lib.mtmc_graph_workspace_bytes(n, f)
     if need == 0:
         raise RuntimeError("mtmc_mpn.build_graph: unsupported size")
     ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
@@ -139,12 +146,14 @@ def _build(node_feats: torch.Tensor, cam_ids, node_labels, l2norm: bool, k=None,
         edge_pos = torch.empty((cap,), dtype=torch.int64, device=dev)
         n_kept = torch.zeros((1,), dtype=torch.int64, device=dev)
         tail = (cap, edge_pos.data_ptr() if e_call else None, n_kept.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
-        if starts is None:
-            _call.run(dev, lib.mtmc_build_graph_knn, *shared, min(k, n), *tail)
+        t_start = up(starts) if starts is not None else None
+        gate = (t_start.data_ptr() if starts is not None else None, max_gap or 0, kk)
+        if panel_rows is not None:
+            _call.run(dev, lib.mtmc_build_graph_paneled, *shared, *gate, panel_rows, *tail)
+        elif starts is None:
+            _call.run(dev, lib.mtmc_build_graph_knn, *shared, kk, *tail)
         else:
-            t_start = up(starts)
-            _call.run(dev, lib.mtmc_build_graph_gated, *shared, t_start.data_ptr(), max_gap, min(k, n) if k is not None else 0,
-                      *tail)
+            _call.run(dev, lib.mtmc_build_graph_gated, *shared, *gate, *tail)
     if k is not None:
         e_k = int(n_kept.item())                              # the one host synchronisation of the k path
         if e_k > cap:
@@ -177,8 +186,8 @@ class _BuildGraph(torch.autograd.Function):
     sized for the few-hundred-node graphs that are fine-tuned."""
 
     @staticmethod
-    def forward(ctx, node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap):
-        b = _build(node_feats.detach(), cam_ids, node_labels, l2norm, k, starts, max_gap)
+    def forward(ctx, node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap, panel_rows):
+        b = _build(node_feats.detach(), cam_ids, node_labels, l2norm, k, starts, max_gap, panel_rows)
         x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos = b.outputs
         ctx.save_for_backward(b.feats, x, edge_attr, *b.tables, *([edge_pos] if edge_pos is not None else []))
         ctx.meta = (bool(l2norm), b.n_cams, b.e_dense)
@@ -196,7 +205,7 @@ class _BuildGraph(torch.autograd.Function):
         if edge_attr.shape[0] == 0:                               # no edges, or none kept: the gradient of x alone
             e, g_attr = 0, None
         if g_x is None and g_attr is None:
-            return torch.zeros((n, f), dtype=torch.float32, device=dev), None, None, None, None, None, None
+            return torch.zeros((n, f), dtype=torch.float32, device=dev), None, None, None, None, None, None, None
         g_x = g_x.contiguous().float() if g_x is not None else None
         g_attr = g_attr.contiguous().float() if g_attr is not None else None
         if pos is not None and g_attr is not None:
@@ -208,11 +217,11 @@ class _BuildGraph(torch.autograd.Function):
                   x.data_ptr(), edge_attr.data_ptr() if e else None,
                   g_x.data_ptr() if g_x is not None else None, g_attr.data_ptr() if g_attr is not None else None,
                   d_feats.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
-        return d_feats, None, None, None, None, None, None
+        return d_feats, None, None, None, None, None, None, None
 
 
 def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: bool = True, k=None, start_frames=None,
-                max_gap=None):
+                max_gap=None, panel_rows=None):
     """node_feats: [N, F] float32 on a ROCm GPU (the stacked per-tracklet ReID features); cam_ids: N camera ids
     (host list / array, as the reference keeps them); node_labels: optional N identities (edge labels for training).
     With grad mode on and `node_feats.requires_grad`, `x` and `edge_attr` carry the gradient back to `node_feats`.
@@ -237,15 +246,21 @@ def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: boo
     without candidates is isolated, and no candidates at all gives E = 0, as one camera does.  Both arguments or neither.
     The backward is the k path's: it scatters through `edge_pos` into dense-layout buffers, 16 bytes x E_dense.  And the
     same warning holds: the encoders normalise over the edges of a call, so train a model on the kind of list -- gated,
-    k-nearest, both or neither -- it is run on."""
+    k-nearest, both or neither -- it is run on.
+
+    panel_rows = int >= 1, with `k` or a gate: the same list through `mtmc_build_graph_paneled`, which forms the Gram matrix
+    in panels of that many node rows (clipped to N), twice, and keeps the picks as per-row lists: every output has the bits
+    of the call without `panel_rows`, the workspace is panel_rows x N x 4 bytes plus 8 N min(k, N) instead of N^2 x 4.125, and
+    min(k, N) <= 4096.  panel_rows=None takes that entry by itself, with a panel of its own choosing
+    (`mtmc_graph_panel_rows`), above 46 000 nodes, where no other applies, up to 262 144 nodes; the all-pairs list stays at
+    46 000.  The backward needs dense [E_dense, 2] buffers and an N x N matrix: above 46 000 nodes features that require a
+    gradient are refused."""
     _call.require_gpu("build_graph", node_feats)
     if node_feats.dim() != 2 or node_feats.dtype != torch.float32 or node_feats.shape[1] % 32:
         raise RuntimeError("mtmc_mpn.build_graph: node_feats must be float32 [N, F] with F a multiple of 32")
     n, f = node_feats.shape
     if len(cam_ids) != n:
         raise RuntimeError("mtmc_mpn.build_graph: one camera id per node expected")
-    if n > MAX_NODES:
-        raise NotImplementedError(f"mtmc_mpn.build_graph: the Gram-matrix builder handles up to {MAX_NODES} nodes")
     if k is not None:
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
             raise RuntimeError("mtmc_mpn.build_graph: k must be None or an integer >= 1")
@@ -255,8 +270,23 @@ def build_graph(node_feats: torch.Tensor, cam_ids, node_labels=None, l2norm: boo
         if start_frames is None or max_gap is None:
             raise RuntimeError("mtmc_mpn.build_graph: start_frames and max_gap go together")
         starts, max_gap = _start_frames(start_frames, n), _max_gap(max_gap)
-    args = (node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap)
+    thinned = k is not None or starts is not None
+    if panel_rows is not None:
+        if isinstance(panel_rows, bool) or not isinstance(panel_rows, (int, np.integer)) or panel_rows < 1:
+            raise RuntimeError("mtmc_mpn.build_graph: panel_rows must be None or an integer >= 1")
+        if not thinned:
+            raise RuntimeError("mtmc_mpn.build_graph: panel_rows needs k or a temporal gate (the all-pairs list is N^2-sized anyway)")
+        panel_rows = int(panel_rows)
+    elif n > MAX_NODES and thinned:
+        panel_rows = 0                                            # the library chooses
     grad = torch.is_grad_enabled() and node_feats.requires_grad
+    if n > MAX_NODES_PANELED or (n > MAX_NODES and panel_rows is None):
+        raise NotImplementedError(f"mtmc_mpn.build_graph: up to {MAX_NODES} nodes, and up to {MAX_NODES_PANELED} with k or a gate")
+    if n > MAX_NODES and grad:
+        raise NotImplementedError(f"mtmc_mpn.build_graph: the backward handles up to {MAX_NODES} nodes")
+    if panel_rows is not None and k is not None and min(k, n) > MAX_K_PANELED:
+        raise RuntimeError(f"mtmc_mpn.build_graph: min(k, N) must be <= {MAX_K_PANELED} with panel_rows or above {MAX_NODES} nodes")
+    args = (node_feats, cam_ids, node_labels, l2norm, k, starts, max_gap, panel_rows)
     x, edge_index, edge_attr, edge_labels, labels_dev, edge_pos = _BuildGraph.apply(*args) if grad else _build(*args).outputs
     out = types.SimpleNamespace(x=x, edge_index=edge_index, edge_attr=edge_attr, edge_labels=edge_labels, y=labels_dev)
     if edge_pos is not None:

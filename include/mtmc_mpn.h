@@ -391,6 +391,29 @@ int32_t mtmc_build_graph_gated(const float* feats, int64_t feat_row_stride, int6
                                int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* The two thinned lists without anything N^2-sized, for 1 <= n_nodes <= 262144: the rule, the order, the
+ * bits, edge_pos_out, edge_capacity and the n_kept_out status of mtmc_build_graph_knn / mtmc_build_graph_gated, but the Gram
+ * matrix is formed in row panels of P node rows ([P][n_nodes] fp32), twice -- once to pick every row's top, once to write
+ * the kept edges -- and the picks live in per-row lists.  With the same input the outputs are those of the unpaneled entry
+ * bit for bit at every P (a panel's product is planned as the whole product is).  start_frames may be NULL (no gate;
+ * max_gap is then ignored); k >= 1 or a gate is needed, k == 0 with a gate keeps the candidates.  k above n_nodes counts
+ * as n_nodes, and min(k, n_nodes) <= 4096.  panel_rows = P >= 1 (clipped to n_nodes), or 0: the library chooses.
+ * mtmc_graph_panel_rows returns the P a call will use: min(panel_rows, n_nodes), and for 0 the largest multiple of 128 with
+ * P * n_nodes * 4 <= 1 GiB, at least 128, clipped to n_nodes.  Workspace: P * n_nodes * 4 bytes for the panel, split times
+ * as much again where the whole product's plan cuts K, 2 * n_nodes * min(k, n_nodes) * 4 for the picks and their
+ * transpose, O(n_nodes + feat_dim) words besides.  Both queries return 0 outside 1 <= n_nodes <= 262144, for a feat_dim
+ * that is no positive multiple of 32, min(k, n_nodes) > 4096, k < 0 or panel_rows < 0, and the entry refuses the same with
+ * MTMC_E_ARG before anything is enqueued.  Nothing synchronises; the result is bitwise repeatable. */
+int64_t mtmc_graph_panel_rows(int64_t n_nodes, int32_t feat_dim, int64_t panel_rows);
+size_t mtmc_graph_paneled_workspace_bytes(int64_t n_nodes, int32_t feat_dim, int32_t k, int64_t panel_rows);
+int32_t mtmc_build_graph_paneled(const float* feats, int64_t feat_row_stride, int64_t n_nodes, int32_t feat_dim, int32_t l2norm,
+                                 const int32_t* in_list, const int32_t* in_off, const int32_t* out_list, const int64_t* out_off,
+                                 const int64_t* block_off, int32_t n_cams, int64_t n_edges, const int64_t* node_labels,
+                                 float* x_out, int64_t* edge_index_out, float* edge_attr_out, float* edge_labels_out,
+                                 const int64_t* start_frames, int64_t max_gap, int32_t k, int64_t panel_rows,
+                                 int64_t edge_capacity, int64_t* edge_pos_out, int64_t* n_kept_out,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the construction to the node features (the reference's CNN_MODEL.finetune chain, train.py:304-342:
  * autograd through F.normalize(dim=0), F.pairwise_distance and 1 - F.cosine_similarity along the edge list).
  * feats, l2norm and the five camera tables as in the forward call (in_list per camera and out_list per camera
