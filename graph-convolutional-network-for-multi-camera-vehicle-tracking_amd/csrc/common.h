@@ -241,14 +241,19 @@ __device__ __forceinline__ int confusion_slot(bool y, bool pred) { return y ? (p
 // BatchNorm (batch statistics) as y = s*z + t from fp64 (sum, sumsq) over `count` rows.
 // Latency matters (this sits in kernel prologues): no fp64 division or square root -- multiply by 1/count,
 // take v_rsq_f32 of the variance and polish it with one fp64 Newton step (error ~1e-14 relative).
-__device__ __forceinline__ void bn_affine(double sum, double sumsq, double count, float gamma, float beta,
-                                          float& s, float& t) {
+// The statistics half, shared with the backward (bwd_common.h: mean_istd): mean and r = 1/sqrt(var + eps).
+__device__ __forceinline__ void bn_mean_rstd(double sum, double sumsq, double count, double& mean, double& r) {
   const double inv = 1.0 / count;            // count is a kernel argument: uniform, hoisted by the compiler
-  const double mean = sum * inv;
+  mean = sum * inv;
   double var = fma(sumsq, inv, -mean * mean);
   var = (var < 0 ? 0 : var) + MTMC_BN_EPS;
-  double r = (double)rsqrtf((float)var);
+  r = (double)rsqrtf((float)var);
   r = r * fma(-0.5 * var, r * r, 1.5);
+}
+__device__ __forceinline__ void bn_affine(double sum, double sumsq, double count, float gamma, float beta,
+                                          float& s, float& t) {
+  double mean, r;
+  bn_mean_rstd(sum, sumsq, count, mean, r);
   const double sd = (double)gamma * r;
   s = (float)sd;
   t = (float)fma(-mean, sd, (double)beta);
@@ -361,15 +366,21 @@ __device__ __forceinline__ double quad_form(const float* w, int n, const double*
   return q;
 }
 
-__device__ __forceinline__ void moments_affine(const float* w, int in_dim, float bias, const double* m1,
-                                               const double* m2, double count, float gamma, float beta,
-                                               float& s, float& t) {
+// sum and sum of squares over `count` rows of an affine layer's pre-activation z = w.a + bias, from the packed moments of a
+__device__ __forceinline__ void moments_sum_sumsq(const float* w, int in_dim, float bias, const double* m1,
+                                                  const double* m2, double count, double& sum, double& sumsq) {
   double wm1 = 0;
   for (int i = 0; i < in_dim; ++i) wm1 += (double)w[i] * m1[i];
   const double q = quad_form(w, in_dim, m2);
   const double b = bias;
-  const double sum = wm1 + b * count;                       // sum over rows of z
-  const double sumsq = q + 2.0 * b * wm1 + b * b * count;   // sum over rows of z^2
+  sum = wm1 + b * count;
+  sumsq = q + 2.0 * b * wm1 + b * b * count;
+}
+__device__ __forceinline__ void moments_affine(const float* w, int in_dim, float bias, const double* m1,
+                                               const double* m2, double count, float gamma, float beta,
+                                               float& s, float& t) {
+  double sum, sumsq;
+  moments_sum_sumsq(w, in_dim, bias, m1, m2, count, sum, sumsq);
   bn_affine(sum, sumsq, count, gamma, beta, s, t);
 }
 

@@ -1,5 +1,5 @@
 // relu(bn(Y)) (+ Dropout) of 16 rows x 64 columns per workgroup with a TRANSPOSED copy beside it: the body of
-// bn_relu_rows_t_kernel (node_kernels.hip) and of the z = 1 workgroups of bn_bwd_kernel<1> (train_kernels.hip: the backward's
+// bn_relu_rows_t_kernel (node_kernels.hip) and of the z = 1 workgroups of bn_bwd_kernel<1> (bwd_node_enc.hip: the backward's
 // recomputation of a layer's input activation rides in the launch that applies the layer's BatchNorm backward -- the two
 // are independent).  A thread keeps ONE column: its BatchNorm affine is derived once; the transposed tile leaves through LDS
 // as one 16-byte store per thread.  bx / by / ny: the workgroup's tile and the number of row tiles.

@@ -1,20 +1,39 @@
-// Launch interface of the backward kernels (train_kernels.hip).
+// Launch interface of the backward kernels (bwd_round.hip, bwd_edge_enc.hip, bwd_node_enc.hip).
 #pragma once
 #include "kernels.h"
 #include "rows_body.h"
 
 namespace mtmc {
 
-constexpr int kGradRep = 16;   // replicas of the dP accumulator (see bwd_edge_upd_kernel)
+constexpr int kGradRep = 16;   // replicas of the dP accumulator (see bwd_edge_upd_kernel, bwd_round.hip)
 
 // Sums that EVERY workgroup of an edge kernel adds to the same few gradient words (biases, the 4-wide edge columns
 // of the update weights, the classifier, the edge encoder): same-address float atomics serialise in L2 at ~130 ns
 // each, i.e. ~90 us behind a 676-workgroup launch.  They go to one of kGradRep replica rows of a workspace scratch
 // instead (row = workgroup % kGradRep, zeroed with the rest of the backward scratch) and grad_fold_kernel adds the
 // rows into the caller's gradient tensors once, at the end of the backward.
+//
+// One row, in the order grad_fold_kernel walks it; the producer writes `first + offset`:
+//   kGaUnB   32  node update bias [k]                                  bwd_node_upd_kernel<1>
+//   kGaUnW  128  node update weight, edge columns [k][4]               bwd_node_upd_kernel<1>
+//   kGaClsW 4*C  classifier weight [c][4]   (C = MTMC_MAX_CLASSES)     bwd_edge_upd_kernel<0>
+//   kGaClsB   C  classifier bias [c]                                   bwd_edge_upd_kernel<0>
+//   kGaUeB    4  edge update bias [kk]                                 bwd_edge_upd_kernel<1>
+//   kGaUeW   32  edge update weight, edge columns [kk][8] (4 used      bwd_edge_upd_kernel<1>
+//                without reattach_edges)
+//   kGaW2    16  edge encoder layer 2 weight [k][4]                    bwd_edge_enc_kernel<1>
+//   kGaB2     4  edge encoder layer 2 bias [k]                         bwd_edge_enc_kernel<1>
+//   kGaW1     8  edge encoder layer 1 weight [k][2] (column 1 unused   bwd_edge_enc_kernel<2>
+//                with one edge attribute)
+//   kGaB1     4  edge encoder layer 1 bias [k]                         bwd_edge_enc_kernel<2>
+// (without rounds bwd_classify_e0_kernel adds the classifier's sums to the caller's tensors itself)
 constexpr int kGaUnB = 0, kGaUnW = 32, kGaClsW = 160, kGaClsB = kGaClsW + 4 * MTMC_MAX_CLASSES,
               kGaUeB = kGaClsB + MTMC_MAX_CLASSES, kGaUeW = kGaUeB + 4, kGaW2 = kGaUeW + 32, kGaB2 = kGaW2 + 16,
               kGaW1 = kGaB2 + 4, kGaB1 = kGaW1 + 8, kGaccN = 256;
+static_assert(kGaUnB == 0 && kGaUnW == kGaUnB + kH && kGaClsW == kGaUnW + kH * 4 && kGaClsB == kGaClsW + 4 * MTMC_MAX_CLASSES &&
+              kGaUeB == kGaClsB + MTMC_MAX_CLASSES && kGaUeW == kGaUeB + 4 && kGaW2 == kGaUeW + 4 * 8 && kGaB2 == kGaW2 + 4 * 4 &&
+              kGaW1 == kGaB2 + 4 && kGaB1 == kGaW1 + 4 * 2,
+              "the segments of a gradient scratch row follow each other in grad_fold_kernel's order, each as wide as its producer writes");
 static_assert(kGaB1 + 4 <= kGaccN, "gradient scratch row too short");
 
 constexpr int kBwdStride = 256;    // doubles per replica of the backward statistics scratch (api_internal.h: Layout::bst)
