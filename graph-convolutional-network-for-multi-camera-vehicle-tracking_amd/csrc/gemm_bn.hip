@@ -16,6 +16,12 @@
 // 16-byte read feeds four consecutive MFMAs (lane half h supplies k = 8*kk + 4*h + j in step j, for A and
 // W alike, so the k-permutation cancels).  Register-staged double buffering: the next k-tile's global loads
 // are in flight while the current one is multiplied.
+//
+// Layout of this file: the staging steps the three operand formats share (tile mapping, tile loads, input activation);
+// the three kernels (fp32 MFMA, bf16x6, f16x3), which differ in how a staged tile is converted into LDS and in the MFMAs
+// that read it, and for fp16 in the operand scales and what goes with them; the split-K combine and the generic kernel;
+// one launcher and the kernel choice (gemm_plan, launch_gemm_bn).  The slab store and the epilogue are still written out
+// in each kernel: as functions they changed the 128x128 kernels' instructions (profiles/gemm_inloop_refactor_isa.txt).
 #include "kernels.h"
 #include <stdlib.h>
 #include <mutex>
@@ -25,6 +31,80 @@
 namespace mtmc {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// ------------------------------------------------------------------------------------------------
+// Staging steps shared by gemm_bn_kernel, gemm_bn_bf16x6_kernel and gemm_bn_f16x3_kernel.  Block = 256 threads = 2x2
+// waves, each wave TM x TN accumulator tiles of one 32x32 MFMA; BM = 64 TM rows, BN = 64 TN columns, BK columns per k-tile.
+// ------------------------------------------------------------------------------------------------
+
+// XCD-aware tile order: blocks b, b+8, b+16, ... share an XCD (round-robin dispatch); give each XCD
+// whole row panels so the A panel is re-read from its own L2 by the panel's column tiles.
+// Past tiles_m (the grid is rounded up to whole groups of eight row panels) the block has no tile.
+struct TileAt { int tm, tn; };
+__device__ __forceinline__ TileAt tile_of_block(int tiles_n) {
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  return {(slot / tiles_n) * 8 + xcd, slot % tiles_n};
+}
+
+// The thread's i-th float4 of a [rows][BK] tile: row r of the tile, float4 c4 of that row.
+template <int BK>
+__device__ __forceinline__ void tile_slot(int i, int& r, int& c4) {
+  const int f = threadIdx.x + i * 256;
+  r = f / (BK / 4);
+  c4 = f % (BK / 4);
+}
+
+// Global -> registers, k-tile at column k0 of rows [row0, row0 + ROWS) of a row-major matrix; rows past `rows` read as 0.
+// (The fp32 and bf16x6 kernels; the fp16 kernel clamps its row pointers instead, see a_src there.)  The matrix is given by
+// reference: its fields are then read from the parameter block inside the row test, where the kernels read them before.
+template <int ROWS, int BK, typename Idx, typename Ld>
+__device__ __forceinline__ void load_tile(float4 (&reg)[ROWS * BK / 1024], const float* const& src, const Ld& ld, const Idx& row0,
+                                          const Idx& rows, int k0) {
+#pragma unroll
+  for (int i = 0; i < ROWS * BK / 1024; ++i) {
+    int r, c4;
+    tile_slot<BK>(i, r, c4);
+    const Idx row = row0 + r;
+    reg[i] = row < rows ? *reinterpret_cast<const float4*>(src + (int64_t)row * ld + k0 + c4 * 4)
+                        : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// The previous layer's BatchNorm + ReLU (+ Dropout) on four staged elements: s_in / t_in hold the affine, k0 + 4 c4 is
+// the elements' column within the resident part of it, idx the first element's index in [M][K] (the Dropout counter).
+__device__ __forceinline__ float4 input_act(float4 v, const float* s_in, const float* t_in, int k0, int c4, const Drop& drop,
+                                            unsigned stream, unsigned long long idx) {
+  const float4 s = *reinterpret_cast<const float4*>(s_in + k0 + c4 * 4);
+  const float4 t = *reinterpret_cast<const float4*>(t_in + k0 + c4 * 4);
+  v.x = fmaxf(fmaf(v.x, s.x, t.x), 0.f);
+  v.y = fmaxf(fmaf(v.y, s.y, t.y), 0.f);
+  v.z = fmaxf(fmaf(v.z, s.z, t.z), 0.f);
+  v.w = fmaxf(fmaf(v.w, s.w, t.w), 0.f);
+  if (drop.on) {
+    float dv[4] = {v.x, v.y, v.z, v.w};
+    drop_apply4(drop, stream, idx, dv);                      // (idx % 4 == 0: one hash for the four)
+    v = make_float4(dv[0], dv[1], dv[2], dv[3]);
+  }
+  return v;
+}
+
+// s_in / t_in <- the input affine of all kc columns of the block's K slice (fp32 and bf16x6; the fp16 kernel keeps
+// kAffChunk columns at a time and takes a bound on |s|, |t| on the way)
+__device__ __forceinline__ void fill_input_affine(const GemmParams& p, int k_base, int kc, float* s_in, float* t_in) {
+  for (int kk = threadIdx.x; kk < kc; kk += 256)
+    bn_affine(p.stats_in[k_base + kk], p.stats_in[p.K + k_base + kk], p.count, p.gamma_in[k_base + kk],
+              p.beta_in[k_base + kk], s_in[kk], t_in[kk]);
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
 
 // BK = 32 for the big-tile configuration (LDS budget), 64 for the few-row split-K configuration, where the
 // k-loop is a chain of dependent HBM/L2 round trips and a deeper tile halves their number.
@@ -45,18 +125,13 @@ __global__ __launch_bounds__(256) void gemm_bn_kernel(GemmParams p, int tiles_m,
 
   // XCD-aware tile order: blocks b, b+8, b+16, ... share an XCD (round-robin dispatch); give each XCD
   // whole row panels so the A panel is re-read from its own L2 by the panel's column tiles.
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int tm_idx = (slot / tiles_n) * 8 + xcd, tn_idx = slot % tiles_n;
-  if (tm_idx >= tiles_m) return;
-  const int64_t m0 = (int64_t)tm_idx * BM;
-  const int n0 = tn_idx * BN;
+  const TileAt tile = tile_of_block(tiles_n);
+  if (tile.tm >= tiles_m) return;
+  const int64_t m0 = (int64_t)tile.tm * BM;
+  const int n0 = tile.tn * BN;
 
   const bool act = p.stats_in != nullptr;
-  if (act) {
-    for (int kk = threadIdx.x; kk < kc; kk += 256)
-      bn_affine(p.stats_in[k_base + kk], p.stats_in[p.K + k_base + kk], p.count, p.gamma_in[k_base + kk],
-                p.beta_in[k_base + kk], s_in[kk], t_in[kk]);
-  }
+  if (act) fill_input_affine(p, k_base, kc, s_in, t_in);
 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid >> 1, wn = wid & 1;
@@ -64,57 +139,30 @@ __global__ __launch_bounds__(256) void gemm_bn_kernel(GemmParams p, int tiles_m,
   float4 ra[A4], rb[B4];
   auto load_tiles = [&](int kt) {
     const int k0 = k_base + kt * BK;
-#pragma unroll
-    for (int i = 0; i < A4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
-      const int64_t row = m0 + r;
-      ra[i] = row < p.M ? *reinterpret_cast<const float4*>(p.A + row * p.lda + k0 + c4 * 4)
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < B4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
-      const int n = n0 + r;
-      rb[i] = n < p.Nout ? *reinterpret_cast<const float4*>(p.W + (int64_t)n * p.K + k0 + c4 * 4)
-                         : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    load_tile<BM, BK>(ra, p.A, p.lda, m0, p.M, k0);
+    load_tile<BN, BK>(rb, p.W, p.K, n0, p.Nout, k0);
   };
   auto store_tiles = [&](int kt) {
     const int k0 = kt * BK;
 #pragma unroll
     for (int i = 0; i < A4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+      int r, c4;
+      tile_slot<BK>(i, r, c4);
       float4 v = ra[i];
-      if (act) {
-        const float4 s = *reinterpret_cast<const float4*>(s_in + k0 + c4 * 4);
-        const float4 t = *reinterpret_cast<const float4*>(t_in + k0 + c4 * 4);
-        v.x = fmaxf(fmaf(v.x, s.x, t.x), 0.f);
-        v.y = fmaxf(fmaf(v.y, s.y, t.y), 0.f);
-        v.z = fmaxf(fmaf(v.z, s.z, t.z), 0.f);
-        v.w = fmaxf(fmaf(v.w, s.w, t.w), 0.f);
-        if (p.drop_in.on) {
-          const unsigned long long idx = (unsigned long long)(m0 + r) * p.K + k_base + k0 + c4 * 4;
-          float dv[4] = {v.x, v.y, v.z, v.w};
-          drop_apply4(p.drop_in, p.drop_stream, idx, dv);        // (idx % 4 == 0: one hash for the four)
-          v = make_float4(dv[0], dv[1], dv[2], dv[3]);
-        }
-      }
+      if (act) v = input_act(v, s_in, t_in, k0, c4, p.drop_in, p.drop_stream,
+                             (unsigned long long)(m0 + r) * p.K + k_base + k0 + c4 * 4);
       *reinterpret_cast<float4*>(As + r * LDK + c4 * 4) = v;
     }
 #pragma unroll
     for (int i = 0; i < B4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+      int r, c4;
+      tile_slot<BK>(i, r, c4);
       *reinterpret_cast<float4*>(Bs + r * LDK + c4 * 4) = rb[i];
     }
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int nk = kc / BK;
   load_tiles(0);
@@ -230,35 +278,20 @@ __global__ __launch_bounds__(256) void gemm_bn_bf16x6_kernel(GemmParams p, int t
   float* s_in = reinterpret_cast<float*>(Bs + 3 * BN * LDB);
   float* t_in = s_in + kc;
 
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int tm_idx = (slot / tiles_n) * 8 + xcd, tn_idx = slot % tiles_n;
-  if (tm_idx >= tiles_m) return;
-  const int64_t m0 = (int64_t)tm_idx * BM;
-  const int n0 = tn_idx * BN;
+  const TileAt tile = tile_of_block(tiles_n);
+  if (tile.tm >= tiles_m) return;
+  const int64_t m0 = (int64_t)tile.tm * BM;
+  const int n0 = tile.tn * BN;
   const bool act = p.stats_in != nullptr;
-  if (act) {
-    for (int kk = threadIdx.x; kk < kc; kk += 256)
-      bn_affine(p.stats_in[k_base + kk], p.stats_in[p.K + k_base + kk], p.count, p.gamma_in[k_base + kk],
-                p.beta_in[k_base + kk], s_in[kk], t_in[kk]);
-  }
+  if (act) fill_input_affine(p, k_base, kc, s_in, t_in);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid >> 1, wn = wid & 1;
 
   float4 ra[A4], rb[B4];
   auto load_tiles = [&](int kt) {
     const int k0 = k_base + kt * BK;
-#pragma unroll
-    for (int i = 0; i < A4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
-      const int64_t row = m0 + r;
-      ra[i] = row < p.M ? *reinterpret_cast<const float4*>(p.A + row * p.lda + k0 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < B4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
-      const int n = n0 + r;
-      rb[i] = n < p.Nout ? *reinterpret_cast<const float4*>(p.W + (int64_t)n * p.K + k0 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    load_tile<BM, BK>(ra, p.A, p.lda, m0, p.M, k0);
+    load_tile<BN, BK>(rb, p.W, p.K, n0, p.Nout, k0);
   };
   auto put = [&](__bf16* base, int rows, int r, int c4, float4 v) {
     bf16x4 q1, q2, q3;
@@ -273,38 +306,23 @@ __global__ __launch_bounds__(256) void gemm_bn_bf16x6_kernel(GemmParams p, int t
     const int k0 = kt * BK;
 #pragma unroll
     for (int i = 0; i < A4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+      int r, c4;
+      tile_slot<BK>(i, r, c4);
       float4 v = ra[i];
-      if (act) {
-        const float4 s = *reinterpret_cast<const float4*>(s_in + k0 + c4 * 4);
-        const float4 t = *reinterpret_cast<const float4*>(t_in + k0 + c4 * 4);
-        v.x = fmaxf(fmaf(v.x, s.x, t.x), 0.f);
-        v.y = fmaxf(fmaf(v.y, s.y, t.y), 0.f);
-        v.z = fmaxf(fmaf(v.z, s.z, t.z), 0.f);
-        v.w = fmaxf(fmaf(v.w, s.w, t.w), 0.f);
-        if (p.drop_in.on) {
-          const unsigned long long idx = (unsigned long long)(m0 + r) * p.K + k_base + k0 + c4 * 4;
-          float dv[4] = {v.x, v.y, v.z, v.w};
-          drop_apply4(p.drop_in, p.drop_stream, idx, dv);        // (idx % 4 == 0: one hash for the four)
-          v = make_float4(dv[0], dv[1], dv[2], dv[3]);
-        }
-      }
+      if (act) v = input_act(v, s_in, t_in, k0, c4, p.drop_in, p.drop_stream,
+                             (unsigned long long)(m0 + r) * p.K + k_base + k0 + c4 * 4);
       put(As, BM, r, c4, v);
     }
 #pragma unroll
     for (int i = 0; i < B4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+      int r, c4;
+      tile_slot<BK>(i, r, c4);
       put(Bs, BN, r, c4, rb[i]);
     }
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int nk = kc / BK;
   load_tiles(0);
@@ -425,6 +443,8 @@ __global__ __launch_bounds__(256) void gemm_bn_f16x3_kernel(GemmParams p, int ti
   const int aff_n = kc < kAffChunk ? kc : kAffChunk;  // BatchNorm affine of the input: kAffChunk columns at a time
   float* t_in = s_in + aff_n;
 
+  // tile_of_block's order, written out: through the function this kernel's epilogue multiplies rows by ldy with other
+  // instructions (profiles/gemm_inloop_refactor_isa.txt)
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int tm_idx = (slot / tiles_n) * 8 + xcd, tn_idx = slot % tiles_n;
   if (tm_idx >= tiles_m) return;
@@ -492,13 +512,15 @@ __global__ __launch_bounds__(256) void gemm_bn_f16x3_kernel(GemmParams p, int ti
   const float* b_src[B4];
 #pragma unroll
   for (int i = 0; i < A4; ++i) {
-    const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+    int r, c4;
+    tile_slot<BK>(i, r, c4);
     const int64_t row = m0 + r < p.M ? m0 + r : p.M - 1;
     a_src[i] = p.A + row * p.lda + k_base + c4 * 4;
   }
 #pragma unroll
   for (int i = 0; i < B4; ++i) {
-    const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+    int r, c4;
+    tile_slot<BK>(i, r, c4);
     const int n = n0 + r < p.Nout ? n0 + r : p.Nout - 1;
     b_src[i] = p.W + (int64_t)n * p.K + k_base + c4 * 4;
   }
@@ -545,38 +567,23 @@ __global__ __launch_bounds__(256) void gemm_bn_f16x3_kernel(GemmParams p, int ti
     const float sa = sc[0], sw = sc[1];
 #pragma unroll
     for (int i = 0; i < A4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+      int r, c4;
+      tile_slot<BK>(i, r, c4);
       float4 v = ra[i];
-      if (act) {
-        const float4 s = *reinterpret_cast<const float4*>(s_in + (k0 % kAffChunk) + c4 * 4);
-        const float4 t = *reinterpret_cast<const float4*>(t_in + (k0 % kAffChunk) + c4 * 4);
-        v.x = fmaxf(fmaf(v.x, s.x, t.x), 0.f);
-        v.y = fmaxf(fmaf(v.y, s.y, t.y), 0.f);
-        v.z = fmaxf(fmaf(v.z, s.z, t.z), 0.f);
-        v.w = fmaxf(fmaf(v.w, s.w, t.w), 0.f);
-        if (p.drop_in.on) {
-          const unsigned long long idx = (unsigned long long)(m0 + r) * p.K + k_base + k0 + c4 * 4;
-          float dv[4] = {v.x, v.y, v.z, v.w};
-          drop_apply4(p.drop_in, p.drop_stream, idx, dv);        // (idx % 4 == 0: one hash for the four)
-          v = make_float4(dv[0], dv[1], dv[2], dv[3]);
-        }
-      }
+      if (act) v = input_act(v, s_in, t_in, (k0 % kAffChunk), c4, p.drop_in, p.drop_stream,
+                             (unsigned long long)(m0 + r) * p.K + k_base + k0 + c4 * 4);
       put(As, PSA, r, c4, v, sa);
     }
 #pragma unroll
     for (int i = 0; i < B4; ++i) {
-      const int f = threadIdx.x + i * 256, r = f / C4, c4 = f % C4;
+      int r, c4;
+      tile_slot<BK>(i, r, c4);
       put(Bs, PSB, r, c4, rb[i], sw);
     }
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int nk = kc / BK;
   load_tiles(0);
@@ -692,33 +699,6 @@ bool allow_big_lds(const void* fn, int bytes) {
   return true;
 }
 
-template <int TM, int TN, int BK>
-static int launch_f16x3(const GemmParams& p, hipStream_t s) {
-  constexpr int BM = 64 * TM, BN = 64 * TN, LDB = BK + 8;
-  const int tiles_m = (int)((p.M + BM - 1) / BM), tiles_n = (p.Nout + BN - 1) / BN;
-  const int grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
-  const int kc = p.K / p.split_k;
-  size_t lds = (size_t)2 * (BM + BN) * LDB * 2 + (size_t)(2 * (kc < kAffChunk ? kc : kAffChunk) + 12) * sizeof(float);
-  const size_t epi = (size_t)4 * BN * sizeof(double);
-  if (lds < epi) lds = epi;
-  if (!allow_big_lds(reinterpret_cast<const void*>(gemm_bn_f16x3_kernel<TM, TN, BK>), 128 * 1024)) return MTMC_E_HIP;
-  hipLaunchKernelGGL((gemm_bn_f16x3_kernel<TM, TN, BK>), dim3(grid + p.pass_blocks, p.split_k), dim3(256), lds, s, p, tiles_m, tiles_n);
-  return MTMC_OK;
-}
-
-template <int TM, int TN, int BK>
-static int launch_bf16x6(const GemmParams& p, hipStream_t s) {
-  constexpr int BM = 64 * TM, BN = 64 * TN, LDB = BK + 8;
-  const int tiles_m = (int)((p.M + BM - 1) / BM), tiles_n = (p.Nout + BN - 1) / BN;
-  const int grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
-  size_t lds = (size_t)3 * (BM + BN) * LDB * 2 + (size_t)2 * (p.K / p.split_k) * sizeof(float);
-  const size_t epi = (size_t)4 * BN * sizeof(double);
-  if (lds < epi) lds = epi;
-  if (!allow_big_lds(reinterpret_cast<const void*>(gemm_bn_bf16x6_kernel<TM, TN, BK>), 160 * 1024)) return MTMC_E_HIP;
-  hipLaunchKernelGGL((gemm_bn_bf16x6_kernel<TM, TN, BK>), dim3(grid, p.split_k), dim3(256), lds, s, p, tiles_m, tiles_n);
-  return MTMC_OK;
-}
-
 // Second half of a split-K layer: Y = bias + sum of the K-slices' slabs (fixed order => reproducible),
 // and the fp64 column statistics of Y.  Block = 64 columns x kCombRows rows; thread = one column, every 4th row;
 // all of a row's slice loads are issued together (they are independent; only the additions are ordered).
@@ -797,15 +777,40 @@ __global__ __launch_bounds__(256) void linear_generic_kernel(GemmParams p) {
     for (int i = threadIdx.x; i < 2 * p.Nout; i += 256) unsafeAtomicAdd(p.stats_out + i, cs[i]);
 }
 
-template <int TM, int TN, int BK>
-static void launch_cfg(const GemmParams& p, hipStream_t s) {
-  constexpr int BM = 64 * TM, BN = 64 * TN, LDK = BK + 4;
+// The three operand formats on the host: the kernel, the LDS bytes of its operand stage (rows = BM + BN) and input affine
+// (kc = the block's share of K), and the dynamic-LDS limit the kernel is registered with (0: the default 64 KiB do).
+struct Fp32 {
+  static constexpr int lds_cap = 0;
+  static size_t lds(int rows, int BK, int kc) { return (size_t)rows * (BK + 4) * sizeof(float) + (size_t)2 * kc * sizeof(float); }
+  template <int TM, int TN, int BK> static constexpr auto kernel() { return gemm_bn_kernel<TM, TN, BK>; }
+};
+struct Bf16x6 {
+  static constexpr int lds_cap = 160 * 1024;
+  static size_t lds(int rows, int BK, int kc) { return (size_t)3 * rows * (BK + 8) * 2 + (size_t)2 * kc * sizeof(float); }
+  template <int TM, int TN, int BK> static constexpr auto kernel() { return gemm_bn_bf16x6_kernel<TM, TN, BK>; }
+};
+struct F16x3 {
+  static constexpr int lds_cap = 128 * 1024;
+  static size_t lds(int rows, int BK, int kc) {
+    return (size_t)2 * rows * (BK + 8) * 2 + (size_t)(2 * (kc < kAffChunk ? kc : kAffChunk) + 12) * sizeof(float);
+  }
+  template <int TM, int TN, int BK> static constexpr auto kernel() { return gemm_bn_f16x3_kernel<TM, TN, BK>; }
+};
+
+// One block per tile, the row panels rounded up to whole groups of eight (tile_of_block), split_k slices along y; the
+// passenger blocks (fp16 only: launch_gemm_bn clears pass_blocks for every other kernel) ride behind the tiles.
+template <class Fmt, int TM, int TN, int BK>
+static int launch_tiles(const GemmParams& p, hipStream_t s) {
+  constexpr int BM = 64 * TM, BN = 64 * TN;
   const int tiles_m = (int)((p.M + BM - 1) / BM), tiles_n = (p.Nout + BN - 1) / BN;
   const int grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
-  size_t lds = (size_t)(BM + BN) * LDK * sizeof(float) + (size_t)2 * (p.K / p.split_k) * sizeof(float);
+  size_t lds = Fmt::lds(BM + BN, BK, p.K / p.split_k);
   const size_t epi = (size_t)4 * BN * sizeof(double);
   if (lds < epi) lds = epi;
-  hipLaunchKernelGGL((gemm_bn_kernel<TM, TN, BK>), dim3(grid, p.split_k), dim3(256), lds, s, p, tiles_m, tiles_n);
+  const auto kernel = Fmt::template kernel<TM, TN, BK>();
+  if (Fmt::lds_cap && !allow_big_lds(reinterpret_cast<const void*>(kernel), Fmt::lds_cap)) return MTMC_E_HIP;
+  hipLaunchKernelGGL(kernel, dim3(grid + p.pass_blocks, p.split_k), dim3(256), lds, s, p, tiles_m, tiles_n);
+  return MTMC_OK;
 }
 
 void launch_combine(const GemmParams& p, hipStream_t s) {
@@ -813,15 +818,17 @@ void launch_combine(const GemmParams& p, hipStream_t s) {
                      dim3(256), 0, s, p);
 }
 
+// The K the MFMA kernels take.  K > 6144 is only a limit for layers with an input BatchNorm under the fp32 / bf16 kernels
+// (their whole input affine sits in LDS); the fp16 kernel chunks it, and a product without an input affine (the
+// weight-gradient GEMM of the backward reduces over the node rows: K = N) has none.
+static bool mfma_shape(int K, bool long_k_ok) { return K % 32 == 0 && (K <= 6144 || long_k_ok); }
+
 // 0: MFMA kernel not applicable; 1: 64x64 tiles; 2: 128x128 tiles.  *split_k > 1 only for few-row problems,
 // where one block per output tile would leave most of the 256 CUs idle and serialise the whole K loop.
-// K > 6144 is only a limit for layers with an input BatchNorm under the fp32 / bf16 kernels (their whole input affine
-// sits in LDS); the fp16 kernel chunks it, and a product without an input affine (the weight-gradient GEMM of the
-// backward reduces over the node rows: K = N) has none.
 int gemm_plan(int64_t M, int K, int Nout, int* split_k, bool long_k_ok) {
   constexpr int BK = 64;
   *split_k = 1;
-  if (K % 32 != 0 || (K > 6144 && !long_k_ok)) return 0;
+  if (!mfma_shape(K, long_k_ok)) return 0;
   const int64_t big_tiles = ((M + 127) / 128) * ((Nout + 127) / 128);
   if (big_tiles >= 256 && Nout >= 128) return 2;   // one 128x128 tile per CU or more (fp16 kernel: 256 beats 512 at M = 6000)
   const int64_t tiles = ((M + 63) / 64) * ((Nout + 63) / 64);
@@ -838,7 +845,7 @@ int launch_gemm_bn(const GemmParams& p, hipStream_t s, int which) {
   const bool fp32_only = knobs().gemm_fp32, no_f16 = knobs().gemm_no_f16;
   const bool f16_ok = p.amax_a && p.amax_w && !fp32_only && !no_f16;
   const bool long_k_ok = f16_ok;          // the fp16 kernel keeps at most kAffChunk affine columns in LDS at a time
-  if (p.K % 32 != 0 || (p.K > 6144 && !long_k_ok) || (p.lda % 4) != 0 || ((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15)) {
+  if (!mfma_shape(p.K, long_k_ok) || (p.lda % 4) != 0 || ((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15)) {
     if (p.stats_in != nullptr || p.Nout > 2048) return MTMC_E_ARG;
     if (!(which & 1)) return MTMC_OK;
     const int64_t blocks = (p.M * p.Nout + 255) / 256;
@@ -856,16 +863,15 @@ int launch_gemm_bn(const GemmParams& p, hipStream_t s, int which) {
   const bool job_behind = p.pass_blocks > 0 && !carries;
   if (!carries) q.pass_blocks = 0;
   if (which & 1) {
-    const bool f16 = f16_ok;
-    int rc = MTMC_OK;
-    if (cfg == 2 && f16 && p.K % 64 == 0) rc = launch_f16x3<2, 2, 64>(q, s);
-    else if (cfg == 2 && f16) rc = launch_f16x3<2, 2, 32>(q, s);
-    else if (cfg == 1 && f16 && (p.K / q.split_k) % 64 == 0) rc = launch_f16x3<1, 1, 64>(q, s);
-    else if (cfg == 1 && f16) rc = launch_f16x3<1, 1, 32>(q, s);
-    else if (cfg == 2 && !fp32_only) rc = launch_bf16x6<2, 2, 32>(q, s);
-    else if (cfg == 2) launch_cfg<2, 2, 32>(q, s);
-    else if ((p.K / q.split_k) % 64 == 0) launch_cfg<1, 1, 64>(q, s);
-    else launch_cfg<1, 1, 32>(q, s);
+    int rc;
+    if (cfg == 2 && f16_ok && p.K % 64 == 0) rc = launch_tiles<F16x3, 2, 2, 64>(q, s);
+    else if (cfg == 2 && f16_ok) rc = launch_tiles<F16x3, 2, 2, 32>(q, s);
+    else if (cfg == 1 && f16_ok && (p.K / q.split_k) % 64 == 0) rc = launch_tiles<F16x3, 1, 1, 64>(q, s);
+    else if (cfg == 1 && f16_ok) rc = launch_tiles<F16x3, 1, 1, 32>(q, s);
+    else if (cfg == 2 && !fp32_only) rc = launch_tiles<Bf16x6, 2, 2, 32>(q, s);
+    else if (cfg == 2) rc = launch_tiles<Fp32, 2, 2, 32>(q, s);
+    else if ((p.K / q.split_k) % 64 == 0) rc = launch_tiles<Fp32, 1, 1, 64>(q, s);
+    else rc = launch_tiles<Fp32, 1, 1, 32>(q, s);
     if (rc != MTMC_OK) return rc;
     if (job_behind) launch_enc2(p.pass_enc, p.pass_attr, p.pass_edges, p.pass_e_total, p.pass_stat, s);
   }

@@ -2,13 +2,13 @@
 tracklets (tests/test_gram_cases.py on the CPU, tests/test_gpu_graph_build_regimes.py on the GPU).  No GPU in here.
 
 G = X X^T goes through launch_gemm_bn(plain_gemm(...)) without |.|max words, so gemm_plan / launch_gemm_bn
-(csrc/gemm_bn.hip:821-874) choose, with M = Nout = N and K = F:
+(csrc/gemm_bn.hip, the last two functions) choose, with M = Nout = N and K = F:
     exact fp32 MFMA, 64 x 64 tiles, split-K 4     F % 256 == 0, N <= 960
     the same, split-K 2                           F % 128 == 0, F % 256 != 0, N <= 960
     the same, unsplit, BK = 64                    F <= 128 or F % 128 != 0, with F % 64 == 0; any such F at 961 <= N <= 1920
     the same, unsplit, BK = 32                    F % 64 != 0
-    gemm_bn_bf16x6_kernel<2,2,32>, 128 x 128      N >= 1921: ceil(N / 128)^2 >= 256 tiles (gemm_bn.hip:825-826)
-    linear_generic_kernel (scalar)                F > 6144 (gemm_bn.hip:824, :841); refused at N > 2048 (:842)
+    gemm_bn_bf16x6_kernel<2,2,32>, 128 x 128      N >= 1921: ceil(N / 128)^2 >= 256 tiles (gemm_plan: big_tiles)
+    linear_generic_kernel (scalar)                F > 6144 (mfma_shape, which both call); refused at N > 2048 (launch_gemm_bn)
 The split shows in mtmc_graph_workspace_bytes (slab term split * N^2 * 4 bytes); the last two rules do not: they are
 restated above from the lines named and a change there has to be followed here by hand.
 """
