@@ -150,6 +150,10 @@ SIGNATURES = {
     "mtmc_pool_tracklets_workspace_bytes": (_sz, [_i64, _i32]),
     "mtmc_pool_tracklets": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _sz, _p]),
     "mtmc_pool_tracklets_backward": (_i32, [_p, _i64, _i32, _p, _i64, _p, _i64, _p]),
+    "mtmc_pool_tracklets_weighted_workspace_bytes": (_sz, [_i64, _i32]),
+    "mtmc_pool_tracklets_weighted": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mtmc_pool_tracklets_weighted_backward": (_i32, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
+    "mtmc_pool_tracklets_weight_grad": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -25,7 +25,8 @@
  *   mtmc_build_graph           <- graph construction around the call  inference.py:402-456, train.py:316-342
  *   mtmc_postprocess           <- softmax/argmax + post_processing    inference.py:475-489, :70-169; utils.py:30-339
  *   mtmc_pool_tracklets        <- per-tracklet mean of the detections' embeddings  train.py:305-316,
- *                                 libs/reid_feature_extraction.py:177-178
+ *                                 libs/reid_feature_extraction.py:177-178 (mtmc_pool_tracklets_weighted: rows in any order, a weight per
+ *                                 detection, libs/filter_mtmc.py's filters as weights)
  *
  * All floating tensors are fp32, row-major, contiguous unless a stride argument says otherwise;
  * BatchNorm statistics are accumulated in fp64.  All work is enqueued on `stream` (a hipStream_t
@@ -610,6 +611,46 @@ int32_t mtmc_pool_tracklets(const float* embeds, int64_t row_stride, int64_t n_r
                             void* workspace, size_t workspace_bytes, void* stream);
 int32_t mtmc_pool_tracklets_backward(const float* grad_out, int64_t n_rows, int32_t feat_dim, const int64_t* offsets,
                                      int64_t n_tracklets, float* grad_embeds, int64_t grad_row_stride, void* stream);
+
+/* ---- the same for detections in any order and with per-detection weights ----
+ * out[s] = (sum_r w_r x_r) / (sum_r w_r) over the rows of tracklet s: box area, ROI and confidence filters
+ * (libs/filter_mtmc.py) as a weight in the mean, and rows that arrive frame by frame instead of tracklet by tracklet.
+ * The three entry points above keep their signatures and their kernels; these take two optional arrays in device memory:
+ *   perm    [n_rows] int64 or NULL: position j of the grouped order holds detection row perm[j], and offsets cut the
+ *           POSITIONS: tracklet s owns positions [offsets[s], offsets[s+1]).  NULL: position j is row j.  With perm,
+ *           offsets[n_tracklets] may be less than n_rows (the positions behind it belong to no tracklet) and an empty
+ *           range is legal.  Every row is to be named once; the sums run in position order.
+ *   weights [n_rows] fp32 or NULL (all 1), indexed by the detection ROW: finite and >= 0.
+ *   wsum    [n_tracklets] fp32, written by the forward: the denominators sum_r w_r, which the two backwards read.
+ *   info    [MTMC_POOL_INFO] int32 (may be NULL), cleared by the first kernel as above:
+ *           info[0] a set of bits: 1 = offsets decrease (without perm: do not strictly increase) or leave [0, n_rows];
+ *                   2 = offsets[0] != 0, or without perm offsets[n_tracklets] != n_rows; 4 = a perm entry outside
+ *                   [0, n_rows); 8 = a weight that is negative, infinite or NaN
+ *           info[1] tracklets with a bad range (bits 1, 2)
+ *           info[2] tracklets that got a zero row: an empty range, or weights that add up to 0 (wsum[s] = 0)
+ *           info[3] positions that count for nothing: a perm entry outside [0, n_rows), or behind offsets[n_tracklets]
+ *           Nothing read from device memory becomes an address unclamped: a bad perm entry names no row (weight 0, no
+ *           gradient row written), a bad weight counts as 0.  A row with weight 0 adds nothing, whatever it holds.
+ * The sums keep the decomposition above (chunks of mtmc_pool_chunk_rows() positions, head and tail partial sums added in
+ * chunk order, fmaf(w, x, acc) per row; no atomics on floats), the weight sums beside the row sums: with every weight 1
+ * the result has the bits of mtmc_pool_tracklets.  Workspace: the partial rows plus 3 words a chunk.
+ * mtmc_pool_tracklets_weighted_backward: grad_embeds[perm[j]] = w * grad_out[s] / wsum[s] for every position j of s, zeros
+ * for positions of no tracklet and where wsum[s] = 0; each named row is written exactly once.
+ * mtmc_pool_tracklets_weight_grad: grad_weights[perm[j]] = grad_out[s] . (embeds[perm[j]] - out[s]) / wsum[s] (0 where the
+ * backward writes zeros); embeds is read once, each dot product is summed in one fixed order.  out is the forward's result.
+ * Sizes, alignment, the empty cases and the error codes are those of the entry points above. */
+size_t mtmc_pool_tracklets_weighted_workspace_bytes(int64_t n_rows, int32_t feat_dim);
+int32_t mtmc_pool_tracklets_weighted(const float* embeds, int64_t row_stride, int64_t n_rows, int32_t feat_dim,
+                                     const int64_t* offsets, int64_t n_tracklets, const int64_t* perm, const float* weights,
+                                     float* out, float* wsum, int32_t* info, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int32_t mtmc_pool_tracklets_weighted_backward(const float* grad_out, int64_t n_rows, int32_t feat_dim, const int64_t* offsets,
+                                              int64_t n_tracklets, const int64_t* perm, const float* weights,
+                                              const float* wsum, float* grad_embeds, int64_t grad_row_stride, void* stream);
+int32_t mtmc_pool_tracklets_weight_grad(const float* embeds, int64_t row_stride, int64_t n_rows, int32_t feat_dim,
+                                        const int64_t* offsets, int64_t n_tracklets, const int64_t* perm,
+                                        const float* grad_out, const float* out, const float* wsum, float* grad_weights,
+                                        void* stream);
 
 #ifdef __cplusplus
 }
