@@ -16,6 +16,7 @@ from . import ops  # noqa: F401
 from .ops import FocalLoss, cross_entropy, cross_entropy_steps, edge_loss, focal_loss  # noqa: F401
 from . import metrics  # noqa: F401
 from .metrics import ClusterScores, EdgePRF, cluster_scores, edge_prf, evaluate  # noqa: F401
+from .metrics import IdScores, idf1, relabel_detections  # noqa: F401
 from .feature_store import FeatureStore  # noqa: F401
 from .modules import (MLP, EdgeModel, MetaLayer, MLPGraphIndependent, MOTMPNet,  # noqa: F401
                       NodeModel)
@@ -23,4 +24,4 @@ from .modules import (MLP, EdgeModel, MetaLayer, MLPGraphIndependent, MOTMPNet, 
 __all__ = ["MOTMPNet", "MetaLayer", "EdgeModel", "NodeModel", "MLPGraphIndependent", "MLP",
            "DEFAULT_GRAPH_NET_PARAMS", "DEFAULT_ARCH", "default_params", "build_graph", "postprocess", "FeatureStore", "cross_entropy", "cross_entropy_steps", "edge_loss", "ops",
            "metrics", "cluster_scores", "edge_prf", "evaluate", "ClusterScores", "EdgePRF", "pool", "pool_tracklets",
-           "focal_loss", "FocalLoss"]
+           "focal_loss", "FocalLoss", "idf1", "relabel_detections", "IdScores"]

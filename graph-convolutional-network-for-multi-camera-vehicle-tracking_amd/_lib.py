@@ -85,6 +85,7 @@ EDGE_LOSS_RECORD = 4
 CLUSTER_SCORES, CLUSTER_COUNTS, EDGE_PRF = 9, 7, 5        # mtmc_cluster_scores: scores / counts; mtmc_edge_prf: out
 CLUSTER_SCORES_MAX_N = 1048576
 POOL_INFO = 4                                             # mtmc_pool_tracklets: info words
+ID_MAX_CELLS, ID_MAX_CAMERAS = 1 << 26, 64                # mtmc_id_overlap: n_obj * n_hyp; mtmc_id_filter: cameras
 
 # MTMC_MPN_LIB: another build of the same ABI (same-box A/B of two library versions, tools/lib_ab.sh); default: the in-tree build
 LIB_PATH = os.environ.get("MTMC_MPN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmtmc_mpn.so")
@@ -154,6 +155,12 @@ SIGNATURES = {
     "mtmc_pool_tracklets_weighted": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "mtmc_pool_tracklets_weighted_backward": (_i32, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
     "mtmc_pool_tracklets_weight_grad": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "mtmc_id_filter": (_i32, [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _p, _p, _i32, _i32, _i32, _i32, _i32,
+                              _p, _p, _p, _p, _p]),
+    "mtmc_id_overlap_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "mtmc_id_overlap": (_i32, [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f64, _p, _sz, _p]),
+    "mtmc_id_cells": (_i32, [_p, _i64, _i64, _p, _i64, _p, _p]),
+    "mtmc_id_assign": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -8,8 +8,12 @@
       int64 predictions that `postprocess` returns
   evaluate         both, with ID_GT = the connected components of the label-1 edges (utils.py:30-52) from `postprocess`
 
-All of them run HIP kernels through the C ABI, read nothing back to the host and leave their results on the device; CPU
-tensors are refused.  Neither scikit-learn nor networkx is needed.
+  relabel_detections, idf1   what main.py:166-213 does with the clusters: the detections written back with the cluster
+      number as identity (inference.py:538-551), then IDF1 / IDP / IDR / IDTP / IDFP / IDFN of eval/eval.py::eval
+
+All of them run HIP kernels through the C ABI; CPU tensors are refused.  The first three read nothing back to the host
+and leave their results on the device; `idf1` reads the non-zero overlap counts and solves the ID assignment on the host
+(in the library, not in Python).  Neither scikit-learn, networkx, motmetrics nor pandas is needed.
 """
 from __future__ import annotations
 
@@ -24,6 +28,7 @@ from .postprocess import postprocess
 ClusterScores = collections.namedtuple("ClusterScores", ["ari", "ami", "homogeneity", "completeness", "v_measure",
                                                          "entropy_true", "entropy_pred", "mi", "emi", "counts"])
 EdgePRF = collections.namedtuple("EdgePRF", ["confusion", "precision", "recall", "f_score", "class_precision"])
+IdScores = collections.namedtuple("IdScores", "idf1 idp idr idtp idfp idfn num_objects num_predictions matches kept")
 
 MAX_LABELS = _lib.CLUSTER_SCORES_MAX_N
 _INT_TYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
@@ -88,3 +93,173 @@ def evaluate(ID_pred, predictions, edge_index, edge_labels, num_nodes: int):
                      preds_prob=edge_labels, predictions=edge_labels, check=False)
     return types.SimpleNamespace(ID_GT=gt.ID_pred, clusters=cluster_scores(gt.ID_pred, ID_pred),
                                  edges=edge_prf(predictions, edge_labels))
+
+
+# ---- IDF1 / IDP / IDR: the score the reference reports (main.py:166-213, eval/eval.py::eval) ----------
+_TABLE_TYPES = (torch.int32, torch.int64, torch.float32, torch.float64)
+
+
+def relabel_detections(table, index, ID_pred):
+    """The reference's last step (inference.py:538-551): a copy of the [n, 7] detection table (camera, id, frame, x, y,
+    width, height) whose id column is ID_pred[index], `index` [n] naming the node (tracklet) of each detection.  Plain
+    torch, so it works on CPU tensors as on the device."""
+    if table.dim() != 2 or table.shape[1] < 2 or index.dim() != 1 or index.shape[0] != table.shape[0]:
+        raise ValueError("mtmc_mpn.relabel_detections: table must be [n, >= 2] and index [n]")
+    out = table.clone()
+    out[:, 1] = ID_pred[index.long()].to(table.dtype)
+    return out
+
+
+def _id_table(name, t):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 7 or t.dtype not in _TABLE_TYPES:
+        raise ValueError(f"mtmc_mpn.idf1: {name} must be an [n, 7] int32, int64, float32 or float64 tensor "
+                         "(camera, id, frame, x, y, width, height)")
+    if t.shape[0] >= 2 ** 31:
+        raise ValueError(f"mtmc_mpn.idf1: {name} has 2^31 rows or more")
+    return t[:, :3].to(torch.int64), t[:, 3:7].to(torch.float64)
+
+
+def _id_side(group_inv, ident_inv, cam_inv, boxes, n_ident, n_groups):
+    """One table in grouped order: a stable sort by (group, identity), so repeats stay in input order."""
+    dev = boxes.device
+    _, perm = torch.sort(group_inv * max(n_ident, 1) + ident_inv, stable=True)
+    group = group_inv[perm]
+    return types.SimpleNamespace(
+        perm=perm, n=boxes.shape[0], n_ident=n_ident, boxes=boxes[perm].contiguous(), group=group.to(torch.int32),
+        cam=cam_inv[perm].to(torch.int32), ident=ident_inv[perm].to(torch.int32), keep=None,
+        offsets=torch.searchsorted(group, torch.arange(n_groups + 1, dtype=torch.int64, device=dev)))
+
+
+def _id_filter(side, n_cam, counter, band, roi, planes, min_cameras, drop_repeats):
+    dev = side.boxes.device
+    stage = torch.empty(side.n, dtype=torch.uint8, device=dev)
+    side.keep = torch.empty(side.n, dtype=torch.uint8, device=dev)
+    cameras = torch.empty(side.n_ident, dtype=torch.int64, device=dev)
+    ptr = (lambda t: t.data_ptr()) if side.n else (lambda t: None)
+    _call.run(dev, _lib.load().mtmc_id_filter, ptr(side.boxes), ptr(side.cam), ptr(side.ident), ptr(side.group), side.n,
+              side.n_ident, n_cam, int(band is not None), *(band or (0.0, 0.0, 0.0, 0.0)),
+              roi.data_ptr() if roi is not None else None, planes.data_ptr() if roi is not None else None,
+              *((roi.shape[0], roi.shape[1], roi.shape[2]) if roi is not None else (0, 0, 0)), int(min_cameras),
+              int(bool(drop_repeats)), ptr(stage), ptr(side.keep), ptr(cameras), counter.data_ptr(), _call.stream(dev))
+
+
+def _id_passes(gt, pred, max_dist, min_cameras, drop_repeats, roi, roi_cameras, border, image_size):
+    """Grouping in torch on the device, then the filter and overlap passes.  Returns a namespace: the two grouped sides,
+    the identity values, the workspace whose first n_obj * n_hyp int32 words are C, and counters (int64 [3] on the device:
+    ground-truth rows kept, prediction rows kept, non-zero cells -- the last written by `mtmc_id_cells`)."""
+    gkeys, gbox = _id_table("gt", gt)
+    pkeys, pbox = _id_table("pred", pred)
+    _call.require_gpu("idf1", gt, pred)
+    dev = gt.device
+    n_gt, n_pr = gt.shape[0], pred.shape[0]
+    cams, cam_inv = torch.unique(torch.cat([gkeys[:, 0], pkeys[:, 0]]), return_inverse=True)
+    n_cam = cams.numel()
+    if n_cam > _lib.ID_MAX_CAMERAS:
+        raise ValueError(f"mtmc_mpn.idf1: {n_cam} cameras, at most {_lib.ID_MAX_CAMERAS}")
+    frames, frame_inv = torch.unique(torch.cat([gkeys[:, 2], pkeys[:, 2]]), return_inverse=True)
+    groups, group_inv = torch.unique(cam_inv * max(frames.numel(), 1) + frame_inv, return_inverse=True)
+    obj_ids, obj_inv = torch.unique(gkeys[:, 1], return_inverse=True)
+    hyp_ids, hyp_inv = torch.unique(pkeys[:, 1], return_inverse=True)
+    n_groups, n_obj, n_hyp = groups.numel(), obj_ids.numel(), hyp_ids.numel()
+    lib = _lib.load()
+    need = lib.mtmc_id_overlap_workspace_bytes(n_obj, n_hyp, n_groups)
+    if need == 0:
+        raise ValueError(f"mtmc_mpn.idf1: {n_obj} ground-truth x {n_hyp} predicted identities are more than "
+                         f"{_lib.ID_MAX_CELLS} cells (or 2^31 groups)")
+    band = planes = None
+    if border is not None:
+        if image_size is None:
+            raise ValueError("mtmc_mpn.idf1: border needs image_size=(W, H)")
+        w, h, p = image_size[0], image_size[1], float(border)
+        band = (float(w * p), float(w - w * p), float(h * p), float(h - h * p))
+    if roi is not None:
+        if roi.dim() != 3 or roi.dtype != torch.uint8 or roi_cameras is None or len(roi_cameras) != roi.shape[0]:
+            raise ValueError("mtmc_mpn.idf1: roi must be a [C, Hr, Wr] uint8 mask stack with roi_cameras = its C camera values")
+        _call.require_gpu("idf1", gt, roi)
+        roi = roi.contiguous()
+        hit = cams[:, None] == torch.as_tensor(roi_cameras, dtype=torch.int64, device=dev)[None, :]
+        planes = torch.where(hit.any(1), hit.int().argmax(1), -1).to(torch.int32)
+        if n_pr and bool((planes[cam_inv[n_gt:]] < 0).any()):
+            raise ValueError("mtmc_mpn.idf1: a prediction's camera has no plane in roi (roi_cameras)")
+    g = _id_side(group_inv[:n_gt], obj_inv, cam_inv[:n_gt], gbox, n_obj, n_groups)
+    q = _id_side(group_inv[n_gt:], hyp_inv, cam_inv[n_gt:], pbox, n_hyp, n_groups)
+    counters = torch.zeros(3, dtype=torch.int64, device=dev)
+    if band is not None:
+        _id_filter(g, n_cam, counters[0:1], band, None, None, 0, False)
+    else:
+        counters[0] = n_gt
+    _id_filter(q, n_cam, counters[1:2], band, roi, planes, min_cameras, drop_repeats)
+    r = types.SimpleNamespace(gt=g, pred=q, obj_ids=obj_ids, hyp_ids=hyp_ids, n_obj=n_obj, n_hyp=n_hyp, n_groups=n_groups,
+                              n_cam=n_cam, ws=torch.empty(need, dtype=torch.uint8, device=dev), counters=counters, dev=dev)
+    _id_overlap(r, max_dist)
+    return r
+
+
+def _id_overlap(r, max_dist):
+    g, q = r.gt, r.pred
+    ptr = (lambda t: t.data_ptr()) if g.n > 0 and q.n > 0 else (lambda t: None)
+    _call.run(r.dev, _lib.load().mtmc_id_overlap, ptr(g.boxes), ptr(g.offsets), ptr(g.ident),
+              ptr(g.keep) if g.keep is not None else None, g.n, ptr(q.boxes), ptr(q.offsets), ptr(q.ident), ptr(q.keep), q.n,
+              r.n_groups, r.n_obj, r.n_hyp, float(max_dist), r.ws.data_ptr(), r.ws.numel(), _call.stream(r.dev))
+
+
+def _input_order(side):
+    kept = torch.empty(side.n, dtype=torch.bool, device=side.boxes.device)
+    kept[side.perm] = side.keep.bool() if side.keep is not None else True
+    return kept
+
+
+def id_overlap_counts(gt, pred, max_dist=0.75, *, min_cameras=2, drop_repeats=True, roi=None, roi_cameras=None,
+                      border=None, image_size=None):
+    """The table behind `idf1`, for inspection: (C, gt_ids, pred_ids, kept_gt, kept_pred) with C int32 [n_obj, n_hyp] on
+    the device, C[o, h] = the frames in which ground-truth identity gt_ids[o] and predicted identity pred_ids[h] have
+    boxes within max_dist, and the two bool row masks in input order."""
+    r = _id_passes(gt, pred, max_dist, min_cameras, drop_repeats, roi, roi_cameras, border, image_size)
+    c = r.ws[:r.n_obj * r.n_hyp * 4].view(torch.int32).view(r.n_obj, r.n_hyp).clone()
+    return c, r.obj_ids, r.hyp_ids, _input_order(r.gt), _input_order(r.pred)
+
+
+def idf1(gt, pred, max_dist=0.75, *, min_cameras=2, drop_repeats=True, roi=None, roi_cameras=None, border=None,
+         image_size=None):
+    """IDF1 / IDP / IDR of a tracking result as the reference scores it (main.py:166-213: the centre band, then
+    eval/eval.py::eval with motmetrics' `compare_to_groundtruth(..., 'iou', max_dist)` and its global ID assignment);
+    the definition is DESIGN.md 3.11.  gt, pred: [n, 7] tensors on one ROCm device in the reference's column order
+    (camera, id, frame, x, y, width, height), int32 / int64 / float32 / float64; columns 0-2 are read as int64, the boxes
+    as fp64.  Ground-truth rows must be unique per (camera, frame, id).  A frame group is one (camera, frame) pair.
+
+    Filters on the predictions, in this order: border=p with image_size=(W, H) (the centre band, applied to the ground
+    truth too; default off), roi= a [C, Hr, Wr] uint8 mask stack with roi_cameras= the camera value of each plane
+    (`isROIOutlier`; default off; a prediction whose camera has no plane is refused), min_cameras (identities seen by
+    fewer cameras go), drop_repeats (the first row of equal (camera, id, frame) stays).
+
+    Returns IdScores(idf1, idp, idr, idtp, idfp, idfn, num_objects, num_predictions, matches, kept): three floats (NaN
+    on 0 / 0), five ints, matches int64 [M, 2] on the device = (ground-truth id, predicted id) of the optimal matching,
+    kept bool [n_pred] on the device in input order.  The overlap counts are made by HIP kernels, the assignment by the
+    library on the host; the host reads the counters, then the non-zero cells."""
+    import ctypes
+    import numpy as np
+    r = _id_passes(gt, pred, max_dist, min_cameras, drop_repeats, roi, roi_cameras, border, image_size)
+    lib, dev = _lib.load(), r.dev
+    n_all = r.n_obj * r.n_hyp
+    cap = min(n_all, max(4096, 4 * (r.n_obj + r.n_hyp)))
+    while True:
+        triples = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+        _call.run(dev, lib.mtmc_id_cells, r.ws.data_ptr(), r.n_obj, r.n_hyp, triples.data_ptr() if cap else None, cap,
+                  r.counters[2:3].data_ptr(), _call.stream(dev))
+        num_objects, num_predictions, n_cells = r.counters.tolist()
+        if n_cells <= cap:
+            break
+        cap = n_cells
+    cells = triples[:n_cells].cpu().numpy()
+    cells = np.ascontiguousarray(cells[np.lexsort((cells[:, 1], cells[:, 0]))])      # (the device lists them in any order)
+    idtp, match = ctypes.c_int64(0), np.full(max(r.n_obj, 1), -1, dtype=np.int32)
+    _lib.check(lib.mtmc_id_assign(cells.ctypes.data if n_cells else None, n_cells, r.n_obj, r.n_hyp, ctypes.addressof(idtp),
+                                  match.ctypes.data, None))
+    idtp = int(idtp.value)
+    o = np.nonzero(match[:r.n_obj] >= 0)[0]
+    matches = torch.stack([r.obj_ids[torch.from_numpy(o).to(dev)],
+                           r.hyp_ids[torch.from_numpy(match[o].astype(np.int64)).to(dev)]], dim=1)
+    idfn, idfp = num_objects - idtp, num_predictions - idtp
+    div = lambda a, b: a / b if b else float("nan")                                  # noqa: E731
+    return IdScores(div(2 * idtp, num_objects + num_predictions), div(idtp, idtp + idfp), div(idtp, idtp + idfn), idtp, idfp,
+                    idfn, num_objects, num_predictions, matches, _input_order(r.pred))

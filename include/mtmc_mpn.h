@@ -27,6 +27,7 @@
  *   mtmc_pool_tracklets        <- per-tracklet mean of the detections' embeddings  train.py:305-316,
  *                                 libs/reid_feature_extraction.py:177-178 (mtmc_pool_tracklets_weighted: rows in any order, a weight per
  *                                 detection, libs/filter_mtmc.py's filters as weights)
+ *   mtmc_id_filter / _overlap / _cells / _assign <- IDF1 / IDP / IDR of a result  main.py:166-213, eval/eval.py::eval
  *
  * All floating tensors are fp32, row-major, contiguous unless a stride argument says otherwise;
  * BatchNorm statistics are accumulated in fp64.  All work is enqueued on `stream` (a hipStream_t
@@ -651,6 +652,55 @@ int32_t mtmc_pool_tracklets_weight_grad(const float* embeds, int64_t row_stride,
                                         const int64_t* offsets, int64_t n_tracklets, const int64_t* perm,
                                         const float* grad_out, const float* out, const float* wsum, float* grad_weights,
                                         void* stream);
+
+/* ---- the score the reference reports: IDF1 / IDP / IDR of a tracking result (main.py:166-213, eval/eval.py::eval) ----
+ * The definition is DESIGN.md 3.11.  Two tables of detections (ground truth, predictions), each already GROUPED by the
+ * caller: rows stably sorted by ((camera, frame) group, identity), with per row
+ *   boxes [n][4] fp64 = x, y, width, height; camera [n] int32 in [0, n_cameras); identity [n] int32 in [0, n_identities);
+ *   group [n] int32, equal for the rows of one (camera, frame)
+ * mtmc_id_filter (both tables; the ground truth takes step 1 only) writes which rows survive, in this order:
+ *   1. border != 0: keep iff x_lo <= x + width / 2 <= x_hi and y_lo <= y + height <= y_hi          (main.py:171-204)
+ *   2. roi != NULL, [n_planes][roi_height][roi_width] uint8, plane_of_camera [n_cameras] int32 (-1: none, no lookup): the
+ *      corners x, x + width, y, y + height in fp64, truncated to int64; a row goes iff a corner column inside [0, roi_width)
+ *      and a corner row inside [0, roi_height) meet a mask value < 255; a corner outside the mask is never looked up
+ *   3. min_cameras > 0: an identity whose rows, after 1-2, come from fewer distinct cameras goes     (removeOutliersSingleCam)
+ *   4. drop_repeats != 0: of the rows of one (group, identity) that are left, the first stays       (removeRepetition)
+ *   stage [n] uint8: after steps 1-2; keep [n] uint8: after all four; cameras [n_identities] uint64: the camera bits of
+ *   step 3; n_kept [1] int64: the rows kept.  All four in device memory, written by the call (one memset, two launches).
+ * mtmc_id_overlap: C[o][h] = the number of (ground-truth row, prediction row) pairs of one group, both kept (gt_keep may be
+ *   NULL: all), with identities o and h, whose boxes have 1 - I / U <= max_dist, I = iw ih, U = aw ah + bw bh - I in fp64
+ *   without fused multiply-adds (U = 0: NaN, does not count).  gt_offsets / pred_offsets [n_groups + 1] int64 in device
+ *   memory cut the two tables over the UNION of their group keys (either side of a group may be empty).  C is int32
+ *   [n_obj][n_hyp] at the start of the workspace, cleared by the call; integer atomic adds, the same bits on every run.
+ *   Lanes walk the linearised pair index (a prefix sum over the groups, kept in the workspace), so there is no limit on a
+ *   group's size and no loop over groups on the host.  Every offset and identity is checked against its array before use.
+ * mtmc_id_cells: the non-zero cells of C as (o, h, count) int32 triples in no particular order, at most max_cells of them
+ *   written; n_cells [1] int64 in device memory gets their number (which may exceed max_cells: call again).
+ * The three run on `stream`, allocate nothing and synchronise nothing.  MTMC_E_ARG (with text): n_obj * n_hyp above
+ * MTMC_ID_MAX_CELLS, more than MTMC_ID_MAX_CAMERAS cameras, a row count >= 2^31, a NULL pointer, a workspace short of
+ * mtmc_id_overlap_workspace_bytes (host-only; 0 for sizes that are refused).  Zero rows on either side are legal.
+ * mtmc_id_assign is HOST-ONLY and touches no GPU: cells [n_cells][3] int32 in host memory (count 0 is ignored) ->
+ *   idtp = the largest sum of C over one-to-one partial matchings of objects and hypotheses, match_of_obj [n_obj] = the
+ *   hypothesis of each object in one such matching (-1: none; only pairs with C > 0 are reported).  The support graph of
+ *   C is split into connected components (union-find) and each is solved exactly by shortest augmenting paths in integer
+ *   arithmetic, O(n^3) of the component.  stats [3] (may be NULL): components, then the rows and columns of the component
+ *   with the largest rows x columns (ties: more rows). */
+#define MTMC_ID_MAX_CELLS 67108864
+#define MTMC_ID_MAX_CAMERAS 64
+int32_t mtmc_id_filter(const double* boxes, const int32_t* camera, const int32_t* identity, const int32_t* group, int64_t n_rows,
+                       int64_t n_identities, int32_t n_cameras, int32_t border, double x_lo, double x_hi, double y_lo,
+                       double y_hi, const uint8_t* roi, const int32_t* plane_of_camera, int32_t n_planes, int32_t roi_height,
+                       int32_t roi_width, int32_t min_cameras, int32_t drop_repeats, uint8_t* stage, uint8_t* keep,
+                       uint64_t* cameras, int64_t* n_kept, void* stream);
+size_t mtmc_id_overlap_workspace_bytes(int64_t n_obj, int64_t n_hyp, int64_t n_groups);
+int32_t mtmc_id_overlap(const double* gt_boxes, const int64_t* gt_offsets, const int32_t* gt_identity, const uint8_t* gt_keep,
+                        int64_t n_gt, const double* pred_boxes, const int64_t* pred_offsets, const int32_t* pred_identity,
+                        const uint8_t* pred_keep, int64_t n_pred, int64_t n_groups, int64_t n_obj, int64_t n_hyp,
+                        double max_dist, void* workspace, size_t workspace_bytes, void* stream);
+int32_t mtmc_id_cells(const void* workspace, int64_t n_obj, int64_t n_hyp, int32_t* cells, int64_t max_cells, int64_t* n_cells,
+                      void* stream);
+int32_t mtmc_id_assign(const int32_t* cells, int64_t n_cells, int64_t n_obj, int64_t n_hyp, int64_t* idtp, int32_t* match_of_obj,
+                       int64_t* stats);
 
 #ifdef __cplusplus
 }
