@@ -12,6 +12,7 @@ from .graph_build import build_graph  # noqa: F401
 from .postprocess import postprocess  # noqa: F401
 from . import pool  # noqa: F401
 from .pool import pool_tracklets  # noqa: F401
+from .grouping import Grouping, group_by_index  # noqa: F401
 from . import ops  # noqa: F401
 from .ops import FocalLoss, cross_entropy, cross_entropy_steps, edge_loss, focal_loss  # noqa: F401
 from . import metrics  # noqa: F401
@@ -24,4 +25,5 @@ from .modules import (MLP, EdgeModel, MetaLayer, MLPGraphIndependent, MOTMPNet, 
 __all__ = ["MOTMPNet", "MetaLayer", "EdgeModel", "NodeModel", "MLPGraphIndependent", "MLP",
            "DEFAULT_GRAPH_NET_PARAMS", "DEFAULT_ARCH", "default_params", "build_graph", "postprocess", "FeatureStore", "cross_entropy", "cross_entropy_steps", "edge_loss", "ops",
            "metrics", "cluster_scores", "edge_prf", "evaluate", "ClusterScores", "EdgePRF", "pool", "pool_tracklets",
-           "focal_loss", "FocalLoss", "idf1", "relabel_detections", "IdScores"]
+           "focal_loss", "FocalLoss", "idf1", "relabel_detections", "IdScores",
+           "Grouping", "group_by_index"]

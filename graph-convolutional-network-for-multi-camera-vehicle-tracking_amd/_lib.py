@@ -117,6 +117,8 @@ SIGNATURES = {
     "mtmc_scatter_add_backward": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "mtmc_scatter_mean_backward": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "mtmc_scatter_max_backward": (_i32, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "mtmc_scatter_grouped_workspace_bytes": (_sz, [_i64, _i64]),
+    "mtmc_scatter_grouped": (_i32, [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _p, _sz, _p]),
     "mtmc_mlp_layer_forward": (_i32, [_Layer, _p, _i64, _i64, _p, _p, _p]),
     "mtmc_linear_raw": (_i32, [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
     "mtmc_linear_few_raw": (_i32, [_p, _i64, _p, _p, _p, _f64, _p, _p, _p, _i64, _i32, _i32, _p, _u64, _p, _p]),
@@ -155,6 +157,9 @@ SIGNATURES = {
     "mtmc_pool_tracklets_weighted": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "mtmc_pool_tracklets_weighted_backward": (_i32, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
     "mtmc_pool_tracklets_weight_grad": (_i32, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "mtmc_group_tile_rows": (_i32, []),
+    "mtmc_group_by_index_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mtmc_group_by_index": (_i32, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
     "mtmc_id_filter": (_i32, [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _p, _p, _i32, _i32, _i32, _i32, _i32,
                               _p, _p, _p, _p, _p]),
     "mtmc_id_overlap_workspace_bytes": (_sz, [_i64, _i64, _i64]),

@@ -5,6 +5,8 @@
 //   add : out zero-filled, out[index[e], c] += src[e, c]
 //   mean: add, then divide by max(count, 1)
 //   max : per-column maximum, rows nobody writes stay 0, argmax = smallest e attaining it (E if none)
+// These three add with atomics: the last bits of a float sum change from run to run.  mtmc_scatter_grouped, further down, is the
+// repeatable forward of the same three: a segmented reduction over a stable grouping of the rows (group_index.hip).
 #include "api_error.h"
 #include "kernels.h"
 #include <limits.h>
@@ -261,6 +263,248 @@ static void launch_scatter_backward(const float* g, const int64_t* arg, const in
 #undef MTMC_SCATTER_BWD
 }
 
+// ---- the repeatable forward: a segmented reduction over a grouping (group_index.hip) ----
+// perm [E] lists the source rows group by group, offsets [N + 1] cut its POSITIONS: out[g] reduces the rows perm[j],
+// offsets[g] <= j < offsets[g + 1].  No fill, no float atomic, no count buffer: every output element has one writer and every
+// sum ONE ORDER, fixed by (E, C, offsets) alone:
+//   * the positions are cut into chunks of kSegR = 64; one wave per chunk (and per slab of 64 lanes' columns);
+//   * a lane holds W columns (4 when C % 4 == 0, else 1) of one row: U = C / W lanes cover a row, rounded up to a power of two
+//     U' <= 64, so a wave covers P = 64 / U' rows at a time (C = 4: 64 rows, C = 32: 8 rows; C > 256 or 64: one row, in
+//     slabs).  The same lanes hold the same columns whether the loads are 16-byte ones or, on unaligned pointers, four
+//     scalar ones: the alignment changes the instructions, not the order;
+//   * the piece [lo, hi) of a group inside a chunk: sub-row q = lane / U' adds positions lo + q, lo + q + P, ... in that order,
+//     starting from -0.0 (x + -0.0 = x for every x, so a group of one row is a copy of that row), then the P sub-rows fold in
+//     a butterfly, partner q ^ (P / 2) first and q ^ 1 last;
+//   * a group inside one chunk is finished there; a group that crosses chunks leaves a partial per chunk (slot 1, "tail", in
+//     its first chunk, slot 0, "head", in the others), and scatter_seg_finish_kernel, one wave per (group, slab), folds the
+//     list tail, head, head, ... in chunk order by the same rule (sub-row q takes items q, q + P, ...; then the butterfly).
+//   mean divides the sum by (float)max(offsets[g + 1] - offsets[g], 1); max compares float_key and keeps the smallest source
+//   row of the maximum, which is order-free.  A perm entry outside [0, E) names no row.  Offsets are clamped into [0, E] before
+//   they index anything.  (A crossing group all of whose entries name no row sums to -0.0.)
+constexpr int kSegR = 64;
+
+__device__ __forceinline__ int64_t seg_clamp(int64_t v, int64_t E) { return v < 0 ? 0 : (v > E ? E : v); }
+// the largest s in [0, N-1] with offsets[s] <= r (0 if none), as pool_find of pool_tracklets.hip
+__device__ __forceinline__ int64_t seg_find(const int64_t* offsets, int64_t N, int64_t E, int64_t r) {
+  int64_t lo = 0, hi = N - 1;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo + 1) / 2;
+    if (seg_clamp(offsets[mid], E) <= r) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// what a lane carries: W sums, or W (key, source row) pairs
+template <int W, bool MAX> struct SegAcc {
+  float v[W];
+  int key[W], arg[W];
+  __device__ __forceinline__ void clear(int none) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) { v[k] = -0.f; key[k] = INT_MIN; arg[k] = none; }
+  }
+  __device__ __forceinline__ void take(int k, int okey, int oarg) {
+    if (okey > key[k] || (okey == key[k] && oarg < arg[k])) { key[k] = okey; arg[k] = oarg; }
+  }
+  __device__ __forceinline__ void fold(int up) {           // the butterfly over the sub-rows: every lane ends with the result
+    for (int m = 32; m >= up; m >>= 1) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        if (MAX) take(k, __shfl_xor(key[k], m, 64), __shfl_xor(arg[k], m, 64));
+        else v[k] += __shfl_xor(v[k], m, 64);
+      }
+    }
+  }
+};
+
+template <int W, bool AL> __device__ __forceinline__ void seg_load(const float* p, float* v) {
+  if (W == 4 && AL) {
+    const sc_f4 t = *reinterpret_cast<const sc_f4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = p[k];
+  }
+}
+template <int W, bool AL> __device__ __forceinline__ void seg_store(float* p, const float* v) {
+  if (W == 4 && AL) {
+    *reinterpret_cast<sc_f4*>(p) = sc_f4{v[0], v[1], v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) p[k] = v[k];
+  }
+}
+
+struct SegArgs {
+  const float* src;
+  const int64_t *perm, *offsets;
+  int64_t E, C, N;
+  int lg_up, slabs, mean;
+  float *out, *partial;
+  int64_t *arg_out, *parg;
+};
+
+// which (item, columns, sub-row) this lane works on; false: the wave has no item
+struct SegLane { int64_t item, col; int q; bool live; };
+template <int W> __device__ __forceinline__ bool seg_lane(const SegArgs& a, int64_t items, SegLane* l) {
+  const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  l->item = w / a.slabs;
+  const int64_t unit = (w - l->item * a.slabs) * 64 + (lane & ((1 << a.lg_up) - 1));
+  l->q = lane >> a.lg_up;
+  l->live = unit < a.C / W;
+  l->col = l->live ? unit * W : 0;
+  return l->item < items;
+}
+
+// the finished row of group s, by the lanes of sub-row 0
+template <int W, bool MAX, bool AL>
+__device__ __forceinline__ void seg_finish_row(const SegArgs& a, const SegLane& l, int64_t s, int64_t count, SegAcc<W, MAX>& acc) {
+  if (l.q != 0 || !l.live) return;
+  float v[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    if (MAX) v[k] = acc.key[k] == INT_MIN ? 0.f : key_float(acc.key[k]);
+    else v[k] = a.mean ? acc.v[k] / (float)(count < 1 ? 1 : count) : acc.v[k];
+  }
+  seg_store<W, AL>(a.out + s * a.C + l.col, v);
+  if (MAX && a.arg_out) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) a.arg_out[s * a.C + l.col + k] = acc.arg[k];
+  }
+}
+
+template <int W, bool MAX, bool AL>
+__global__ __launch_bounds__(256) void scatter_seg_chunks_kernel(SegArgs a) {
+  SegLane l;
+  if (!seg_lane<W>(a, (a.E + kSegR - 1) / kSegR, &l)) return;
+  const int up = 1 << a.lg_up, P = 64 >> a.lg_up, lane = threadIdx.x & 63;
+  const int64_t c = l.item, r0 = c * kSegR, r1 = r0 + kSegR < a.E ? r0 + kSegR : a.E;
+  int row = -1;                                            // of position r0 + lane; -1: names no row
+  if (r0 + lane < r1) {
+    const int64_t p = a.perm[r0 + lane];
+    if (p >= 0 && p < a.E) row = (int)p;                   // E < 2^31
+  }
+  int64_t cur = r0;
+  for (int64_t s = seg_find(a.offsets, a.N, a.E, r0); s < a.N && cur < r1;) {
+    const int64_t ga = seg_clamp(a.offsets[s], a.E), gb = seg_clamp(a.offsets[s + 1], a.E);
+    if (gb <= cur) { ++s; continue; }                      // empty, inverted or behind us: the finish kernel's
+    const int64_t lo = ga > cur ? ga : cur, hi = gb < r1 ? gb : r1;
+    if (lo >= r1) break;
+    SegAcc<W, MAX> acc;
+    acc.clear((int)a.E);
+    const int end = (int)(hi - r0);
+    bool any = false;
+    for (int base = (int)(lo - r0); base < end; base += 2 * P) {      // (the same trips in every lane: all 64 shuffle)
+      int rr[2];
+      bool ok[2];
+      float v[2][W];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int at = base + t * P + l.q;
+        rr[t] = __shfl(row, at & 63, 64);
+        ok[t] = at < end && rr[t] >= 0;
+        any |= __ballot(ok[t]) != 0;
+        ok[t] = ok[t] && l.live;
+        if (ok[t]) seg_load<W, AL>(a.src + (int64_t)rr[t] * a.C + l.col, v[t]);
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (!ok[t]) continue;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          if (MAX) acc.take(k, float_key(v[t][k]), rr[t]); else acc.v[k] += v[t][k];
+        }
+      }
+    }
+    acc.fold(up);
+    if (ga >= r0 && gb <= r1) {
+      if (!any) {                                          // no entry named a row: the row nobody writes
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc.v[k] = 0.f;
+      }
+      seg_finish_row<W, MAX, AL>(a, l, s, gb - ga, acc);
+    } else if (l.q == 0 && l.live) {
+      const int64_t at = (c * 2 + (ga < r0 ? 0 : 1)) * a.C + l.col;
+      if (MAX) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          a.partial[at + k] = __int_as_float(acc.key[k]);
+          a.parg[at + k] = acc.arg[k];
+        }
+      } else {
+        seg_store<W, AL>(a.partial + at, acc.v);
+      }
+    }
+    cur = hi;
+    if (gb > r1) break;
+    ++s;
+  }
+}
+
+template <int W, bool MAX, bool AL>
+__global__ __launch_bounds__(256) void scatter_seg_finish_kernel(SegArgs a) {
+  SegLane l;
+  if (!seg_lane<W>(a, a.N, &l)) return;
+  const int up = 1 << a.lg_up, P = 64 >> a.lg_up;
+  const int64_t s = l.item, ga = seg_clamp(a.offsets[s], a.E), gb = seg_clamp(a.offsets[s + 1], a.E);
+  SegAcc<W, MAX> acc;
+  acc.clear((int)a.E);
+  if (gb <= ga) {                                          // nobody writes this row: 0, argmax E
+#pragma unroll
+    for (int k = 0; k < W; ++k) acc.v[k] = 0.f;
+    seg_finish_row<W, MAX, AL>(a, l, s, 1, acc);
+    return;
+  }
+  const int64_t c0 = ga / kSegR, c1 = (gb - 1) / kSegR;
+  if (c0 == c1) return;                                    // finished inside its chunk
+  const int64_t items = c1 - c0 + 1;                       // the tail of chunk c0, then the heads of c0 + 1 .. c1
+  for (int64_t i = l.q; i < items && l.live; i += P) {
+    const int64_t at = (i == 0 ? c0 * 2 + 1 : (c0 + i) * 2) * a.C + l.col;
+    float v[W];
+    seg_load<W, AL>(a.partial + at, v);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      if (MAX) acc.take(k, __float_as_int(v[k]), (int)a.parg[at + k]); else acc.v[k] += v[k];
+    }
+  }
+  acc.fold(up);
+  seg_finish_row<W, MAX, AL>(a, l, s, gb - ga, acc);
+}
+
+static inline int64_t seg_chunks(int64_t n_src) { return (n_src + kSegR - 1) / kSegR; }
+static inline size_t seg_parg_offset(int64_t n_src, int64_t n_cols) {
+  return ((size_t)seg_chunks(n_src) * 2 * (size_t)n_cols * sizeof(float) + 255) / 256 * 256;
+}
+static inline bool seg_sizes_ok(int64_t n_src, int64_t n_cols) {
+  return n_src >= 0 && n_src < (1ll << 31) && n_cols >= 1 && n_cols < (1ll << 31);
+}
+static inline size_t seg_bytes(int64_t n_src, int64_t n_cols) {
+  return seg_parg_offset(n_src, n_cols) + (size_t)seg_chunks(n_src) * 2 * (size_t)n_cols * sizeof(int64_t) + 256;
+}
+
+template <int W, bool MAX, bool AL> static void launch_scatter_seg_as(const SegArgs& a, hipStream_t s) {
+  if (a.E > 0)
+    hipLaunchKernelGGL((scatter_seg_chunks_kernel<W, MAX, AL>), dim3(blocks_for(seg_chunks(a.E) * a.slabs, 4, INT_MAX)), dim3(256),
+                       0, s, a);
+  hipLaunchKernelGGL((scatter_seg_finish_kernel<W, MAX, AL>), dim3(blocks_for(a.N * a.slabs, 4, INT_MAX)), dim3(256), 0, s, a);
+}
+
+// mode 0 add, 1 mean, 2 max; dim_size >= 1
+static void launch_scatter_seg(SegArgs a, int mode, hipStream_t s) {
+  const bool four = a.C % 4 == 0;
+  const bool al = four && !(((uintptr_t)a.src | (uintptr_t)a.out | (uintptr_t)a.partial) & 15);
+  const int64_t units = four ? a.C / 4 : a.C;
+  a.lg_up = 0;
+  while (a.lg_up < 6 && (1ll << a.lg_up) < units) ++a.lg_up;
+  a.slabs = (int)((units + 63) / 64);
+  a.mean = mode == 1;
+#define MTMC_SCATTER_SEG(MAX)                                                                                           \
+  (!four ? launch_scatter_seg_as<1, MAX, false>(a, s)                                                                   \
+         : al ? launch_scatter_seg_as<4, MAX, true>(a, s) : launch_scatter_seg_as<4, MAX, false>(a, s))
+  if (mode == 2) MTMC_SCATTER_SEG(true); else MTMC_SCATTER_SEG(false);
+#undef MTMC_SCATTER_SEG
+}
+
 }  // namespace mtmc
 
 extern "C" {
@@ -296,6 +540,34 @@ int32_t mtmc_scatter_mean(const float* src, const int64_t* index, int64_t n_src,
 int32_t mtmc_scatter_max(const float* src, const int64_t* index, int64_t n_src, int64_t n_cols, int64_t dim_size,
                          float* out, int64_t* arg_out, void* stream) {
   return scatter_common("scatter_max", src, index, n_src, n_cols, dim_size, out, nullptr, arg_out, 2, stream);
+}
+
+size_t mtmc_scatter_grouped_workspace_bytes(int64_t n_src, int64_t n_cols) {
+  return mtmc::seg_sizes_ok(n_src, n_cols) ? mtmc::seg_bytes(n_src, n_cols) : 0;
+}
+
+int32_t mtmc_scatter_grouped(const float* src, int64_t n_src, int64_t n_cols, const int64_t* perm, const int64_t* offsets,
+                             int64_t dim_size, int32_t mode, float* out, int64_t* arg_out, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if (!mtmc::seg_sizes_ok(n_src, n_cols) || dim_size < 0 || dim_size >= (1ll << 31) || mode < 0 || mode > 2)
+    return fail(MTMC_E_ARG, "scatter_grouped: n_src and dim_size must be in [0, 2^31), n_cols in [1, 2^31), mode 0 (add), 1 (mean) or 2 (max)");
+  if (dim_size == 0) return MTMC_OK;
+  if (!out || !offsets || (n_src > 0 && (!src || !perm)))
+    return fail(MTMC_E_ARG, "scatter_grouped: out and offsets (with rows: src and perm) must not be NULL");
+  if ((((uintptr_t)src | (uintptr_t)out) & 3) || (((uintptr_t)perm | (uintptr_t)offsets | (uintptr_t)arg_out) & 7))
+    return fail(MTMC_E_ARG, "scatter_grouped: src and out must be 4-byte, perm, offsets and arg_out 8-byte aligned");
+  const size_t need = mtmc::seg_bytes(n_src, n_cols);
+  if (n_src > 0 && (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need))
+    return fail(MTMC_E_ARG, "scatter_grouped: workspace (16-byte aligned) has %zu bytes, %zu needed (mtmc_scatter_grouped_workspace_bytes)",
+                workspace_bytes, need);
+  mtmc::SegArgs a = {};
+  a.src = src; a.perm = perm; a.offsets = offsets;
+  a.E = n_src; a.C = n_cols; a.N = dim_size;
+  a.out = out; a.arg_out = arg_out;
+  a.partial = static_cast<float*>(workspace);
+  a.parg = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + mtmc::seg_parg_offset(n_src, n_cols));
+  mtmc::launch_scatter_seg(a, mode, static_cast<hipStream_t>(stream));
+  return launched("scatter_grouped");
 }
 
 static int scatter_backward_common(const char* entry, const float* grad_out, const int64_t* arg, const int64_t* index,

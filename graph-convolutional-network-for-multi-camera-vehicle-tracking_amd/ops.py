@@ -2,7 +2,8 @@
 
   scatter_add / scatter_mean / scatter_max   the call forms of the third-party `torch_scatter` op the
       reference aggregates with (`scatter_*(src, index, dim=0, dim_size=N)`, reference models/mpn.py:196-202);
-      differentiable (once) with respect to a floating `src`, like the op they stand in for
+      differentiable (once) with respect to a floating `src`, like the op they stand in for; `deterministic=True` or a
+      `Grouping` makes the forward a segmented reduction in one fixed order instead of float atomics
   mlp_forward                                `MLP.forward` (reference models/mlp.py:32-33), eval mode
   cross_entropy                              `F.cross_entropy(input, target, weight, reduction=...)` on the [E, C<=4]
       edge logits, forward and backward fused (the training callers' loss, reference train.py:88-93, :109-142)
@@ -25,36 +26,70 @@ import torch
 
 from . import _call, _lib
 from . import torch_ops  # noqa: F401  (registers torch.ops.mtmc_mpn.*)
+from .grouping import Grouping, group_by_index
 
 
-def _scatter(name, src, index, dim, out, dim_size):
+def _scatter(name, src, index, dim, out, dim_size, deterministic=False):
     if out is not None:
         raise NotImplementedError(f"mtmc_mpn.{name}: `out=` is not supported")
+    if deterministic is False or deterministic is None:
+        _call.require_gpu(name, src, index)
+        return getattr(torch.ops.mtmc_mpn, name)(src, index, dim, dim_size)
+    # the repeatable forward: a segmented reduction over a stable grouping of the rows (csrc/group_index.hip)
+    g = deterministic if isinstance(deterministic, Grouping) else None
+    if g is None and deterministic is not True:
+        raise TypeError(f"mtmc_mpn.{name}: deterministic must be False, True or a Grouping (mtmc_mpn.group_by_index)")
+    if g is None and dim_size is None:
+        raise ValueError(f"mtmc_mpn.{name}: deterministic=True needs dim_size: without it the size of the result is found "
+                         "with a host read of index.max(), which the repeatable forward never does (it synchronises and "
+                         "cannot be captured)")
+    if g is not None and dim_size is not None and int(dim_size) != g.num_groups:
+        raise ValueError(f"mtmc_mpn.{name}: dim_size is {int(dim_size)}, the Grouping has {g.num_groups} groups")
+    if g is not None and index is None:
+        index = g.index
     _call.require_gpu(name, src, index)
-    return getattr(torch.ops.mtmc_mpn, name)(src, index, dim, dim_size)
+    if dim not in (0, -max(src.dim(), 1)):
+        raise NotImplementedError("mtmc_mpn.scatter_*: only dim=0 (the reference's call form) is implemented")
+    if index.dim() != 1 or src.dim() < 1 or index.shape[0] != src.shape[0]:
+        raise RuntimeError("mtmc_mpn.scatter_*: index must be 1-D with one entry per row of src")
+    if not src.dtype.is_floating_point:                # exact int64 sums: no order to fix
+        return getattr(torch.ops.mtmc_mpn, name)(src, index, dim, g.num_groups if g is not None else dim_size)
+    if g is None:
+        g = group_by_index(index, dim_size)
+    elif g.index.device != src.device or g.perm.shape[0] != src.shape[0]:
+        raise RuntimeError(f"mtmc_mpn.{name}: the Grouping must group the rows of src, on its device")
+    return getattr(torch.ops.mtmc_mpn, name + "_grouped")(src, g.index, g.perm, g.offsets)
 
 
-def scatter_add(src, index, dim=0, out=None, dim_size=None):
+def scatter_add(src, index, dim=0, out=None, dim_size=None, deterministic=False):
     """`torch_scatter.scatter_add(src, index, dim=0, dim_size=N)`; integer `src` (the 1-D int64 form of reference
     utils.py:173-174) is summed exactly and keeps its dtype.  Differentiable with respect to a floating `src`:
-    d_src[e] = grad[index[e]], zeros for a row whose index lies outside [0, N)."""
-    return _scatter("scatter_add", src, index, dim, out, dim_size)
+    d_src[e] = grad[index[e]], zeros for a row whose index lies outside [0, N).
+
+    deterministic=False adds with float atomics: the last bits of a sum change from run to run.  deterministic=True groups
+    the rows on the device (`mtmc_mpn.group_by_index`) and reduces group by group in one fixed order: the same bits on
+    every run, no fill launch and no float atomic; `dim_size` is then required, nothing is read back, and forward and
+    backward are legal inside `torch.cuda.graph`.  deterministic=G, a `Grouping` made beforehand from the same index,
+    skips the grouping (`index` may then be `G.index` or None): group once, scatter every round and every step.  The
+    gradients are those of the default call, bit for bit."""
+    return _scatter("scatter_add", src, index, dim, out, dim_size, deterministic)
 
 
 scatter_sum = scatter_add
 
 
-def scatter_mean(src, index, dim=0, out=None, dim_size=None):
+def scatter_mean(src, index, dim=0, out=None, dim_size=None, deterministic=False):
     """`torch_scatter.scatter_mean(src, index, dim=0, dim_size=N)`: the sum divided by max(count, 1).  Differentiable with
-    respect to `src`: d_src[e] = grad[index[e]] / max(count[index[e]], 1)."""
-    return _scatter("scatter_mean", src, index, dim, out, dim_size)
+    respect to `src`: d_src[e] = grad[index[e]] / max(count[index[e]], 1).  `deterministic`: as in `scatter_add`."""
+    return _scatter("scatter_mean", src, index, dim, out, dim_size, deterministic)
 
 
-def scatter_max(src, index, dim=0, out=None, dim_size=None):
+def scatter_max(src, index, dim=0, out=None, dim_size=None, deterministic=False):
     """Returns (values, argmax) like torch_scatter; rows nobody writes hold 0 and argmax = src.size(0).  `values` is
     differentiable with respect to `src`: the gradient of values[r, c] goes to row argmax[r, c], the first row that attains
-    the maximum, and to no other; the argmax carries none."""
-    return _scatter("scatter_max", src, index, dim, out, dim_size)
+    the maximum, and to no other; the argmax carries none.  `deterministic`: as in `scatter_add` (a maximum has the same
+    bits either way; the grouped form needs no fill and no atomic)."""
+    return _scatter("scatter_max", src, index, dim, out, dim_size, deterministic)
 
 
 def layer_forward(a: torch.Tensor, weight, bias, gamma=None, beta=None) -> torch.Tensor:

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _call, _lib
+from .grouping import Grouping
 
 CHUNK_ROWS = 32          # mtmc_pool_chunk_rows(): rows per chunk of the kernels' decomposition
 MAX_FEAT_DIM = 16384
@@ -106,12 +107,12 @@ def group_by_index(index: torch.Tensor, num_tracklets: int):
     detection) -> (perm [D], offsets [num_tracklets + 1]), both int64 on that device.  perm lists the detection rows
     tracklet by tracklet, each tracklet's rows in increasing row order (a stable sort of D keys); tracklet s owns
     perm[offsets[s]:offsets[s+1]].  Detections whose index lies outside [0, num_tracklets) sort behind offsets[-1] and
-    belong to no tracklet.  Plumbing in PyTorch on the device (sort, searchsorted): nothing is read back."""
-    n = int(num_tracklets)
-    key = torch.where((index >= 0) & (index < n), index, torch.full_like(index, n))
-    key, perm = torch.sort(key, stable=True)
-    offsets = torch.searchsorted(key, torch.arange(n + 1, dtype=torch.int64, device=index.device))
-    return perm, offsets
+    belong to no tracklet.  One library call (`mtmc_group_by_index`: a radix sort in HIP, csrc/group_index.hip): nothing is
+    read back or synchronised, and the call can be captured.  `mtmc_mpn.group_by_index` returns the same two tensors as a
+    `Grouping`, for `pool_tracklets(grouping=)`."""
+    from . import torch_ops  # noqa: F401  (registers torch.ops.mtmc_mpn.group_by_index)
+    _call.require_gpu("group_by_index", index)
+    return torch.ops.mtmc_mpn.group_by_index(index.contiguous(), int(num_tracklets))
 
 
 def _forward_weighted_raw(embeds, offsets_dev, perm=None, weights=None, out=None, info=None, wsum=None):
@@ -239,7 +240,7 @@ def _raise_on(info: torch.Tensor, by_index: bool):
 
 
 def pool_tracklets(embeds: torch.Tensor, lengths=None, *, offsets=None, index=None, num_tracklets=None, weights=None,
-                   check: bool = True) -> torch.Tensor:
+                   check: bool = True, grouping=None) -> torch.Tensor:
     """embeds: [D, F] float32 on a ROCm GPU, the detections' embeddings.  Returns the [N, F] float32 per-tracklet means
     (contiguous).  Give exactly one of
 
@@ -251,7 +252,9 @@ def pool_tracklets(embeds: torch.Tensor, lengths=None, *, offsets=None, index=No
              rows of a tracklet are added in increasing row order (`group_by_index`: a stable sort on the device), so the
              result has the same bits on every run and the bits of the grouped call on the same rows.  A tracklet no
              detection names gets a zero row.  A detection whose index is outside [0, N) belongs to no tracklet: it adds
-             nothing and its gradient row is zero (check=True raises RuntimeError about `index`).
+             nothing and its gradient row is zero (check=True raises RuntimeError about `index`);
+    grouping a `Grouping` of the D detections made beforehand (`mtmc_mpn.group_by_index(index, N)`): the `index` form
+             without its grouping step, with the same bits.  Group once, pool many times.
 
     weights  optional float32 [D] tensor on that device (any stride), one weight per detection ROW, finite and >= 0:
              out[s] = sum_r w_r x_r / sum_r w_r.  A weight of 0 removes a detection without repacking `embeds`; a
@@ -260,14 +263,14 @@ def pool_tracklets(embeds: torch.Tensor, lengths=None, *, offsets=None, index=No
 
     check=True reads the kernels' four status words with one small D2H copy and raises RuntimeError on bad offsets,
     index or weights (with `lengths` and no weights there is nothing to read).  check=False never synchronises, so the
-    `offsets` forms, weighted or not, are legal inside `torch.cuda.graph`; the `index` form makes no host read either,
-    but its grouping runs torch's sort, which allocates and is not known to be capturable on every torch build.
+    `offsets`, `index` and `grouping` forms, weighted or not, are legal inside `torch.cuda.graph` (the grouping of `index`
+    is three to four kernel launches of this library on the current stream).
 
     With grad mode on the result carries the gradient back to `embeds` (d_embeds[r] = w_r g[s] / W_s) and, when
     `weights.requires_grad`, to the weights (d_w[r] = g[s] . (x_r - out[s]) / W_s; `embeds` and the result are kept for
     the backward only then).  Once differentiable."""
-    if sum(v is not None for v in (lengths, offsets, index)) != 1:
-        raise ValueError("mtmc_mpn.pool_tracklets: give exactly one of lengths, offsets and index")
+    if sum(v is not None for v in (lengths, offsets, index, grouping)) != 1:
+        raise ValueError("mtmc_mpn.pool_tracklets: give exactly one of lengths, offsets, index and grouping")
     if (index is None) != (num_tracklets is None):
         raise ValueError("mtmc_mpn.pool_tracklets: num_tracklets goes with index (a host int), and only with it")
     _call.require_gpu("pool_tracklets", embeds)
@@ -284,6 +287,10 @@ def pool_tracklets(embeds: torch.Tensor, lengths=None, *, offsets=None, index=No
                 offsets.dim() == 1 and offsets.numel() >= 1):
             raise RuntimeError("mtmc_mpn.pool_tracklets: offsets must be an int64 [N+1] tensor on the device of embeds")
         offsets_dev = offsets.contiguous()
+    elif grouping is not None:
+        if not (isinstance(grouping, Grouping) and grouping.perm.device == dev and tuple(grouping.perm.shape) == (d,)):
+            raise RuntimeError("mtmc_mpn.pool_tracklets: grouping must be a Grouping of the D rows of embeds, on its device")
+        perm, offsets_dev = grouping.perm, grouping.offsets
     else:
         if not (isinstance(index, torch.Tensor) and index.device == dev and index.dtype == torch.int64 and
                 tuple(index.shape) == (d,)):

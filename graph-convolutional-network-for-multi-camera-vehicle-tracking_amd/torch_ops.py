@@ -19,6 +19,10 @@ through `torch.ops.mtmc_mpn.mp_backward`.  CUDA (= ROCm) dispatch key only: CPU 
       floating `src` through
   scatter_add_backward / scatter_mean_backward(grad, index, n_src), scatter_max_backward(grad, arg, index, n_src)
       -> d_src [n_src, ...] float32: gathers of grad [dim_size, ...] by index (csrc/scatter_ops.hip), bitwise repeatable
+  group_by_index(index, num_groups) -> (perm, offsets)        a stable grouping of int64 keys (csrc/group_index.hip)
+  scatter_add_grouped / scatter_mean_grouped / scatter_max_grouped(src, index, perm, offsets)   the same three scatters as a
+      segmented reduction over such a grouping (`ops.scatter_*(..., deterministic=)`): bitwise repeatable forwards, the
+      gradients through the three backward ops above
 """
 from __future__ import annotations
 
@@ -470,3 +474,99 @@ torch.library.register_autograd("mtmc_mpn::scatter_mean", _scatter_autograd(torc
                                 setup_context=_scatter_setup_context)
 torch.library.register_autograd("mtmc_mpn::scatter_max", _scatter_autograd(torch.ops.mtmc_mpn.scatter_max_backward),
                                 setup_context=_scatter_setup_context)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the stable grouping (csrc/group_index.hip) and the repeatable scatter forwards over it (mtmc_scatter_grouped)
+# ---------------------------------------------------------------------------------------------------------------
+torch.library.define("mtmc_mpn::group_by_index", "(Tensor index, int num_groups) -> (Tensor, Tensor)")
+torch.library.define("mtmc_mpn::scatter_add_grouped", "(Tensor src, Tensor index, Tensor perm, Tensor offsets) -> Tensor")
+torch.library.define("mtmc_mpn::scatter_mean_grouped", "(Tensor src, Tensor index, Tensor perm, Tensor offsets) -> Tensor")
+torch.library.define("mtmc_mpn::scatter_max_grouped",
+                     "(Tensor src, Tensor index, Tensor perm, Tensor offsets) -> (Tensor, Tensor)")
+
+
+@torch.library.impl("mtmc_mpn::group_by_index", "CUDA")
+def _group_by_index(index, num_groups):
+    from . import grouping
+    if index.dim() != 1 or index.dtype != torch.int64:
+        raise RuntimeError("mtmc_mpn.group_by_index: index must be a 1-D int64 tensor")
+    return grouping.group_raw(index.contiguous(), grouping.check_num_groups("group_by_index", num_groups))
+
+
+@torch.library.register_fake("mtmc_mpn::group_by_index")
+def _group_by_index_fake(index, num_groups):
+    return index.new_empty(index.shape, dtype=torch.int64), index.new_empty((num_groups + 1,), dtype=torch.int64)
+
+
+def _scatter_grouped(name, mode, src, index, perm, offsets):
+    """One call of mtmc_scatter_grouped: (values, argmax or None), in the shape the atomics op of that name returns."""
+    _call.require_gpu(name, src, index, perm, offsets)
+    e = src.shape[0] if src.dim() else -1
+    if not src.dtype.is_floating_point or any(t.dtype != torch.int64 or t.dim() != 1 for t in (index, perm, offsets)) or \
+            index.shape[0] != e or perm.shape[0] != e or offsets.shape[0] < 1:
+        raise RuntimeError(f"mtmc_mpn.{name}: src must be a floating [E, ...] tensor, index and perm int64 [E], offsets int64 "
+                           "[dim_size + 1] (a Grouping of the rows of src)")
+    s2 = _rows(src).float()
+    n, c = offsets.shape[0] - 1, s2.shape[1]
+    shape = (n,) + tuple(src.shape[1:])
+    dev = src.device
+    res = torch.empty((n, c), dtype=torch.float32, device=dev)
+    arg = torch.empty((n, c), dtype=torch.int64, device=dev) if mode == 2 else None
+    if c == 0 or n == 0:
+        return res.reshape(shape), None if arg is None else arg.reshape(shape)
+    lib = _lib.load()
+    need = lib.mtmc_scatter_grouped_workspace_bytes(e, c)
+    if need == 0:
+        raise RuntimeError(f"mtmc_mpn.{name}: unsupported size")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _call.run(dev, lib.mtmc_scatter_grouped, s2.data_ptr(), e, c, perm.contiguous().data_ptr(), offsets.contiguous().data_ptr(),
+              n, mode, res.data_ptr(), None if arg is None else arg.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
+    return res.reshape(shape), None if arg is None else arg.reshape(shape)
+
+
+@torch.library.impl("mtmc_mpn::scatter_add_grouped", "CUDA")
+def _scatter_add_grouped(src, index, perm, offsets):
+    return _scatter_grouped("scatter_add_grouped", 0, src, index, perm, offsets)[0]
+
+
+@torch.library.impl("mtmc_mpn::scatter_mean_grouped", "CUDA")
+def _scatter_mean_grouped(src, index, perm, offsets):
+    return _scatter_grouped("scatter_mean_grouped", 1, src, index, perm, offsets)[0]
+
+
+@torch.library.impl("mtmc_mpn::scatter_max_grouped", "CUDA")
+def _scatter_max_grouped(src, index, perm, offsets):
+    return _scatter_grouped("scatter_max_grouped", 2, src, index, perm, offsets)
+
+
+def _scatter_grouped_fake(src, index, perm, offsets):
+    return src.new_empty((offsets.shape[0] - 1,) + tuple(src.shape[1:]), dtype=torch.float32)
+
+
+torch.library.register_fake("mtmc_mpn::scatter_add_grouped")(_scatter_grouped_fake)
+torch.library.register_fake("mtmc_mpn::scatter_mean_grouped")(_scatter_grouped_fake)
+
+
+@torch.library.register_fake("mtmc_mpn::scatter_max_grouped")
+def _scatter_max_grouped_fake(src, index, perm, offsets):
+    out = _scatter_grouped_fake(src, index, perm, offsets)
+    return out, out.new_empty(out.shape, dtype=torch.int64)
+
+
+def _scatter_grouped_setup_context(ctx, inputs, output):
+    src, index, _perm, _offsets = inputs
+    ctx.n_src, ctx.src_dtype = src.shape[0], src.dtype
+    if isinstance(output, tuple):                      # scatter_max_grouped: (values, argmax)
+        ctx.save_for_backward(output[1], index)
+    else:
+        ctx.save_for_backward(index)
+
+
+# the gradients are gathers by `index` through the backward ops of the atomics forwards: the same bits as theirs
+torch.library.register_autograd("mtmc_mpn::scatter_add_grouped", _scatter_autograd(torch.ops.mtmc_mpn.scatter_add_backward),
+                                setup_context=_scatter_grouped_setup_context)
+torch.library.register_autograd("mtmc_mpn::scatter_mean_grouped", _scatter_autograd(torch.ops.mtmc_mpn.scatter_mean_backward),
+                                setup_context=_scatter_grouped_setup_context)
+torch.library.register_autograd("mtmc_mpn::scatter_max_grouped", _scatter_autograd(torch.ops.mtmc_mpn.scatter_max_backward),
+                                setup_context=_scatter_grouped_setup_context)

@@ -20,7 +20,9 @@
  *                                 BatchNorm statistics / node states (no reference counterpart:
  *                                 the reference is single-GPU)
  *   mtmc_scatter_{add,mean,max}<- torch_scatter.scatter_{add,mean,max}(src, index, dim=0, dim_size)
- *                                 (third-party pytorch-scatter 2.0.8; call sites models/mpn.py:196,199,202)
+ *                                 (third-party pytorch-scatter 2.0.8; call sites models/mpn.py:196,199,202);
+ *                                 mtmc_scatter_grouped: the same three as a repeatable segmented reduction over a
+ *                                 grouping of the rows, mtmc_group_by_index: that grouping (a stable radix sort)
  *   mtmc_mlp_forward           <- MLP.forward as a stand-alone op  models/mlp.py:32-33
  *   mtmc_build_graph           <- graph construction around the call  inference.py:402-456, train.py:316-342
  *   mtmc_postprocess           <- softmax/argmax + post_processing    inference.py:475-489, :70-169; utils.py:30-339
@@ -296,6 +298,24 @@ int32_t mtmc_scatter_mean_backward(const float* grad_out, const int64_t* index, 
                                    int64_t dim_size, int32_t* count_scratch, float* grad_src, void* stream);
 int32_t mtmc_scatter_max_backward(const float* grad_out, const int64_t* arg, const int64_t* index, int64_t n_src,
                                   int64_t n_cols, int64_t dim_size, float* grad_src, void* stream);
+
+/* The repeatable forward of the three float scatters: a segmented reduction over a grouping of the rows (mtmc_group_by_index
+ * below, or any perm / offsets pair of that form): out[g] reduces the rows perm[j], offsets[g] <= j < offsets[g + 1].
+ * mode 0 add, 1 mean, 2 max (arg_out as above, may be NULL).  Semantics of the three entries above: rows behind
+ * offsets[dim_size] count for nothing, a row nobody writes is 0, mean divides by (float)max(offsets[g + 1] - offsets[g], 1),
+ * max compares as mtmc_scatter_max does and arg_out is the smallest source row of the maximum (n_src where none).
+ * No fill launch, no float atomic, no count buffer: every output element has one writer, and every sum one order that is a
+ * function of (n_src, n_cols, offsets) alone -- chunks of 64 positions, per chunk strided sub-row sums folded in a fixed
+ * butterfly, chunk partials of a group that crosses chunks folded by the same rule in chunk order (csrc/scatter_ops.hip
+ * writes it out) -- so the result has the same bits on every run, on every grid and however the grouping was made.  A
+ * group of one row is a bit-exact copy of that row.  perm entries outside [0, n_src) name no row; offsets are clamped into
+ * [0, n_src] before use.  16-byte loads when n_cols % 4 == 0 and src, out and workspace are 16-byte aligned (the order does
+ * not depend on it).  Two launches (one when n_src == 0; none when dim_size == 0).  The size query is host-only and
+ * returns 0 for sizes the entry refuses (n_src outside [0, 2^31), n_cols < 1). */
+size_t mtmc_scatter_grouped_workspace_bytes(int64_t n_src, int64_t n_cols);
+int32_t mtmc_scatter_grouped(const float* src, int64_t n_src, int64_t n_cols, const int64_t* perm, const int64_t* offsets,
+                             int64_t dim_size, int32_t mode, float* out, int64_t* arg_out, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* y[rows, out] = relu(batchnorm_batchstats(x[rows,in] . W^T + b)) for one Linear+BN+ReLU group
  * (gamma == NULL: bare Linear).  stats_scratch: f64[2*out], y_raw aliases y. */
@@ -652,6 +672,22 @@ int32_t mtmc_pool_tracklets_weight_grad(const float* embeds, int64_t row_stride,
                                         const int64_t* offsets, int64_t n_tracklets, const int64_t* perm,
                                         const float* grad_out, const float* out, const float* wsum, float* grad_weights,
                                         void* stream);
+
+/* ---- stable grouping of int64 keys: the perm / offsets pair of mtmc_pool_tracklets_weighted and mtmc_scatter_grouped ----
+ * index [n_rows] int64 in device memory, n_groups a host int.  The key of row r is index[r] if it lies in [0, n_groups), else
+ * n_groups.  perm [n_rows] int64 lists the rows by key, rows with equal keys in increasing row order (a stable sort: there
+ * is one answer); offsets [n_groups + 1] int64: group g owns perm[offsets[g] : offsets[g + 1]], and the rows keyed n_groups
+ * lie behind offsets[n_groups], in row order.  info (may be NULL): one int32, the number of rows keyed n_groups.
+ * An LSD radix sort over ceil(bits(n_groups) / digit_bits) passes on tiles of mtmc_group_tile_rows() rows (per pass a
+ * per-tile digit histogram, an exclusive scan over (digit, tile), and a placement whose ranks are computed with wave ballots
+ * and prefixed in wave order, never drawn from an atomic); digit_bits = 0 lets the library choose, 1 .. 11 forces the width.
+ * One pass when n_groups + 1 <= 2^digit_bits.  Nothing is read back, allocated or synchronised; nothing read from index
+ * becomes an address unclamped.  n_rows == 0 or n_groups == 0: an all-zero offsets and perm in row order, one launch, no
+ * workspace.  Limits: n_rows, n_groups < 2^31.  The size query is host-only and returns 0 for sizes the entry refuses. */
+int32_t mtmc_group_tile_rows(void);
+size_t mtmc_group_by_index_workspace_bytes(int64_t n_rows, int64_t n_groups, int32_t digit_bits);
+int32_t mtmc_group_by_index(const int64_t* index, int64_t n_rows, int64_t n_groups, int32_t digit_bits, int64_t* perm,
+                            int64_t* offsets, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- the score the reference reports: IDF1 / IDP / IDR of a tracking result (main.py:166-213, eval/eval.py::eval) ----
  * The definition is DESIGN.md 3.11.  Two tables of detections (ground truth, predictions), each already GROUPED by the
