@@ -18,6 +18,7 @@ from .ops import FocalLoss, cross_entropy, cross_entropy_steps, edge_loss, focal
 from . import metrics  # noqa: F401
 from .metrics import ClusterScores, EdgePRF, cluster_scores, edge_prf, evaluate  # noqa: F401
 from .metrics import IdScores, idf1, relabel_detections  # noqa: F401
+from .metrics import MotScores, mot_pairs, mot_scores, tracking_summary  # noqa: F401
 from .feature_store import FeatureStore  # noqa: F401
 from .modules import (MLP, EdgeModel, MetaLayer, MLPGraphIndependent, MOTMPNet,  # noqa: F401
                       NodeModel)
@@ -26,4 +27,5 @@ __all__ = ["MOTMPNet", "MetaLayer", "EdgeModel", "NodeModel", "MLPGraphIndepende
            "DEFAULT_GRAPH_NET_PARAMS", "DEFAULT_ARCH", "default_params", "build_graph", "postprocess", "FeatureStore", "cross_entropy", "cross_entropy_steps", "edge_loss", "ops",
            "metrics", "cluster_scores", "edge_prf", "evaluate", "ClusterScores", "EdgePRF", "pool", "pool_tracklets",
            "focal_loss", "FocalLoss", "idf1", "relabel_detections", "IdScores",
+           "mot_scores", "mot_pairs", "tracking_summary", "MotScores",
            "Grouping", "group_by_index"]

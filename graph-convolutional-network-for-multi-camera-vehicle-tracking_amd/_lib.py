@@ -86,6 +86,7 @@ CLUSTER_SCORES, CLUSTER_COUNTS, EDGE_PRF = 9, 7, 5        # mtmc_cluster_scores:
 CLUSTER_SCORES_MAX_N = 1048576
 POOL_INFO = 4                                             # mtmc_pool_tracklets: info words
 ID_MAX_CELLS, ID_MAX_CAMERAS = 1 << 26, 64                # mtmc_id_overlap: n_obj * n_hyp; mtmc_id_filter: cameras
+MOT_COUNTS = 12                                           # mtmc_mot_walk: count words
 
 # MTMC_MPN_LIB: another build of the same ABI (same-box A/B of two library versions, tools/lib_ab.sh); default: the in-tree build
 LIB_PATH = os.environ.get("MTMC_MPN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmtmc_mpn.so")
@@ -166,6 +167,9 @@ SIGNATURES = {
     "mtmc_id_overlap": (_i32, [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f64, _p, _sz, _p]),
     "mtmc_id_cells": (_i32, [_p, _i64, _i64, _p, _i64, _p, _p]),
     "mtmc_id_assign": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p]),
+    "mtmc_mot_pairs_workspace_bytes": (_sz, [_i64]),
+    "mtmc_mot_pairs": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _f64, _p, _p, _i64, _p, _p, _sz, _p]),
+    "mtmc_mot_walk": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -2,6 +2,7 @@
 // their arguments and enqueue the kernels of id_metrics.hip; mtmc_id_assign is the host half, the exact assignment that
 // turns the overlap counts C into IDTP.  It touches no GPU.
 #include "api_error.h"
+#include "assign.h"
 #include "id_metrics.h"
 
 #include <algorithm>
@@ -14,47 +15,14 @@ using mtmc_api::fail;
 
 constexpr int64_t kRowLimit = (int64_t)1 << 31;
 
-// Max-weight assignment of an n x m matrix of weights >= 0 (row-major, n <= m): every row gets a column, shortest
-// augmenting paths with potentials (the Hungarian method in its O(n^2 m) form) on the costs -w, integers throughout.
-// col_of_row[i] = the column of row i.  Returns the optimum.
+// Max-weight assignment of an n x m matrix of weights >= 0 (row-major, n <= m): every row gets a column, by the shared
+// solver (assign.h) on the costs -w, integers throughout.  col_of_row[i] = the column of row i.  Returns the optimum.
 int64_t assign_dense(const int32_t* w, int n, int m, std::vector<int>& col_of_row) {
-  const int64_t inf = INT64_MAX / 4;
-  std::vector<int64_t> u(n + 1, 0), v(m + 1, 0), minv(m + 1);
-  std::vector<int> p(m + 1, 0), way(m + 1, 0);
-  std::vector<char> used(m + 1);
-  for (int i = 1; i <= n; ++i) {
-    p[0] = i;
-    int j0 = 0;
-    std::fill(minv.begin(), minv.end(), inf);
-    std::fill(used.begin(), used.end(), 0);
-    do {
-      used[j0] = 1;
-      const int i0 = p[j0];
-      int64_t delta = inf;
-      int j1 = 0;
-      const int32_t* row = w + (size_t)(i0 - 1) * m;
-      for (int j = 1; j <= m; ++j) {
-        if (used[j]) continue;
-        const int64_t cur = -(int64_t)row[j - 1] - u[i0] - v[j];
-        if (cur < minv[j]) { minv[j] = cur; way[j] = j0; }
-        if (minv[j] < delta) { delta = minv[j]; j1 = j; }
-      }
-      for (int j = 0; j <= m; ++j) {
-        if (used[j]) { u[p[j]] += delta; v[j] -= delta; }
-        else minv[j] -= delta;
-      }
-      j0 = j1;
-    } while (p[j0] != 0);
-    do {
-      const int j1 = way[j0];
-      p[j0] = p[j1];
-      j0 = j1;
-    } while (j0);
-  }
-  col_of_row.assign(n, -1);
+  mtmc_assign::assign_rows<int64_t>(n, m, [w, m](int i, int j) { return -(int64_t)w[(size_t)i * m + j]; }, INT64_MAX / 4,
+                                    col_of_row);
   int64_t best = 0;
-  for (int j = 1; j <= m; ++j)
-    if (p[j]) { col_of_row[p[j] - 1] = j - 1; best += w[(size_t)(p[j] - 1) * m + (j - 1)]; }
+  for (int i = 0; i < n; ++i)
+    if (col_of_row[i] >= 0) best += w[(size_t)i * m + col_of_row[i]];
   return best;
 }
 

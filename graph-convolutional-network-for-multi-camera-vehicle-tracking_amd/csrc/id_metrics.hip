@@ -116,57 +116,14 @@ __global__ __launch_bounds__(256) void id_prefix_kernel(IdOverlapArgs a) {
   }
 }
 
-// ---- the overlap of one pair ---------------------------------------------------------------------------------------------
-// d = 1 - I / U with I = iw ih and U = aw ah + bw bh - I, every operation rounded on its own: a fused multiply-add in U
-// moves its last bit and with it a pair that sits on the threshold.  U = 0 gives NaN, which is not <= max_dist.
-__device__ __forceinline__ bool id_pair_counts(const double* a, const double* b, double max_dist) {
-#pragma clang fp contract(off)
-  const double ax = a[0], ay = a[1], aw = a[2], ah = a[3], bx = b[0], by = b[1], bw = b[2], bh = b[3];
-  const double iw = fmax(0.0, fmin(ax + aw, bx + bw) - fmax(ax, bx));
-  const double ih = fmax(0.0, fmin(ay + ah, by + bh) - fmax(ay, by));
-  const double inter = iw * ih;
-  const double area_a = aw * ah, area_b = bw * bh;
-  const double uni = area_a + area_b - inter;
-  const double d = 1.0 - inter / uni;
-  return d <= max_dist;
-}
-
+// ---- the hot pass: one int32 atomicAdd into C[o][h] per pair within max_dist (distance and work split: id_metrics.h) ----
 __global__ __launch_bounds__(256) void id_pairs_kernel(IdOverlapArgs a) {
-  const long long total = a.prefix[a.n_groups];
-  const long long stride = (long long)gridDim.x * kIdPairsPerBlock;
-  for (long long base = (long long)blockIdx.x * kIdPairsPerBlock; base < total; base += stride) {
-    const long long p0 = base + (long long)threadIdx.x * kIdPairsPerLane;
-    if (p0 >= total) continue;
-    const long long p1 = p0 + kIdPairsPerLane < total ? p0 + kIdPairsPerLane : total;
-    int64_t g = 0, hi = a.n_groups;                  // prefix[g] <= p0 < prefix[hi]
-    while (hi - g > 1) {
-      const int64_t mid = g + (hi - g) / 2;
-      if (a.prefix[mid] <= p0) g = mid; else hi = mid;
-    }
-    long long g0 = a.gt_off[g], q0 = a.pr_off[g], np = a.pr_off[g + 1] - q0;
-    np = np > a.n_pr ? a.n_pr : np;                  // (as id_group_pairs clamps it; np >= 1: the group has pairs)
-    long long local = p0 - a.prefix[g];
-    long long o = local / np, h = local - o * np;
-    for (long long p = p0; p < p1; ++p) {
-      const long long r = g0 + o, c = q0 + h;
-      if (r >= 0 && r < a.n_gt && c >= 0 && c < a.n_pr && a.pr_keep[c] && (!a.gt_keep || a.gt_keep[r])) {
-        const int32_t oi = a.gt_ident[r], hi_ = a.pr_ident[c];
-        if (oi >= 0 && oi < a.n_obj && hi_ >= 0 && hi_ < a.n_hyp &&
-            id_pair_counts(a.gt_boxes + 4 * r, a.pr_boxes + 4 * c, a.max_dist))
-          atomicAdd(a.cells + (int64_t)oi * a.n_hyp + hi_, 1);
-      }
-      if (++h == np) {
-        h = 0;
-        ++o;
-        if (p + 1 < p1 && a.prefix[g + 1] == p + 1) {  // the group is done: on to the next one that has pairs
-          do ++g; while (g + 1 < a.n_groups && a.prefix[g + 1] == a.prefix[g]);
-          g0 = a.gt_off[g]; q0 = a.pr_off[g]; np = a.pr_off[g + 1] - q0;
-          np = np > a.n_pr ? a.n_pr : np;
-          o = 0;
-        }
-      }
-    }
-  }
+  id_walk_pairs(a, [&a](int64_t, long long r, long long c) {
+    const int32_t oi = a.gt_ident[r], hi_ = a.pr_ident[c];
+    if (oi >= 0 && oi < a.n_obj && hi_ >= 0 && hi_ < a.n_hyp &&
+        id_pair_distance(a.gt_boxes + 4 * r, a.pr_boxes + 4 * c) <= a.max_dist)
+      atomicAdd(a.cells + (int64_t)oi * a.n_hyp + hi_, 1);
+  });
 }
 
 __global__ __launch_bounds__(256) void id_compact_kernel(const int32_t* cells, int64_t n_cells, int64_t n_hyp, int32_t* triples,
@@ -190,10 +147,13 @@ void launch_id_filter(const IdFilterArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(id_finish_kernel, dim3(blocks), dim3(256), 0, s, a);
 }
 
-void launch_id_overlap(const IdOverlapArgs& a, hipStream_t s) {
+void launch_id_prefix(const IdOverlapArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(id_prefix_kernel, dim3(1), dim3(256), 0, s, a);
-  // the pair count stays on the device: n_gt n_pr (both below 2^31) bounds it, the grid rule caps the launch
-  hipLaunchKernelGGL(id_pairs_kernel, dim3(blocks_for(a.n_gt * a.n_pr, kIdPairsPerBlock, 2048)), dim3(256), 0, s, a);
+}
+
+void launch_id_overlap(const IdOverlapArgs& a, hipStream_t s) {
+  launch_id_prefix(a, s);
+  hipLaunchKernelGGL(id_pairs_kernel, dim3(id_pair_blocks(a)), dim3(256), 0, s, a);
 }
 
 void launch_id_compact(const int32_t* cells, int64_t n_obj, int64_t n_hyp, int32_t* triples, int64_t max_triples,

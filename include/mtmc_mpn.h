@@ -30,6 +30,7 @@
  *                                 libs/reid_feature_extraction.py:177-178 (mtmc_pool_tracklets_weighted: rows in any order, a weight per
  *                                 detection, libs/filter_mtmc.py's filters as weights)
  *   mtmc_id_filter / _overlap / _cells / _assign <- IDF1 / IDP / IDR of a result  main.py:166-213, eval/eval.py::eval
+ *   mtmc_mot_pairs / _walk     <- the CLEAR MOT columns of that result (MOTA, MOTP, switches, ...)  eval/eval.py:409-411
  *
  * All floating tensors are fp32, row-major, contiguous unless a stride argument says otherwise;
  * BatchNorm statistics are accumulated in fp64.  All work is enqueued on `stream` (a hipStream_t
@@ -737,6 +738,48 @@ int32_t mtmc_id_cells(const void* workspace, int64_t n_obj, int64_t n_hyp, int32
                       void* stream);
 int32_t mtmc_id_assign(const int32_t* cells, int64_t n_cells, int64_t n_obj, int64_t n_hyp, int64_t* idtp, int32_t* match_of_obj,
                        int64_t* stats);
+
+/* ---- the CLEAR MOT columns of the same result row: MOTA, MOTP, recall, precision, switches, ... (eval/eval.py:409-411) ----
+ * The definition is DESIGN.md 3.12.  The tables are the GROUPED ones of mtmc_id_filter / mtmc_id_overlap above, with their
+ * offsets and keep bytes; the groups are numbered in ascending (camera, frame).
+ * mtmc_mot_pairs: every CANDIDATE, a (ground-truth row, prediction row) pair of one group, both kept (gt_keep may be NULL:
+ *   all), with d = 1 - I / U <= max_dist -- the very test of mtmc_id_overlap, so a pair is listed exactly when it counts
+ *   there.  pairs [max_pairs][3] int32 = (group, ground-truth row, prediction row) and dist [max_pairs] fp64 = d, both in
+ *   device memory, filled behind the counter n_pairs [1] int64 (device memory, cleared by the call) in NO PARTICULAR ORDER:
+ *   sort by (group, ground-truth row, prediction row), which is the order of (ground-truth row, prediction row) alone.
+ *   n_pairs may exceed max_pairs: nothing is written past the list, call again with a larger one.  A lane counts the
+ *   candidates among its pairs, one integer atomic add per wave reserves their slots, the lane writes them; there are no
+ *   floating-point atomics: the sorted list is the same bits on every run.  The work split is
+ *   mtmc_id_overlap's (a prefix sum over the groups in the workspace; no limit on a group's size); every offset and row is
+ *   checked against its array before use.  Runs on `stream`, allocates nothing, synchronises nothing.  MTMC_E_ARG (with
+ *   text): a row or group count >= 2^31, a NULL pointer, a workspace short of mtmc_mot_pairs_workspace_bytes (host-only;
+ *   0 for sizes that are refused).  Zero rows on either side are legal.
+ * mtmc_mot_walk is HOST-ONLY and touches no GPU: the sorted candidates and, per row of either grouped table, its group,
+ *   its compact identity and its keep byte (NULL: all kept), for ground-truth rows also the position in the input (any
+ *   strictly increasing numbering of the input order).  Ground-truth rows are sorted by (group, identity), prediction rows
+ *   by group.  It visits the groups in ascending order and does what MOTAccumulator.update does with an infinite
+ *   max_switch_time: first every identity keeps the prediction it was last matched to while the two are candidates (in
+ *   input order), then the rows not taken are assigned -- the most pairs, among those the smallest fp64 sum of d, exactly,
+ *   by shortest augmenting paths per connected component of the group's candidates (a group in which no row has two
+ *   candidates needs no solver) -- a pair whose identity was last matched to another predicted identity being a SWITCH.
+ *   counts [MTMC_MOT_COUNTS] int64 = matches, switches, misses, false positives, fragmentations, mostly tracked, partially
+ *   tracked, mostly lost, unique objects, kept ground-truth rows, kept prediction rows, frames (groups with a kept row);
+ *   dist_sum = the sum of d over matches and switches, added sequentially in the order of the ground-truth rows;
+ *   match_of_row [n_gt] int32 = the prediction row of each ground-truth row, -1: a miss, -2: not kept; stats [3] (may be
+ *   NULL) = the groups that needed the solver, then the rows and columns of the largest component solved (rows x columns,
+ *   ties: more rows).  MTMC_E_ARG (with text): candidates not sorted or listed twice, a row outside its table, a pair
+ *   across groups or of a row not kept, a NaN distance, rows not sorted, a predicted identity kept twice in one group. */
+#define MTMC_MOT_COUNTS 12
+size_t mtmc_mot_pairs_workspace_bytes(int64_t n_groups);
+int32_t mtmc_mot_pairs(const double* gt_boxes, const int64_t* gt_offsets, const uint8_t* gt_keep, int64_t n_gt,
+                       const double* pred_boxes, const int64_t* pred_offsets, const uint8_t* pred_keep, int64_t n_pred,
+                       int64_t n_groups, double max_dist, int32_t* pairs, double* dist, int64_t max_pairs, int64_t* n_pairs,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int32_t mtmc_mot_walk(const int32_t* pairs, const double* dist, int64_t n_pairs, const int32_t* gt_group,
+                      const int32_t* gt_identity, const int64_t* gt_position, const uint8_t* gt_keep, int64_t n_gt,
+                      const int32_t* pred_group, const int32_t* pred_identity, const uint8_t* pred_keep, int64_t n_pred,
+                      int64_t n_groups, int64_t n_obj, int64_t n_hyp, int64_t* counts, double* dist_sum, int32_t* match_of_row,
+                      int64_t* stats);
 
 #ifdef __cplusplus
 }
