@@ -6,21 +6,13 @@
 //   mtmc_pool_tracklets_weighted (+ _backward, mtmc_pool_tracklets_weight_grad)  the same through a row permutation and
 //                                 with per-detection weights: out[s] = sum w_r x_r / sum w_r (further down)
 // A pure streaming problem (F = 2048: 8 KB per row, tracklets of 1 to a few thousand rows); what there is to get right is the
-// load balance and the order of the additions:
-//   * the D rows are cut into chunks of kPoolR rows, the F columns into slabs of 256: ONE WAVE per (chunk, slab), one
-//     float4 per lane, so every row read is 1 KiB coalesced and no wave ever walks more than kPoolR rows, however long the
-//     longest tracklet is;
-//   * a chunk finds its first tracklet by binary search in offsets, finishes the tracklets that lie wholly inside it (sum,
-//     divide, store) and leaves at most two partial sums, in partial[chunk][2][F]: slot 0 ("head") for the tracklet that
-//     came in from the previous chunk, slot 1 ("tail") for the one that goes on into the next;
-//   * pool_finish_kernel, one wave per (tracklet, slab), adds the partial sums of a chunk-crossing tracklet IN CHUNK ORDER
-//     (its first chunk's tail, then the heads of the chunks after it), divides and stores; it also writes the zero row of an
-//     empty range and checks the offsets.
-// No atomics on floats anywhere: every sum has one fixed order, so the result is the same bits on every run.
-// The offsets live in device memory and the host never sees them: every value is clamped into [0, D] before it indexes
-// anything, and what was wrong with them is reported in info[0] (0 ok; 1 not strictly increasing or outside [0, D];
-// 2 offsets[0] != 0 or offsets[N] != D -- the larger one if both), info[1] = how many tracklets had a bad range.
+// load balance and the order of the additions.  The decomposition is seg_walk.h's with chunks of kPoolR
+// rows and slabs of 256 columns: one float4 per lane, so every row read is 1 KiB coalesced and no wave ever walks more
+// than kPoolR rows.  The finish kernels also write the zero row of an empty range and check the offsets.  No atomics on
+// floats anywhere: every sum has one fixed order.  What was wrong with the offsets is reported in info[0] (0 ok; 1 not strictly
+// increasing or outside [0, D]; 2 offsets[0] != 0 or offsets[N] != D -- the larger one if both), info[1] = tracklets with a bad range.
 #include "api_internal.h"
+#include "seg_walk.h"
 #include <limits.h>
 
 namespace mtmc {
@@ -30,23 +22,11 @@ constexpr int kPoolSlab = 256;        // columns per wave
 constexpr int kPoolMaxF = 16384;
 typedef float pool_f4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int64_t pool_clamp(int64_t v, int64_t D) { return v < 0 ? 0 : (v > D ? D : v); }
-
-// the largest s in [0, N-1] with offsets[s] <= r (s = 0 if there is none); any contents of offsets end the search
-__device__ __forceinline__ int64_t pool_find(const int64_t* offsets, int64_t N, int64_t D, int64_t r) {
-  int64_t lo = 0, hi = N - 1;
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if (pool_clamp(offsets[mid], D) <= r) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// which (item, slab) this wave works on: the waves of a workgroup take neighbouring slabs of one item first
+// the item (chunk or tracklet) and the four columns of this lane; false: nothing to do
 __device__ __forceinline__ bool pool_wave(int64_t items, int slabs, int F, int64_t* item, int* col) {
-  const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  *item = w / slabs;
-  *col = (int)(w - *item * slabs) * kPoolSlab + (int)(threadIdx.x & 63) * 4;
+  int slab;
+  seg_wave(slabs, item, &slab);
+  *col = slab * kPoolSlab + (int)(threadIdx.x & 63) * 4;
   return *item < items && *col < F;
 }
 
@@ -82,24 +62,16 @@ __global__ __launch_bounds__(256) void pool_chunks_kernel(const float* embeds, i
   const int slabs = (F + kPoolSlab - 1) / kPoolSlab;
   int64_t c;
   int col;
-  if (!pool_wave((D + kPoolR - 1) / kPoolR, slabs, F, &c, &col)) return;
-  const int64_t r0 = c * kPoolR, r1 = r0 + kPoolR < D ? r0 + kPoolR : D;
-  int64_t cur = r0;
-  for (int64_t s = pool_find(offsets, N, D, r0); s < N && cur < r1;) {
-    const int64_t a = pool_clamp(offsets[s], D), b = pool_clamp(offsets[s + 1], D);
-    if (b <= cur) { ++s; continue; }                      // empty, inverted or behind us: pool_finish_kernel's
-    const int64_t lo = a > cur ? a : cur, hi = b < r1 ? b : r1;
-    if (lo >= r1) break;
+  if (!pool_wave(seg_chunks(D, kPoolR), slabs, F, &c, &col)) return;
+  const int64_t r0 = c * kPoolR, r1 = seg_chunk_end(r0, kPoolR, D);
+  seg_walk(offsets, N, D, r0, r1, [&](int64_t s, int64_t a, int64_t b, int64_t lo, int64_t hi) {
     const pool_f4 acc = pool_sum_rows(embeds + col, stride, lo, hi);
-    if (a >= r0 && b <= r1) {
+    if (seg_inside(a, b, r0, r1)) {
       *reinterpret_cast<pool_f4*>(out + s * F + col) = acc / (float)(b - a);
     } else {
-      *reinterpret_cast<pool_f4*>(partial + (c * 2 + (a < r0 ? 0 : 1)) * F + col) = acc;
+      *reinterpret_cast<pool_f4*>(partial + seg_slot(c, a, r0) * F + col) = acc;
     }
-    cur = hi;
-    if (b > r1) break;
-    ++s;
-  }
+  }, SegNoGap());
 }
 
 __global__ __launch_bounds__(256) void pool_finish_kernel(int64_t D, int F, const int64_t* offsets, int64_t N, float* out,
@@ -117,16 +89,16 @@ __global__ __launch_bounds__(256) void pool_finish_kernel(int64_t D, int F, cons
       atomicAdd(info + 1, 1);
     }
   }
-  const int64_t a = pool_clamp(ra, D), b = pool_clamp(rb, D);
+  const int64_t a = seg_clamp(ra, D), b = seg_clamp(rb, D);
   pool_f4* dst = reinterpret_cast<pool_f4*>(out + s * F + col);
   if (b <= a) {
     *dst = pool_f4{0.f, 0.f, 0.f, 0.f};
     return;
   }
-  const int64_t c0 = a / kPoolR, c1 = (b - 1) / kPoolR;
+  const int64_t c0 = seg_first_chunk(a, kPoolR), c1 = seg_last_chunk(b, kPoolR);
   if (c0 == c1) return;                                    // finished inside its chunk
   // the tail of chunk c0, then the heads of chunks c0 + 1 .. c1: rows of stride 2 F starting at the first head
-  const pool_f4 tail = *reinterpret_cast<const pool_f4*>(partial + (c0 * 2 + 1) * F + col);
+  const pool_f4 tail = *reinterpret_cast<const pool_f4*>(partial + seg_tail(c0) * F + col);
   const pool_f4 heads = pool_sum_rows(partial + col, 2 * (int64_t)F, c0 + 1, c1 + 1);
   *dst = (tail + heads) / (float)(b - a);
 }
@@ -139,24 +111,16 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const float* g, int6
   const int slabs = (F + kPoolSlab - 1) / kPoolSlab;
   int64_t c;
   int col;
-  if (!pool_wave((D + kPoolR - 1) / kPoolR, slabs, F, &c, &col)) return;
-  const int64_t r0 = c * kPoolR, r1 = r0 + kPoolR < D ? r0 + kPoolR : D;
+  if (!pool_wave(seg_chunks(D, kPoolR), slabs, F, &c, &col)) return;
+  const int64_t r0 = c * kPoolR, r1 = seg_chunk_end(r0, kPoolR, D);
   float* dst = d_embeds + col;
-  const pool_f4 zero = {0.f, 0.f, 0.f, 0.f};
-  int64_t cur = r0;
-  for (int64_t s = pool_find(offsets, N, D, r0); s < N && cur < r1;) {
-    const int64_t a = pool_clamp(offsets[s], D), b = pool_clamp(offsets[s + 1], D);
-    if (b <= cur) { ++s; continue; }
-    const int64_t lo = a > cur ? (a < r1 ? a : r1) : cur, hi = b < r1 ? b : r1;
-    for (; cur < lo; ++cur) *reinterpret_cast<pool_f4*>(dst + cur * stride) = zero;
-    if (lo >= r1) break;
+  seg_walk(offsets, N, D, r0, r1, [&](int64_t s, int64_t a, int64_t b, int64_t lo, int64_t hi) {
     const pool_f4 v = *reinterpret_cast<const pool_f4*>(g + s * F + col) / (float)(b - a);
     // (non-temporal: D F 4 bytes nobody in this launch reads again; measured 84 -> 55 us on 310 MB against plain stores)
-    for (; cur < hi; ++cur) __builtin_nontemporal_store(v, reinterpret_cast<pool_f4*>(dst + cur * stride));
-    if (b > r1) break;
-    ++s;
-  }
-  for (; cur < r1; ++cur) *reinterpret_cast<pool_f4*>(dst + cur * stride) = zero;
+    for (int64_t r = lo; r < hi; ++r) __builtin_nontemporal_store(v, reinterpret_cast<pool_f4*>(dst + r * stride));
+  }, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) *reinterpret_cast<pool_f4*>(dst + r * stride) = pool_f4{0.f, 0.f, 0.f, 0.f};
+  });
 }
 
 // ---- detections in any order (perm) and per-detection weights: out[s] = sum_r w_r x_r / sum_r w_r ----
@@ -172,11 +136,11 @@ constexpr int kPoolBadOffsets = 1, kPoolBadEnds = 2, kPoolBadPerm = 4, kPoolBadW
 
 struct PoolRowRef { int row; float w; };      // of one position, held by the lane of that position
 
-// (chunk or tracklet, slab) of this wave as pool_wave, but lanes past F stay: they work on column 0 and store nothing
+// as pool_wave, but lanes past F stay: they work on column 0 and store nothing
 __device__ __forceinline__ bool pool_wave_all(int64_t items, int slabs, int F, int64_t* item, int* col, bool* live) {
-  const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  *item = w / slabs;
-  const int c = (int)(w - *item * slabs) * kPoolSlab + (int)(threadIdx.x & 63) * 4;
+  int slab;
+  seg_wave(slabs, item, &slab);
+  const int c = slab * kPoolSlab + (int)(threadIdx.x & 63) * 4;
   *live = c < F;
   *col = *live ? c : 0;
   return *item < items;
@@ -234,8 +198,8 @@ __global__ __launch_bounds__(256) void pool_chunks_wp_kernel(const float* embeds
   int64_t c;
   int col;
   bool live;
-  if (!pool_wave_all((D + kPoolR - 1) / kPoolR, slabs, F, &c, &col, &live)) return;
-  const int64_t r0 = c * kPoolR, r1 = r0 + kPoolR < D ? r0 + kPoolR : D;
+  if (!pool_wave_all(seg_chunks(D, kPoolR), slabs, F, &c, &col, &live)) return;
+  const int64_t r0 = c * kPoolR, r1 = seg_chunk_end(r0, kPoolR, D);
   int flags = 0;
   const PoolRowRef ref = pool_row_ref<kPerm, kWeighted>(perm, weights, D, r0, r1, &flags);
   const bool first = col == 0 && live;                     // lane 0 of the chunk's first slab: the scalars are its to write
@@ -243,12 +207,7 @@ __global__ __launch_bounds__(256) void pool_chunks_wp_kernel(const float* embeds
     const unsigned long long lost = __ballot(flags & kPoolBadPerm), badw = __ballot(flags & kPoolBadWeight);
     if (first) cflag[c] = (lost ? kPoolBadPerm : 0) | (badw ? kPoolBadWeight : 0) | ((int)__popcll(lost) << 8);
   }
-  int64_t cur = r0;
-  for (int64_t s = pool_find(offsets, N, D, r0); s < N && cur < r1;) {
-    const int64_t a = pool_clamp(offsets[s], D), b = pool_clamp(offsets[s + 1], D);
-    if (b <= cur) { ++s; continue; }                      // empty, inverted or behind us: pool_finish_wp_kernel's
-    const int64_t lo = a > cur ? a : cur, hi = b < r1 ? b : r1;
-    if (lo >= r1) break;
+  seg_walk(offsets, N, D, r0, r1, [&](int64_t s, int64_t a, int64_t b, int64_t lo, int64_t hi) {
     pool_f4 acc = {0.f, 0.f, 0.f, 0.f};
     float W = 0.f;
     int at = (int)(lo - r0);
@@ -256,19 +215,16 @@ __global__ __launch_bounds__(256) void pool_chunks_wp_kernel(const float* embeds
     for (; at + 8 <= end; at += 8) pool_wrows_step<8>(embeds + col, stride, ref, at, &acc, &W);
     if (at + 4 <= end) { pool_wrows_step<4>(embeds + col, stride, ref, at, &acc, &W); at += 4; }
     for (; at < end; ++at) pool_wrows_step<1>(embeds + col, stride, ref, at, &acc, &W);
-    if (a >= r0 && b <= r1) {
+    if (seg_inside(a, b, r0, r1)) {
       const pool_f4 mean = W > 0.f ? acc / W : pool_f4{0.f, 0.f, 0.f, 0.f};
       if (live) *reinterpret_cast<pool_f4*>(out + s * F + col) = mean;
       if (first) wsum[s] = W;
     } else {
-      const int64_t slot = c * 2 + (a < r0 ? 0 : 1);
+      const int64_t slot = seg_slot(c, a, r0);
       if (live) *reinterpret_cast<pool_f4*>(partial + slot * F + col) = acc;
       if (first) wpart[slot] = W;
     }
-    cur = hi;
-    if (b > r1) break;
-    ++s;
-  }
+  }, SegNoGap());
 }
 
 // sum of wpart[2 c] for c in [lo, hi), in chunk order (every lane the same loads: one broadcast each)
@@ -294,7 +250,7 @@ __global__ __launch_bounds__(256) void pool_finish_wp_kernel(int64_t D, int F, c
                                                              const int* cflag, int* info) {
   if (info && blockIdx.x == 0 && threadIdx.x < 64) {       // one wave folds the chunks' words into info
     int bits = 0, lost = 0;
-    for (int64_t c = threadIdx.x; c < (D + kPoolR - 1) / kPoolR; c += 64) {
+    for (int64_t c = threadIdx.x; c < seg_chunks(D, kPoolR); c += 64) {
       const int v = cflag[c];
       bits |= v & 0xff;
       lost += v >> 8;
@@ -314,7 +270,7 @@ __global__ __launch_bounds__(256) void pool_finish_wp_kernel(int64_t D, int F, c
   if (!pool_wave_all(N, slabs, F, &s, &col, &live)) return;
   const bool first = col == 0 && live;
   const int64_t ra = offsets[s], rb = offsets[s + 1];
-  const int64_t a = pool_clamp(ra, D), b = pool_clamp(rb, D);
+  const int64_t a = seg_clamp(ra, D), b = seg_clamp(rb, D);
   if (info && first) {                                     // one lane per tracklet
     int st = ((kPerm ? ra > rb : ra >= rb) || ra < 0 || rb > D) ? kPoolBadOffsets : 0;
     if ((s == 0 && ra != 0) || (!kPerm && s == N - 1 && rb != D)) st |= kPoolBadEnds;
@@ -330,14 +286,14 @@ __global__ __launch_bounds__(256) void pool_finish_wp_kernel(int64_t D, int F, c
     if (live) *dst = pool_f4{0.f, 0.f, 0.f, 0.f};
     if (first) wsum[s] = 0.f;
   } else {
-    const int64_t c0 = a / kPoolR, c1 = (b - 1) / kPoolR;
+    const int64_t c0 = seg_first_chunk(a, kPoolR), c1 = seg_last_chunk(b, kPoolR);
     if (c0 == c1) {                                        // finished inside its chunk
       W = wsum[s];
     } else {
       // the tail of chunk c0, then the heads of chunks c0 + 1 .. c1, rows and weight sums alike
-      const pool_f4 tail = *reinterpret_cast<const pool_f4*>(partial + (c0 * 2 + 1) * F + col);
+      const pool_f4 tail = *reinterpret_cast<const pool_f4*>(partial + seg_tail(c0) * F + col);
       const pool_f4 heads = pool_sum_rows(partial + col, 2 * (int64_t)F, c0 + 1, c1 + 1);
-      W = wpart[c0 * 2 + 1] + pool_sum_heads(wpart, c0 + 1, c1 + 1);
+      W = wpart[seg_tail(c0)] + pool_sum_heads(wpart, c0 + 1, c1 + 1);
       const pool_f4 mean = W > 0.f ? (tail + heads) / W : pool_f4{0.f, 0.f, 0.f, 0.f};
       if (live) *dst = mean;
       if (first) wsum[s] = W;
@@ -357,8 +313,8 @@ __global__ __launch_bounds__(256) void pool_backward_wp_kernel(const float* g, i
   int64_t c;
   int col;
   bool live;
-  if (!pool_wave_all((D + kPoolR - 1) / kPoolR, slabs, F, &c, &col, &live)) return;
-  const int64_t r0 = c * kPoolR, r1 = r0 + kPoolR < D ? r0 + kPoolR : D;
+  if (!pool_wave_all(seg_chunks(D, kPoolR), slabs, F, &c, &col, &live)) return;
+  const int64_t r0 = c * kPoolR, r1 = seg_chunk_end(r0, kPoolR, D);
   int flags = 0;
   const PoolRowRef ref = pool_row_ref<kPerm, kWeighted>(perm, weights, D, r0, r1, &flags);
   const unsigned long long lost = __ballot(flags & kPoolBadPerm);
@@ -371,20 +327,13 @@ __global__ __launch_bounds__(256) void pool_backward_wp_kernel(const float* g, i
     if (kWeighted) v = v * __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ref.w), at));
     if (live) __builtin_nontemporal_store(v, reinterpret_cast<pool_f4*>(dst + (int64_t)row * stride));
   };
-  int64_t cur = r0;
-  for (int64_t s = pool_find(offsets, N, D, r0); s < N && cur < r1;) {
-    const int64_t a = pool_clamp(offsets[s], D), b = pool_clamp(offsets[s + 1], D);
-    if (b <= cur) { ++s; continue; }
-    const int64_t lo = a > cur ? (a < r1 ? a : r1) : cur, hi = b < r1 ? b : r1;
-    for (; cur < lo; ++cur) put(cur, zero);
-    if (lo >= r1) break;
+  seg_walk(offsets, N, D, r0, r1, [&](int64_t s, int64_t, int64_t, int64_t lo, int64_t hi) {
     const float W = wsum[s];
     const pool_f4 v = W > 0.f ? *reinterpret_cast<const pool_f4*>(g + s * F + col) / W : zero;
-    for (; cur < hi; ++cur) put(cur, v);
-    if (b > r1) break;
-    ++s;
-  }
-  for (; cur < r1; ++cur) put(cur, zero);
+    for (int64_t r = lo; r < hi; ++r) put(r, v);
+  }, [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) put(r, zero);
+  });
 }
 
 // d_w[perm[j]] = g[s] . (x[perm[j]] - out[s]) / W_s: one wave per kPoolGradRows positions, every load of the slab loop
@@ -401,18 +350,24 @@ __global__ __launch_bounds__(256) void pool_weight_grad_kernel(const float* embe
   if (j0 >= D) return;
   const int lane = (int)(threadIdx.x & 63);
   int64_t row[kPoolGradRows], seg[kPoolGradRows];         // -1: no such row / no tracklet
-  int64_t s = pool_find(offsets, N, D, j0);
 #pragma unroll
   for (int i = 0; i < kPoolGradRows; ++i) {
     const int64_t j = j0 + i;
     row[i] = seg[i] = -1;
     if (j < D) {
-      while (s < N && pool_clamp(offsets[s + 1], D) <= j) ++s;
-      if (s < N && pool_clamp(offsets[s], D) <= j) seg[i] = s;
       const int64_t p = kPerm ? perm[j] : j;
       if (p >= 0 && p < D) row[i] = p;
     }
   }
+  // each position's owner by the rule of the other kernels, walked over this wave's own positions (on offsets that decrease
+  // it can differ from the 32-row chunks': it depends on where a walk begins).  Unrolled compares: seg[] stays in registers
+  const int64_t j1 = j0 + kPoolGradRows < D ? j0 + kPoolGradRows : D;
+  seg_walk(offsets, N, D, j0, j1, [&](int64_t s, int64_t, int64_t, int64_t lo, int64_t hi) {
+#pragma unroll
+    for (int i = 0; i < kPoolGradRows; ++i) {
+      if (j0 + i >= lo && j0 + i < hi) seg[i] = s;
+    }
+  }, SegNoGap());
   float acc[kPoolGradRows];
   const float *px[kPoolGradRows], *pg[kPoolGradRows], *po[kPoolGradRows];
 #pragma unroll
@@ -455,22 +410,15 @@ __global__ __launch_bounds__(256) void pool_weight_grad_kernel(const float* embe
 static inline bool pool_sizes_ok(int64_t n_rows, int32_t feat_dim) {
   return n_rows >= 0 && n_rows < (1ll << 31) && feat_dim >= 4 && feat_dim <= kPoolMaxF && feat_dim % 4 == 0;
 }
-static inline int64_t pool_chunks(int64_t n_rows) { return (n_rows + kPoolR - 1) / kPoolR; }
-static inline size_t pool_partial_bytes(int64_t n_rows, int32_t feat_dim) {
-  return (size_t)pool_chunks(n_rows) * 2 * (size_t)feat_dim * sizeof(float);
-}
-static inline unsigned pool_grid(int64_t items, int32_t feat_dim) {      // four waves per workgroup
-  const int64_t waves = items * ((feat_dim + kPoolSlab - 1) / kPoolSlab);
-  return (unsigned)blocks_for(waves, 4, INT_MAX);
-}
+static inline unsigned pool_grid(int64_t items, int32_t feat_dim) { return seg_grid(items, (feat_dim + kPoolSlab - 1) / kPoolSlab); }
 // the weighted entry points' workspace: the partial rows, then wpart[chunks][2] and cflag[chunks]
 static inline size_t pool_wpart_offset(int64_t n_rows, int32_t feat_dim) {
-  return mtmc_api::align_up(pool_partial_bytes(n_rows, feat_dim));
+  return mtmc_api::align_up(seg_plane_bytes(n_rows, kPoolR, feat_dim));
 }
 static inline size_t pool_weighted_bytes(int64_t n_rows, int32_t feat_dim) {
-  return pool_wpart_offset(n_rows, feat_dim) + (size_t)pool_chunks(n_rows) * 3 * sizeof(float);
+  return pool_wpart_offset(n_rows, feat_dim) + (size_t)seg_chunks(n_rows, kPoolR) * 3 * sizeof(float);
 }
-// what the weighted entry points check first: MTMC_OK, or the refusal with its text
+// what every entry point checks first: MTMC_OK, or the refusal with its text
 static inline int pool_args(const char* entry, int64_t n_rows, int32_t feat_dim, int64_t n_tracklets) {
   if (!pool_sizes_ok(n_rows, feat_dim))
     return mtmc_api::fail(MTMC_E_ARG, "%s: n_rows must be in [0, 2^31) and feat_dim a multiple of 4 in [4, %d]", entry, kPoolMaxF);
@@ -497,7 +445,7 @@ int32_t mtmc_pool_chunk_rows(void) { return mtmc::kPoolR; }
 
 size_t mtmc_pool_tracklets_workspace_bytes(int64_t n_rows, int32_t feat_dim) {
   if (!mtmc::pool_sizes_ok(n_rows, feat_dim)) return 0;
-  return mtmc_api::align_up(mtmc::pool_partial_bytes(n_rows, feat_dim) + 1);
+  return mtmc_api::align_up(mtmc::seg_plane_bytes(n_rows, mtmc::kPoolR, feat_dim) + 1);
 }
 
 int32_t mtmc_pool_tracklets(const float* embeds, int64_t row_stride, int64_t n_rows, int32_t feat_dim, const int64_t* offsets,
@@ -505,21 +453,19 @@ int32_t mtmc_pool_tracklets(const float* embeds, int64_t row_stride, int64_t n_r
                             void* stream) {
   using namespace mtmc;
   using mtmc_api::fail;
-  if (!pool_sizes_ok(n_rows, feat_dim))
-    return fail(MTMC_E_ARG, "pool_tracklets: n_rows must be in [0, 2^31) and feat_dim a multiple of 4 in [4, %d]", kPoolMaxF);
-  if (n_tracklets < 0 || n_tracklets >= (1ll << 31)) return fail(MTMC_E_ARG, "pool_tracklets: n_tracklets must be in [0, 2^31)");
+  if (const int rc = pool_args("pool_tracklets", n_rows, feat_dim, n_tracklets)) return rc;
   if (n_tracklets == 0 || n_rows == 0) return MTMC_OK;
   if (!embeds || !offsets || !out) return fail(MTMC_E_ARG, "pool_tracklets: NULL embeds, offsets or out");
-  if (((uintptr_t)embeds & 15) || (row_stride & 3) || row_stride < feat_dim)
+  if (!pool_rows_ok(embeds, row_stride, feat_dim))
     return fail(MTMC_E_ARG, "pool_tracklets: embeds must be 16-byte aligned with a row stride that is a multiple of 4 and >= feat_dim");
   if (((uintptr_t)out & 15) || ((uintptr_t)offsets & 7) || ((uintptr_t)info & 3) || ((uintptr_t)workspace & 15))
     return fail(MTMC_E_ARG, "pool_tracklets: out and workspace must be 16-byte, offsets 8-byte and info 4-byte aligned");
-  const size_t need = pool_partial_bytes(n_rows, feat_dim);
+  const size_t need = seg_plane_bytes(n_rows, kPoolR, feat_dim);
   if (!workspace || workspace_bytes < need)
     return fail(MTMC_E_ARG, "pool_tracklets: workspace has %zu bytes, %zu needed (mtmc_pool_tracklets_workspace_bytes)", workspace_bytes, need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(pool_chunks_kernel, dim3(pool_grid(pool_chunks(n_rows), feat_dim)), dim3(256), 0, s, embeds, row_stride,
+  hipLaunchKernelGGL(pool_chunks_kernel, dim3(pool_grid(seg_chunks(n_rows, kPoolR), feat_dim)), dim3(256), 0, s, embeds, row_stride,
                      n_rows, (int)feat_dim, offsets, n_tracklets, out, partial, reinterpret_cast<int*>(info));
   hipLaunchKernelGGL(pool_finish_kernel, dim3(pool_grid(n_tracklets, feat_dim)), dim3(256), 0, s, n_rows, (int)feat_dim, offsets,
                      n_tracklets, out, (const float*)partial, reinterpret_cast<int*>(info));
@@ -530,15 +476,12 @@ int32_t mtmc_pool_tracklets_backward(const float* grad_out, int64_t n_rows, int3
                                      int64_t n_tracklets, float* grad_embeds, int64_t grad_row_stride, void* stream) {
   using namespace mtmc;
   using mtmc_api::fail;
-  if (!pool_sizes_ok(n_rows, feat_dim))
-    return fail(MTMC_E_ARG, "pool_tracklets_backward: n_rows must be in [0, 2^31) and feat_dim a multiple of 4 in [4, %d]", kPoolMaxF);
-  if (n_tracklets < 0 || n_tracklets >= (1ll << 31)) return fail(MTMC_E_ARG, "pool_tracklets_backward: n_tracklets must be in [0, 2^31)");
+  if (const int rc = pool_args("pool_tracklets_backward", n_rows, feat_dim, n_tracklets)) return rc;
   if (n_tracklets == 0 || n_rows == 0) return MTMC_OK;
   if (!grad_out || !offsets || !grad_embeds) return fail(MTMC_E_ARG, "pool_tracklets_backward: NULL grad_out, offsets or grad_embeds");
-  if (((uintptr_t)grad_out & 15) || ((uintptr_t)grad_embeds & 15) || ((uintptr_t)offsets & 7) || (grad_row_stride & 3) ||
-      grad_row_stride < feat_dim)
+  if (((uintptr_t)grad_out & 15) || ((uintptr_t)offsets & 7) || !pool_rows_ok(grad_embeds, grad_row_stride, feat_dim))
     return fail(MTMC_E_ARG, "pool_tracklets_backward: grad_out and grad_embeds must be 16-byte aligned, the row stride a multiple of 4 and >= feat_dim");
-  hipLaunchKernelGGL(pool_backward_kernel, dim3(pool_grid(pool_chunks(n_rows), feat_dim)), dim3(256), 0,
+  hipLaunchKernelGGL(pool_backward_kernel, dim3(pool_grid(seg_chunks(n_rows, kPoolR), feat_dim)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), grad_out, n_rows, (int)feat_dim, offsets, n_tracklets, grad_embeds,
                      grad_row_stride);
   return mtmc_api::launched("pool_tracklets_backward");
@@ -569,9 +512,9 @@ int32_t mtmc_pool_tracklets_weighted(const float* embeds, int64_t row_stride, in
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(workspace);
   float* wpart = reinterpret_cast<float*>(static_cast<char*>(workspace) + pool_wpart_offset(n_rows, feat_dim));
-  int* cflag = reinterpret_cast<int*>(wpart + 2 * pool_chunks(n_rows));
+  int* cflag = reinterpret_cast<int*>(wpart + 2 * seg_chunks(n_rows, kPoolR));
   int* inf = reinterpret_cast<int*>(info);
-  POOL_LAUNCH_WP(pool_chunks_wp_kernel, perm, weights, dim3(pool_grid(pool_chunks(n_rows), feat_dim)), s, embeds, row_stride, n_rows,
+  POOL_LAUNCH_WP(pool_chunks_wp_kernel, perm, weights, dim3(pool_grid(seg_chunks(n_rows, kPoolR), feat_dim)), s, embeds, row_stride, n_rows,
                  (int)feat_dim, offsets, n_tracklets, perm, weights, out, wsum, partial, wpart, cflag, inf);
   const dim3 grid(pool_grid(n_tracklets, feat_dim));
   if (perm)
@@ -595,7 +538,7 @@ int32_t mtmc_pool_tracklets_weighted_backward(const float* grad_out, int64_t n_r
     return fail(MTMC_E_ARG, "pool_tracklets_weighted_backward: grad_out and grad_embeds must be 16-byte aligned, the row stride a multiple of 4 and >= feat_dim");
   if (((uintptr_t)offsets & 7) || ((uintptr_t)perm & 7) || ((uintptr_t)weights & 3) || ((uintptr_t)wsum & 3))
     return fail(MTMC_E_ARG, "pool_tracklets_weighted_backward: offsets and perm must be 8-byte, weights and wsum 4-byte aligned");
-  POOL_LAUNCH_WP(pool_backward_wp_kernel, perm, weights, dim3(pool_grid(pool_chunks(n_rows), feat_dim)),
+  POOL_LAUNCH_WP(pool_backward_wp_kernel, perm, weights, dim3(pool_grid(seg_chunks(n_rows, kPoolR), feat_dim)),
                  static_cast<hipStream_t>(stream), grad_out, n_rows, (int)feat_dim, offsets, n_tracklets, perm, weights, wsum,
                  grad_embeds, grad_row_stride);
   return mtmc_api::launched("pool_tracklets_weighted_backward");
@@ -614,7 +557,7 @@ int32_t mtmc_pool_tracklets_weight_grad(const float* embeds, int64_t row_stride,
     return fail(MTMC_E_ARG, "pool_tracklets_weight_grad: embeds, grad_out and out must be 16-byte aligned, the row stride a multiple of 4 and >= feat_dim");
   if (((uintptr_t)offsets & 7) || ((uintptr_t)perm & 7) || ((uintptr_t)wsum & 3) || ((uintptr_t)grad_weights & 3))
     return fail(MTMC_E_ARG, "pool_tracklets_weight_grad: offsets and perm must be 8-byte, wsum and grad_weights 4-byte aligned");
-  const dim3 grid((unsigned)blocks_for((n_rows + kPoolGradRows - 1) / kPoolGradRows, 4, INT_MAX));
+  const dim3 grid(seg_grid(seg_chunks(n_rows, kPoolGradRows), 1));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (perm)
     hipLaunchKernelGGL(pool_weight_grad_kernel<true>, grid, dim3(256), 0, s, embeds, row_stride, n_rows, (int)feat_dim, offsets,

@@ -9,6 +9,7 @@
 // repeatable forward of the same three: a segmented reduction over a stable grouping of the rows (group_index.hip).
 #include "api_error.h"
 #include "kernels.h"
+#include "seg_walk.h"
 #include <limits.h>
 
 namespace mtmc {
@@ -266,8 +267,8 @@ static void launch_scatter_backward(const float* g, const int64_t* arg, const in
 // ---- the repeatable forward: a segmented reduction over a grouping (group_index.hip) ----
 // perm [E] lists the source rows group by group, offsets [N + 1] cut its POSITIONS: out[g] reduces the rows perm[j],
 // offsets[g] <= j < offsets[g + 1].  No fill, no float atomic, no count buffer: every output element has one writer and every
-// sum ONE ORDER, fixed by (E, C, offsets) alone:
-//   * the positions are cut into chunks of kSegR = 64; one wave per chunk (and per slab of 64 lanes' columns);
+// sum ONE ORDER, fixed by (E, C, offsets) alone.  The decomposition is seg_walk.h's, with chunks of kSegR = 64 positions and
+// slabs of 64 lanes' columns:
 //   * a lane holds W columns (4 when C % 4 == 0, else 1) of one row: U = C / W lanes cover a row, rounded up to a power of two
 //     U' <= 64, so a wave covers P = 64 / U' rows at a time (C = 4: 64 rows, C = 32: 8 rows; C > 256 or 64: one row, in
 //     slabs).  The same lanes hold the same columns whether the loads are 16-byte ones or, on unaligned pointers, four
@@ -275,24 +276,12 @@ static void launch_scatter_backward(const float* g, const int64_t* arg, const in
 //   * the piece [lo, hi) of a group inside a chunk: sub-row q = lane / U' adds positions lo + q, lo + q + P, ... in that order,
 //     starting from -0.0 (x + -0.0 = x for every x, so a group of one row is a copy of that row), then the P sub-rows fold in
 //     a butterfly, partner q ^ (P / 2) first and q ^ 1 last;
-//   * a group inside one chunk is finished there; a group that crosses chunks leaves a partial per chunk (slot 1, "tail", in
-//     its first chunk, slot 0, "head", in the others), and scatter_seg_finish_kernel, one wave per (group, slab), folds the
-//     list tail, head, head, ... in chunk order by the same rule (sub-row q takes items q, q + P, ...; then the butterfly).
+//   * scatter_seg_finish_kernel folds the list tail, head, head, ... of a crossing group by the same rule (sub-row q takes
+//     items q, q + P, ...; then the butterfly).
 //   mean divides the sum by (float)max(offsets[g + 1] - offsets[g], 1); max compares float_key and keeps the smallest source
-//   row of the maximum, which is order-free.  A perm entry outside [0, E) names no row.  Offsets are clamped into [0, E] before
-//   they index anything.  (A crossing group all of whose entries name no row sums to -0.0.)
+//   row of the maximum, which is order-free.  A perm entry outside [0, E) names no row.  (A crossing group all of whose
+//   entries name no row sums to -0.0.)
 constexpr int kSegR = 64;
-
-__device__ __forceinline__ int64_t seg_clamp(int64_t v, int64_t E) { return v < 0 ? 0 : (v > E ? E : v); }
-// the largest s in [0, N-1] with offsets[s] <= r (0 if none), as pool_find of pool_tracklets.hip
-__device__ __forceinline__ int64_t seg_find(const int64_t* offsets, int64_t N, int64_t E, int64_t r) {
-  int64_t lo = 0, hi = N - 1;
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if (seg_clamp(offsets[mid], E) <= r) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // what a lane carries: W sums, or W (key, source row) pairs
 template <int W, bool MAX> struct SegAcc {
@@ -346,10 +335,10 @@ struct SegArgs {
 // which (item, columns, sub-row) this lane works on; false: the wave has no item
 struct SegLane { int64_t item, col; int q; bool live; };
 template <int W> __device__ __forceinline__ bool seg_lane(const SegArgs& a, int64_t items, SegLane* l) {
-  const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  int slab;
+  seg_wave(a.slabs, &l->item, &slab);
   const int lane = threadIdx.x & 63;
-  l->item = w / a.slabs;
-  const int64_t unit = (w - l->item * a.slabs) * 64 + (lane & ((1 << a.lg_up) - 1));
+  const int64_t unit = (int64_t)slab * 64 + (lane & ((1 << a.lg_up) - 1));
   l->q = lane >> a.lg_up;
   l->live = unit < a.C / W;
   l->col = l->live ? unit * W : 0;
@@ -376,20 +365,16 @@ __device__ __forceinline__ void seg_finish_row(const SegArgs& a, const SegLane& 
 template <int W, bool MAX, bool AL>
 __global__ __launch_bounds__(256) void scatter_seg_chunks_kernel(SegArgs a) {
   SegLane l;
-  if (!seg_lane<W>(a, (a.E + kSegR - 1) / kSegR, &l)) return;
+  if (!seg_lane<W>(a, seg_chunks(a.E, kSegR), &l)) return;
   const int up = 1 << a.lg_up, P = 64 >> a.lg_up, lane = threadIdx.x & 63;
-  const int64_t c = l.item, r0 = c * kSegR, r1 = r0 + kSegR < a.E ? r0 + kSegR : a.E;
+  const int64_t c = l.item, r0 = c * kSegR, r1 = seg_chunk_end(r0, kSegR, a.E);
   int row = -1;                                            // of position r0 + lane; -1: names no row
   if (r0 + lane < r1) {
     const int64_t p = a.perm[r0 + lane];
     if (p >= 0 && p < a.E) row = (int)p;                   // E < 2^31
   }
-  int64_t cur = r0;
-  for (int64_t s = seg_find(a.offsets, a.N, a.E, r0); s < a.N && cur < r1;) {
-    const int64_t ga = seg_clamp(a.offsets[s], a.E), gb = seg_clamp(a.offsets[s + 1], a.E);
-    if (gb <= cur) { ++s; continue; }                      // empty, inverted or behind us: the finish kernel's
-    const int64_t lo = ga > cur ? ga : cur, hi = gb < r1 ? gb : r1;
-    if (lo >= r1) break;
+  for (SegCursor<const int64_t*> w(a.offsets, a.N, a.E, r0, r1); w.next();) {
+    const int64_t s = w.s, ga = w.a, gb = w.b, lo = w.lo, hi = w.hi;
     SegAcc<W, MAX> acc;
     acc.clear((int)a.E);
     const int end = (int)(hi - r0);
@@ -417,14 +402,14 @@ __global__ __launch_bounds__(256) void scatter_seg_chunks_kernel(SegArgs a) {
       }
     }
     acc.fold(up);
-    if (ga >= r0 && gb <= r1) {
+    if (seg_inside(ga, gb, r0, r1)) {
       if (!any) {                                          // no entry named a row: the row nobody writes
 #pragma unroll
         for (int k = 0; k < W; ++k) acc.v[k] = 0.f;
       }
       seg_finish_row<W, MAX, AL>(a, l, s, gb - ga, acc);
     } else if (l.q == 0 && l.live) {
-      const int64_t at = (c * 2 + (ga < r0 ? 0 : 1)) * a.C + l.col;
+      const int64_t at = seg_slot(c, ga, r0) * a.C + l.col;
       if (MAX) {
 #pragma unroll
         for (int k = 0; k < W; ++k) {
@@ -435,9 +420,6 @@ __global__ __launch_bounds__(256) void scatter_seg_chunks_kernel(SegArgs a) {
         seg_store<W, AL>(a.partial + at, acc.v);
       }
     }
-    cur = hi;
-    if (gb > r1) break;
-    ++s;
   }
 }
 
@@ -455,11 +437,11 @@ __global__ __launch_bounds__(256) void scatter_seg_finish_kernel(SegArgs a) {
     seg_finish_row<W, MAX, AL>(a, l, s, 1, acc);
     return;
   }
-  const int64_t c0 = ga / kSegR, c1 = (gb - 1) / kSegR;
+  const int64_t c0 = seg_first_chunk(ga, kSegR), c1 = seg_last_chunk(gb, kSegR);
   if (c0 == c1) return;                                    // finished inside its chunk
   const int64_t items = c1 - c0 + 1;                       // the tail of chunk c0, then the heads of c0 + 1 .. c1
   for (int64_t i = l.q; i < items && l.live; i += P) {
-    const int64_t at = (i == 0 ? c0 * 2 + 1 : (c0 + i) * 2) * a.C + l.col;
+    const int64_t at = (i == 0 ? seg_tail(c0) : seg_head(c0 + i)) * a.C + l.col;
     float v[W];
     seg_load<W, AL>(a.partial + at, v);
 #pragma unroll
@@ -471,22 +453,20 @@ __global__ __launch_bounds__(256) void scatter_seg_finish_kernel(SegArgs a) {
   seg_finish_row<W, MAX, AL>(a, l, s, gb - ga, acc);
 }
 
-static inline int64_t seg_chunks(int64_t n_src) { return (n_src + kSegR - 1) / kSegR; }
 static inline size_t seg_parg_offset(int64_t n_src, int64_t n_cols) {
-  return ((size_t)seg_chunks(n_src) * 2 * (size_t)n_cols * sizeof(float) + 255) / 256 * 256;
+  return (seg_plane_bytes(n_src, kSegR, n_cols) + 255) / 256 * 256;
 }
 static inline bool seg_sizes_ok(int64_t n_src, int64_t n_cols) {
   return n_src >= 0 && n_src < (1ll << 31) && n_cols >= 1 && n_cols < (1ll << 31);
 }
 static inline size_t seg_bytes(int64_t n_src, int64_t n_cols) {
-  return seg_parg_offset(n_src, n_cols) + (size_t)seg_chunks(n_src) * 2 * (size_t)n_cols * sizeof(int64_t) + 256;
+  return seg_parg_offset(n_src, n_cols) + (size_t)seg_chunks(n_src, kSegR) * 2 * (size_t)n_cols * sizeof(int64_t) + 256;
 }
 
 template <int W, bool MAX, bool AL> static void launch_scatter_seg_as(const SegArgs& a, hipStream_t s) {
   if (a.E > 0)
-    hipLaunchKernelGGL((scatter_seg_chunks_kernel<W, MAX, AL>), dim3(blocks_for(seg_chunks(a.E) * a.slabs, 4, INT_MAX)), dim3(256),
-                       0, s, a);
-  hipLaunchKernelGGL((scatter_seg_finish_kernel<W, MAX, AL>), dim3(blocks_for(a.N * a.slabs, 4, INT_MAX)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((scatter_seg_chunks_kernel<W, MAX, AL>), dim3(seg_grid(seg_chunks(a.E, kSegR), a.slabs)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((scatter_seg_finish_kernel<W, MAX, AL>), dim3(seg_grid(a.N, a.slabs)), dim3(256), 0, s, a);
 }
 
 // mode 0 add, 1 mean, 2 max; dim_size >= 1

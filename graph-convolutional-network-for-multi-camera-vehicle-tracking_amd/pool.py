@@ -56,9 +56,9 @@ def _usable(t: torch.Tensor) -> torch.Tensor:
     return t if ok or t.numel() == 0 else t.contiguous()
 
 
-def _forward_raw(embeds: torch.Tensor, offsets_dev: torch.Tensor, out=None, info=None) -> torch.Tensor:
-    """The raw library call: embeds [D, F] float32, offsets_dev [N+1] int64 on the same device.  `out` [N, F] (contiguous) and
-    `info` [4] int32 are written when given.  Nothing is read back."""
+def _forward_call(entry, embeds, offsets_dev, out, info, wsum=None, extra=()):
+    """What the two forward entry points share: `out` [N, F] and `info` [4] made or checked, the early-out of a call in
+    which the library launches nothing, the workspace, the call.  `wsum` and `extra` (perm, weights) go to the weighted one."""
     d, f = embeds.shape
     n = offsets_dev.numel() - 1
     dev = embeds.device
@@ -68,24 +68,26 @@ def _forward_raw(embeds: torch.Tensor, offsets_dev: torch.Tensor, out=None, info
         raise RuntimeError("mtmc_mpn.pool_tracklets: out must be a contiguous float32 [N, F] tensor on the device of embeds")
     if info is None:
         info = torch.empty(_lib.POOL_INFO, dtype=torch.int32, device=dev)
+    results = [out] if wsum is None else [out, wsum]
     if n == 0 or d == 0:                       # the library launches nothing
-        out.zero_()
-        info.zero_()
+        for t in results + [info]:
+            t.zero_()
         return out
     embeds = _usable(embeds)
     lib = _lib.load()
-    need = lib.mtmc_pool_tracklets_workspace_bytes(d, f)
+    need = getattr(lib, entry + "_workspace_bytes")(d, f)
     if need == 0:
         raise RuntimeError("mtmc_mpn.pool_tracklets: unsupported size")
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _call.run(dev, lib.mtmc_pool_tracklets, embeds.data_ptr(), embeds.stride(0), d, f, offsets_dev.data_ptr(), n, out.data_ptr(),
-              info.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
+    _call.run(dev, getattr(lib, entry), embeds.data_ptr(), embeds.stride(0), d, f, offsets_dev.data_ptr(), n,
+              *[None if t is None else t.data_ptr() for t in extra], *[t.data_ptr() for t in results], info.data_ptr(),
+              ws.data_ptr(), ws.numel(), _call.stream(dev))
     return out
 
 
-def _backward_raw(grad_out: torch.Tensor, offsets_dev: torch.Tensor, n_rows: int, out=None) -> torch.Tensor:
-    """grad_out [N, F] float32 -> the gradient [n_rows, F] of the embeddings (written into `out` when given: unit column
-    stride, row stride a multiple of 4)."""
+def _backward_call(entry, grad_out, offsets_dev, n_rows, out, extra=()):
+    """What the two backward entry points share: `out` [n_rows, F] made or checked (unit column stride, row stride a
+    multiple of 4), the early-out, the call.  `extra` (perm, weights, wsum) goes to the weighted one."""
     n, f = grad_out.shape
     dev = grad_out.device
     grad_out = grad_out.contiguous()
@@ -97,9 +99,21 @@ def _backward_raw(grad_out: torch.Tensor, offsets_dev: torch.Tensor, n_rows: int
     if n == 0 or n_rows == 0:
         out.zero_()
         return out
-    _call.run(dev, _lib.load().mtmc_pool_tracklets_backward, grad_out.data_ptr(), n_rows, f, offsets_dev.data_ptr(), n,
-              out.data_ptr(), out.stride(0), _call.stream(dev))
+    _call.run(dev, getattr(_lib.load(), entry), grad_out.data_ptr(), n_rows, f, offsets_dev.data_ptr(), n,
+              *[None if t is None else t.data_ptr() for t in extra], out.data_ptr(), out.stride(0), _call.stream(dev))
     return out
+
+
+def _forward_raw(embeds: torch.Tensor, offsets_dev: torch.Tensor, out=None, info=None) -> torch.Tensor:
+    """The raw library call: embeds [D, F] float32, offsets_dev [N+1] int64 on the same device.  `out` [N, F] (contiguous) and
+    `info` [4] int32 are written when given.  Nothing is read back."""
+    return _forward_call("mtmc_pool_tracklets", embeds, offsets_dev, out, info)
+
+
+def _backward_raw(grad_out: torch.Tensor, offsets_dev: torch.Tensor, n_rows: int, out=None) -> torch.Tensor:
+    """grad_out [N, F] float32 -> the gradient [n_rows, F] of the embeddings (written into `out` when given: unit column
+    stride, row stride a multiple of 4)."""
+    return _backward_call("mtmc_pool_tracklets_backward", grad_out, offsets_dev, n_rows, out)
 
 
 def group_by_index(index: torch.Tensor, num_tracklets: int):
@@ -119,52 +133,15 @@ def _forward_weighted_raw(embeds, offsets_dev, perm=None, weights=None, out=None
     """The raw call of `mtmc_pool_tracklets_weighted`: embeds [D, F] float32, offsets_dev [N+1] int64, perm [D] int64 or
     None, weights [D] float32 (contiguous) or None, all on one device.  Returns (out [N, F], wsum [N]); `info` [4] int32
     is written when given.  Nothing is read back."""
-    d, f = embeds.shape
-    n = offsets_dev.numel() - 1
-    dev = embeds.device
-    if out is None:
-        out = torch.empty((n, f), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (n, f) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise RuntimeError("mtmc_mpn.pool_tracklets: out must be a contiguous float32 [N, F] tensor on the device of embeds")
     if wsum is None:
-        wsum = torch.empty(n, dtype=torch.float32, device=dev)
-    if info is None:
-        info = torch.empty(_lib.POOL_INFO, dtype=torch.int32, device=dev)
-    if n == 0 or d == 0:                       # the library launches nothing
-        out.zero_()
-        wsum.zero_()
-        info.zero_()
-        return out, wsum
-    embeds = _usable(embeds)
-    lib = _lib.load()
-    need = lib.mtmc_pool_tracklets_weighted_workspace_bytes(d, f)
-    if need == 0:
-        raise RuntimeError("mtmc_mpn.pool_tracklets: unsupported size")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _call.run(dev, lib.mtmc_pool_tracklets_weighted, embeds.data_ptr(), embeds.stride(0), d, f, offsets_dev.data_ptr(), n,
-              None if perm is None else perm.data_ptr(), None if weights is None else weights.data_ptr(), out.data_ptr(),
-              wsum.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), _call.stream(dev))
-    return out, wsum
+        wsum = torch.empty(offsets_dev.numel() - 1, dtype=torch.float32, device=embeds.device)
+    return _forward_call("mtmc_pool_tracklets_weighted", embeds, offsets_dev, out, info, wsum, (perm, weights)), wsum
 
 
 def _backward_weighted_raw(grad_out, offsets_dev, n_rows, wsum, perm=None, weights=None, out=None):
     """grad_out [N, F] float32 -> the gradient [n_rows, F] of the embeddings, w_r g[s(r)] / W_s, each row written once
     through `perm` (into `out` when given: unit column stride, row stride a multiple of 4)."""
-    n, f = grad_out.shape
-    dev = grad_out.device
-    grad_out = grad_out.contiguous()
-    if out is None:
-        out = torch.empty((n_rows, f), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (n_rows, f) or out.dtype != torch.float32 or out.device != dev or _usable(out) is not out:
-        raise RuntimeError("mtmc_mpn.pool_tracklets: backward out must be float32 [D, F] with unit column stride and a row "
-                           "stride that is a multiple of 4")
-    if n == 0 or n_rows == 0:
-        out.zero_()
-        return out
-    _call.run(dev, _lib.load().mtmc_pool_tracklets_weighted_backward, grad_out.data_ptr(), n_rows, f, offsets_dev.data_ptr(), n,
-              None if perm is None else perm.data_ptr(), None if weights is None else weights.data_ptr(), wsum.data_ptr(),
-              out.data_ptr(), out.stride(0), _call.stream(dev))
-    return out
+    return _backward_call("mtmc_pool_tracklets_weighted_backward", grad_out, offsets_dev, n_rows, out, (perm, weights, wsum))
 
 
 def _weight_grad_raw(embeds, grad_out, pooled, offsets_dev, wsum, perm=None):
@@ -321,5 +298,3 @@ def pool_tracklets(embeds: torch.Tensor, lengths=None, *, offsets=None, index=No
     if check:
         _raise_on(info, perm is not None)
     return out
-
-
